@@ -390,6 +390,43 @@ def scalars_to_ints(sc):
 PREWARM_S = float(os.environ.get("NCG_BENCH_PREWARM_S", "0.05"))
 PREWARM_DIST_STEPS = 6
 
+DUMP_WHOLE_BYTES = 8 << 20      # --dump-outputs: a per-item output up to this size (as float32) is written whole,
+DUMP_ROWS = 1 << 16              # a larger one as this many rows picked with a fixed seed
+DUMP_SEED = 0x64756D70
+DUMP_MAX_BYTES = 64 << 20
+
+
+class OutputDump:
+    """--dump-outputs DIR: what the timed path computed in its last step, as DIR/<name>.npy in float32 (every byte of a wire-format
+    point / every verdict as one exactly representable value).  A large per-item output keeps the same seeded sample of rows on
+    every run (OutputDump.rows), so two builds can be compared output for output."""
+
+    def __init__(self, path):
+        self.path = path
+        self.arrays = {}
+
+    @staticmethod
+    def rows(n, row_bytes):
+        if n * row_bytes <= DUMP_WHOLE_BYTES or n <= DUMP_ROWS:
+            return np.arange(n, dtype=np.int64)
+        pick = np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False)
+        return np.union1d(pick, [0, 1, 2]).astype(np.int64)       # plus rows 0-2, where the bench plants its edge-case scalars
+
+    def add(self, name, a):
+        self.arrays[name] = np.asarray(a).astype(np.float32)
+
+    def add_rows(self, name, t):
+        """the rows of the device tensor `t`, or a sample of them"""
+        rows = self.rows(t.shape[0], 4 * (t.numel() // max(1, t.shape[0])))
+        self.add(name, t.index_select(0, torch.from_numpy(rows).to(t.device)).cpu().numpy())
+
+    def write(self):
+        total = sum(a.nbytes for a in self.arrays.values())
+        assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES)
+        os.makedirs(self.path, exist_ok=True)
+        for name, a in self.arrays.items():
+            np.save(os.path.join(self.path, name + ".npy"), a)
+
 
 class StepTimes(tuple):
     """(wall seconds, HIP-event milliseconds) of the K timed steps, plus the per-step distributions:
@@ -669,6 +706,9 @@ def main():
     ap.add_argument("--dist-dry-run", action="store_true",
                     help="run the multi-rank code path (nccl process group, the engine's RCCL communicator, sharded / in-flight MSM legs) with a world of ONE "
                          "rank: what a 1-GPU box can execute of `--gpus N`; the line is labelled dist_dry_run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what each workload's timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, at most 64 MB; a fixed, seeded sample of the rows of the large per-item outputs; rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -733,6 +773,7 @@ def main():
     result = {}
     extra = {}
     host = cpu_info() if rank == 0 else {}
+    dump = OutputDump(args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     from oracle import refjs
     ref_ok = rank == 0 and refjs.available()
@@ -769,6 +810,9 @@ def main():
 
         st_secp = time_steps(step, K, W, dist_on)
         wall, ev_ms = st_secp
+        if dump:
+            dump.add_rows("secp256k1_points", out)          # affine wire format, 64 bytes per point
+            dump.add_rows("secp256k1_infinity", inf)
         pstate = power_state(step, dev_index) if (rank == 0 and world == 1 and not args.quick_verify) else None
         wall = max_over_ranks(wall, dist_on, device)
         ev_ms = max_over_ranks(ev_ms, dist_on, device)
@@ -901,6 +945,9 @@ def main():
 
         st_msm = time_steps(step, K, W, dist_on)
         wall, ev_ms = st_msm
+        if dump:
+            dump.add("msm_%s_point" % cname, holder["r"][0])
+            dump.add("msm_%s_infinity" % cname, [holder["r"][1]])
         pstate_m = power_state(step, dev_index, 0.9) if (rank == 0 and world == 1 and not args.quick_verify) else None
         wall = max_over_ranks(wall, dist_on, device)
         expect = sum_over_ranks_bigint(local_expect, BLS_R, dist_on, device)
@@ -1259,6 +1306,8 @@ def main():
 
         st_edk = time_steps(step_ed_k, K, W, dist_on)
         wall_k, ev_ms_k = st_edk
+        if dump:
+            dump.add_rows("ed25519_valid_prehashed", d_ok)
         wall_k = max_over_ranks(wall_k, dist_on, device)
         assert np.array_equal(d_ok.cpu().numpy().astype(bool), expect), "ed25519 verdict mismatch (pre-hashed)"
 
@@ -1267,6 +1316,8 @@ def main():
 
         st_ed = time_steps(step_ed, K, W, dist_on)
         wall, ev_ms = st_ed
+        if dump:
+            dump.add_rows("ed25519_valid", d_ok)
         pstate_e = power_state(step_ed, dev_index, 0.9) if (rank == 0 and world == 1 and not args.quick_verify) else None
         wall = max_over_ranks(wall, dist_on, device)
         got = d_ok.cpu().numpy().astype(bool)
@@ -1350,6 +1401,8 @@ def main():
 
         st_ntt = time_steps(step_ntt, K, W, dist_on)
         wall, ev_ms = st_ntt
+        if dump:
+            dump.add_rows("ntt_fr", y)                      # 32-byte little-endian residues
         wall = max_over_ranks(wall, dist_on, device)
         eng.ntt_dev(bits, 1, om, dev_ptr(y), dev_ptr(z), stream, inverse=True)
         torch.cuda.synchronize()
@@ -1420,6 +1473,8 @@ def main():
                 f.write(json.dumps(result) + "\n")
         except OSError:
             full_path = None
+        if dump:
+            dump.write()
         import bench_compact
         json_out.write(bench_compact.dumps(bench_compact.compact_line(result, full_path and os.path.relpath(full_path, ROOT))) + "\n")
         json_out.flush()

@@ -47,6 +47,13 @@ class HostTwinEngine:
         return self.ht.msm_shard_combine(curve, n_max, slots, POINT_BYTES[curve])
 
 
+def _cpu_barrier(dist):
+    """dist.barrier() asks torch for the machine's accelerator, which opens the GPU where one exists; these ranks are CPU twins
+    and hold no device, so they wait for each other with an all-reduce of one CPU tensor (gloo blocks until every rank is in)."""
+    import torch
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker_windows(rank, world, port, curve_name, n, q, bad_at, c_forced=0, shared=False):
     """window-sharded mode: every rank holds ALL n points and scalars, rank r computes its range of the windows."""
     if c_forced:
@@ -78,7 +85,7 @@ def _worker_windows(rank, world, port, curve_name, n, q, bad_at, c_forced=0, sha
         q.put((rank, wire_to_affine(curve, out) == exp, inf, None))
     except ValueError as e:
         q.put((rank, False, False, str(e)))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 
@@ -120,7 +127,7 @@ def _worker(rank, world, port, curve_name, sizes, q, wrong_n_max, bad_at=None, c
         q.put((rank, wire_to_affine(curve, out) == exp, inf, None))
     except ValueError as e:
         q.put((rank, False, False, str(e)))
-    dist.barrier()
+    _cpu_barrier(dist)
     dist.destroy_process_group()
 
 

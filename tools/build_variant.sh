@@ -2,8 +2,9 @@
 # build_variant.sh <name> <extra flags...> : builds tools/_build/libncg_<name>.so from the current sources with extra flags
 set -e
 NAME=$1; shift
-SRC=/root/repo/noble-curves_amd/csrc
-OUT=/root/repo/tools/_build
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+SRC=$ROOT/noble-curves_amd/csrc
+OUT=$ROOT/tools/_build
 B=${TMPDIR:-/tmp}/abbuild/$NAME
 mkdir -p $B $OUT
 cd $SRC
