@@ -14,6 +14,13 @@ struct CurveSecp {  // src/secp256k1.ts:48-64
   static constexpr int SCALAR_BITS = 256;
   static NCG_DI Fe9<Fe9SecpPR, 1> beta() { return Fe9<Fe9SecpPR, 1>::from_limbs(Fe9SecpPR::BETA); }
   static NCG_DI GlvSplit glv_split(const uint32_t (&k)[8]) { return secp_glv_split(k); }
+  static constexpr bool ODD_HALVES = true;    // secp_glv_make_odd after the split: no was_even fix-ups in the ladder
+  static constexpr bool FUSED_LADDER = false;
+};
+// The same curve with the ladder-local fused formulas (ec_sw.hpp jac_dbl_neg / jac_madd_neg) in mul_var_lane: the batch
+// multiply with the field multiply inlined (mulvar_inl.hip).  Its own name gives its kernels their own symbols.
+struct CurveSecpI : CurveSecp {
+  static constexpr bool FUSED_LADDER = true;
 };
 struct CurveG1 {  // src/bls12-381.ts:134-148; no endomorphism in the reference (and inputs are
   using F = FeBls;  // not subgroup-checked), so none here either (SURVEY 8a gotcha 1)

@@ -217,6 +217,54 @@ NCG_DI Jac<Fe9<PR, B>> jac_add(const Jac<Fe9<PR, B>>& p, const Jac<Fe9<PR, B>>& 
   return {X3, Y3, Z3};
 }
 
+// ----------------------------------------------------------------- Jacobian over Fe9: ladder-local negated forms
+// Every output coordinate is ONE fused expression (fe9.hpp f_mul_mul / f_mul_sqr / f_mul_add / f_sqr_add: one reduction per
+// output, no separate subtraction and normalisation).  Both return the NEGATED result: -Y3 is a sum of two products with no
+// negated operand, Y3 is not.  (X, -Y, Z) is -(X, Y, Z), so the ladder carries the sign and fixes it once at the end.
+//
+// -(2P), dbl-2009-l scaled by 1/2 (the same point: (X, Y, Z) ~ (X/4, Y/8, Z/2)):
+//   S = Y^2, T = X S, L = 3X^2 / 2,  X3 = L^2 - 2T,  -Y3 = L (X3 - T) + S^2,  Z3 = Y Z
+// 3M + 4S in six reductions (L (X3 - T) and S^2 share one) against seven for jac_dbl above.  Bounds: L 2 (f_half),
+// X3 - T 3: L (X3 - T) + S^2 is 2*3 + 1*1 = 7.  Z = 0 stays Z = 0.
+template <class PR, int B>
+NCG_DI Jac<Fe9<PR, B>> jac_dbl_neg(const Jac<Fe9<PR, B>>& p) {
+  auto A = f_sqr(p.X);
+  auto S = f_sqr(p.Y);
+  auto T = p.X * S;
+  auto L = f_half(fe9_norm(A + A + A));
+  auto X3 = f_sqr_add(L, f_neg_lin2(T));
+  auto W = f_mul_sqr(L, X3 - T, S);
+  auto Z3 = p.Y * p.Z;
+  return {X3, W, Z3};
+}
+
+// -(P + Q), Q = (x, y) affine (madd-2007-bl without the 2x scaling, as jac_madd_xy), with the exceptional cases of jac_madd_q:
+//   H = x Z^2 - X, R = y Z^3 - Y (each a product with a linear addend), X3 = R^2 - H^3 - 2V (V = X H^2),
+//   -Y3 = R (X3 - V) + Y H^3,  Z3 = Z H
+// 10 reductions against 11.  Bounds: R (X3 - V) + Y H^3 is 1*3 + B*1 <= 7.  H and R carry the sign of y as passed, so their
+// zero tests are the ones of the point the caller means.
+template <class PR, int B, int BX, int BY>
+NCG_DI Jac<Fe9<PR, B>> jac_madd_neg(const Jac<Fe9<PR, B>>& p, const Fe9<PR, BX>& qx, const Fe9<PR, BY>& qy) {
+  using F = Fe9<PR, B>;
+  if (qx.is_zero() && qy.is_zero()) return {p.X, f_neg(p.Y), p.Z};   // Q = O: -P
+  if (p.is_inf()) return {qx, f_neg(qy), F::one()};                   // P = O: -Q
+  auto Z1Z1 = f_sqr(p.Z);
+  auto Z1Z1Z1 = p.Z * Z1Z1;
+  auto H = f_mul_add(qx, Z1Z1, f_neg_lin(p.X));
+  auto R = f_mul_add(qy, Z1Z1Z1, f_neg_lin(p.Y));
+  if (f_eqz(H)) {
+    if (f_eqz(R)) return jac_dbl_neg(p);  // P == Q
+    return Jac<F>::inf();                 // P == -Q
+  }
+  auto HH = f_sqr(H);
+  auto HHH = H * HH;
+  auto V = p.X * HH;
+  auto X3 = f_sqr_add(R, f_neg_lin(HHH, V));
+  auto W = f_mul_mul(R, X3 - V, p.Y, HHH);
+  auto Z3 = p.Z * H;
+  return {X3, W, Z3};
+}
+
 // ----------------------------------------------------------------- XYZZ
 template <class F>
 NCG_DI Xyzz<F> xyzz_from_affine(const Affine<F>& p) {

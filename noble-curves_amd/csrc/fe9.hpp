@@ -237,6 +237,67 @@ NCG_DI void fe9_sqr_limbs(uint32_t (&r)[9], const uint32_t (&a)[9]) {
   fe9_tail<PR>(r, t, c, (uint32_t)d, t8);
 }
 
+// ---- fused expressions: the terms of two sources go into ONE column pair, so the sum pays one fold and one carry tail
+// (fe9_asm_gen.hpp fe9_blk_{mm,ms,ma,sa}_*).  Operands a, b, f, g by kind:
+//   FE9_MM  a*b + f*g           FE9_MS  a*b + f^2 (g = 2f)
+//   FE9_MA  a*b + f             FE9_SA  a^2 + f   (b = 2a)      f of MA / SA: a linear addend, limb k into column k
+// The column capacity is the product's: every column holds at most the terms of a*b and f*g (their limb-bound products add up),
+// and an addend limb below 2^32 takes a 2^-26 share of the head column's headroom (63 U^2 + 2^32 < 2^64).  Output limbs below
+// 2^29 + 2, as for the product.
+enum Fe9Kind { FE9_MM, FE9_MS, FE9_MA, FE9_SA };
+template <int KIND, int K>
+NCG_DI void fe9_fblk(uint64_t& c, uint64_t& d, const uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&f)[9],
+                     const uint32_t (&g)[9], bool fold, uint32_t u, uint32_t C1) {
+#define NCG_FE9_FCASE(kd, nm, k)                                                                                            \
+  if constexpr (KIND == kd && K == k) {                                                                                     \
+    if (fold) fe9_blk_##nm##_##k##_f(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g), u, C1);  \
+    else fe9_blk_##nm##_##k(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g));                   \
+  }
+#define NCG_FE9_FKIND(kd, nm)                                                                                                  \
+  NCG_FE9_FCASE(kd, nm, 0) NCG_FE9_FCASE(kd, nm, 1) NCG_FE9_FCASE(kd, nm, 2) NCG_FE9_FCASE(kd, nm, 3) NCG_FE9_FCASE(kd, nm, 4) \
+  NCG_FE9_FCASE(kd, nm, 5) NCG_FE9_FCASE(kd, nm, 6) NCG_FE9_FCASE(kd, nm, 7)
+  NCG_FE9_FKIND(FE9_MM, mm) NCG_FE9_FKIND(FE9_MS, ms) NCG_FE9_FKIND(FE9_MA, ma) NCG_FE9_FKIND(FE9_SA, sa)
+#undef NCG_FE9_FKIND
+#undef NCG_FE9_FCASE
+}
+template <int KIND>
+NCG_DI void fe9_fhead(uint64_t& c, uint64_t& d, const uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&f)[9],
+                      const uint32_t (&g)[9]) {
+  if constexpr (KIND == FE9_MM) fe9_blk_mm_head(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g));
+  if constexpr (KIND == FE9_MS) fe9_blk_ms_head(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g));
+  if constexpr (KIND == FE9_MA) fe9_blk_ma_head(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g));
+  if constexpr (KIND == FE9_SA) fe9_blk_sa_head(c, d, NCG_FE9_ARGS9(a), NCG_FE9_ARGS9(b), NCG_FE9_ARGS9(f), NCG_FE9_ARGS9(g));
+}
+// columns 0..7 + their folds: fe9_cols with the fused blocks
+template <class PR, int KIND, int K = 0>
+NCG_DI void fe9_fcols(uint64_t& c, uint64_t& d, uint32_t (&t)[9], const uint32_t (&a)[9], const uint32_t (&b)[9],
+                      const uint32_t (&f)[9], const uint32_t (&g)[9], uint32_t u_prev) {
+  constexpr uint32_t C0 = PR::C0, C1 = PR::C1;
+  if constexpr (K < 8) {
+    fe9_fblk<KIND, K>(c, d, a, b, f, g, K > 0 && C1 != 0, u_prev, C1);
+    const uint32_t u = (uint32_t)d & FE9_MASK;
+    d >>= 29;
+    fe9_mac_k(c, u, C0);
+    t[K] = (uint32_t)c & FE9_MASK;
+    c >>= 29;
+    if constexpr (K == 7) {
+      if (C1) fe9_mac_k(c, u, C1);
+    }
+    fe9_fcols<PR, KIND, K + 1>(c, d, t, a, b, f, g, u);
+  }
+}
+template <class PR, int KIND>
+NCG_DI void fe9_fused_limbs(uint32_t (&r)[9], const uint32_t (&a)[9], const uint32_t (&b)[9], const uint32_t (&f)[9],
+                            const uint32_t (&g)[9]) {
+  uint64_t c, d;
+  fe9_fhead<KIND>(c, d, a, b, f, g);
+  const uint32_t t8 = (uint32_t)d & FE9_MASK;
+  d >>= 29;
+  uint32_t t[9];
+  fe9_fcols<PR, KIND>(c, d, t, a, b, f, g, 0u);
+  fe9_tail<PR>(r, t, c, (uint32_t)d, t8);
+}
+
 // Out-of-line entry points.  The limbs travel as SCALAR arguments: an aggregate argument beyond the
 // first is passed by reference through scratch memory by the AMDGPU calling convention (9 stores + 9
 // loads + their latency per multiply), scalars go in v0..v17.
@@ -399,6 +460,78 @@ NCG_DI Fe9<PR, 1> f_sqr(const Fe9<PR, A>& a) {
     return r;
   }
 }
+
+// ---- fused expressions (fe9_fused_limbs): one reduction for the whole sum, result bound 1.  Bounds as for the product: the
+// limb-bound products of the two sources add up in every column, so A*B + C*D <= 7 (a square counts as C*C, its doubled
+// operand needs C <= 2).  An addend of any bound (<= 7: limbs below 2^32) rides along.
+template <class PR, int KIND, int A, int B, int C, int D>
+NCG_DI Fe9<PR, 1> fe9_fused(const Fe9<PR, A>& a, const Fe9<PR, B>& b, const Fe9<PR, C>& f, const Fe9<PR, D>& g) {
+  Fe9<PR, 1> r;
+  fe9_fused_limbs<PR, KIND>(r.v, a.v, b.v, f.v, g.v);
+  return r;
+}
+// a*b + c*d
+template <class PR, int A, int B, int C, int D>
+NCG_DI Fe9<PR, 1> f_mul_mul(const Fe9<PR, A>& a, const Fe9<PR, B>& b, const Fe9<PR, C>& c, const Fe9<PR, D>& d) {
+  static_assert(A * B + C * D <= 7, "fused a*b + c*d: the two products overflow the 64-bit columns");
+  return fe9_fused<PR, FE9_MM>(a, b, c, d);
+}
+// a*b + c^2
+template <class PR, int A, int B, int C>
+NCG_DI Fe9<PR, 1> f_mul_sqr(const Fe9<PR, A>& a, const Fe9<PR, B>& b, const Fe9<PR, C>& c) {
+  static_assert(C <= 2 && A * B + C * C <= 7, "fused a*b + c^2: the two sources overflow the 64-bit columns");
+  return fe9_fused<PR, FE9_MS>(a, b, c, f_dbl(c));
+}
+// a*b + s, s a lazily reduced linear addend (e.g. f_neg_lin): the carry pass of the product reduces it as well
+template <class PR, int A, int B, int S>
+NCG_DI Fe9<PR, 1> f_mul_add(const Fe9<PR, A>& a, const Fe9<PR, B>& b, const Fe9<PR, S>& s) {
+  static_assert(A * B <= 7, "fused a*b + s: the product overflows the 64-bit columns");
+  return fe9_fused<PR, FE9_MA>(a, b, s, s);
+}
+// a^2 + s
+template <class PR, int A, int S>
+NCG_DI Fe9<PR, 1> f_sqr_add(const Fe9<PR, A>& a, const Fe9<PR, S>& s) {
+  static_assert(A <= 2, "fused a^2 + s: the square overflows the 64-bit columns");
+  return fe9_fused<PR, FE9_SA>(a, f_dbl(a), s, s);
+}
+// linear addends: -s1 - 2*s2, -s1 and -2*s2 as BIAS - (...) (a multiple of p with every limb at least the subtrahend's bound; no
+// literal-zero rule, unlike f_neg: these feed a sum, never a stored coordinate)
+template <class PR, int S1, int S2>
+NCG_DI Fe9<PR, S1 + 2 * S2 + 1> f_neg_lin(const Fe9<PR, S1>& s1, const Fe9<PR, S2>& s2) {
+  Fe9<PR, S1 + 2 * S2 + 1> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.v[i] = PR::BIAS[S1 + 2 * S2][i] - (s1.v[i] + (s2.v[i] << 1));
+  return r;
+}
+template <class PR, int S1>
+NCG_DI Fe9<PR, S1 + 1> f_neg_lin(const Fe9<PR, S1>& s1) {
+  Fe9<PR, S1 + 1> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.v[i] = PR::BIAS[S1][i] - s1.v[i];
+  return r;
+}
+template <class PR, int S2>
+NCG_DI Fe9<PR, 2 * S2 + 1> f_neg_lin2(const Fe9<PR, S2>& s2) {
+  Fe9<PR, 2 * S2 + 1> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.v[i] = PR::BIAS[2 * S2][i] - (s2.v[i] << 1);
+  return r;
+}
+// a / 2 (mod p): add p when a is odd - the parity of the value is that of limb 0 - then shift the limbs right by one, the low
+// bit of limb i + 1 going to bit 28 of limb i.  Limbs below U + 2^29 before the shift, so below U / 2 + 2^28 + 2^28 < 2U after.
+template <class PR>
+NCG_DI Fe9<PR, 2> f_half(const Fe9<PR, 1>& a) {
+  const uint32_t m = 0u - (a.v[0] & 1u);
+  uint32_t t[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) t[i] = a.v[i] + (PR::P[i] & m);
+  Fe9<PR, 2> r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (t[i] >> 1) + ((t[i + 1] & 1u) << 28);
+  r.v[8] = t[8] >> 1;
+  return r;
+}
+
 template <class PR>
 NCG_DI Fe9<PR, 1> fe9_sqr_n(Fe9<PR, 1> a, int n) {
   for (int i = 0; i < n; i++) a = f_sqr(a);

@@ -206,6 +206,58 @@ static int ht_shard_combine_t(int curve, int n_max, int nparts, const uint8_t* s
     default: return -1;                               \
   }
 
+// fused Fe9 expressions at fixed operand bounds (the loosest each admits)
+template <class PR, int A, int B, int C, int D>
+static void ht_fe9_fused_ab(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* r) {
+  Fe9<PR, A> x;
+  Fe9<PR, B> y;
+  Fe9<PR, C> z;
+  Fe9<PR, D> w;
+  for (int i = 0; i < 9; i++) {
+    x.v[i] = a[i];
+    y.v[i] = b[i];
+    z.v[i] = c[i];
+    w.v[i] = d[i];
+  }
+  Fe9<PR, 1> o;
+  if constexpr (A * B + C * D <= 7) {
+    if (op == 0) o = f_mul_mul(x, y, z, w);
+  }
+  if constexpr (C <= 2 && A * B + C * C <= 7) {
+    if (op == 1) o = f_mul_sqr(x, y, z);
+  }
+  if constexpr (A * B <= 7) {
+    if (op == 2) o = f_mul_add(x, y, z);
+  }
+  if constexpr (A <= 2) {
+    if (op == 3) o = f_sqr_add(x, z);
+  }
+  if constexpr (A == 1) {
+    if (op == 4) {
+      const Fe9<PR, 2> h = f_half(x);
+      for (int i = 0; i < 9; i++) r[i] = h.v[i];
+      return;
+    }
+  }
+  for (int i = 0; i < 9; i++) r[i] = o.v[i];
+}
+template <class PR>
+static int ht_fe9_fused_t(int op, int variant, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* r) {
+  switch (variant) {  // decimal digits A B C D
+    case 1111: ht_fe9_fused_ab<PR, 1, 1, 1, 1>(op, a, b, c, d, r); return 0;
+    case 1322: ht_fe9_fused_ab<PR, 1, 3, 2, 2>(op, a, b, c, d, r); return 0;
+    case 3211: ht_fe9_fused_ab<PR, 3, 2, 1, 1>(op, a, b, c, d, r); return 0;
+    case 2311: ht_fe9_fused_ab<PR, 2, 3, 1, 1>(op, a, b, c, d, r); return 0;
+    case 1123: ht_fe9_fused_ab<PR, 1, 1, 2, 3>(op, a, b, c, d, r); return 0;
+    case 3121: ht_fe9_fused_ab<PR, 3, 1, 2, 1>(op, a, b, c, d, r); return 0;
+    case 1327: ht_fe9_fused_ab<PR, 1, 3, 2, 7>(op, a, b, c, d, r); return 0;
+    case 7171: ht_fe9_fused_ab<PR, 7, 1, 7, 1>(op, a, b, c, d, r); return 0;
+    case 1771: ht_fe9_fused_ab<PR, 1, 7, 7, 1>(op, a, b, c, d, r); return 0;
+    case 2171: ht_fe9_fused_ab<PR, 2, 1, 7, 1>(op, a, b, c, d, r); return 0;
+    default: return -1;
+  }
+}
+
 extern "C" {
 
 // field: 0 secp256k1 p, 1 ed25519 p (radix-2^29 lazy form, fe9.hpp); a, b: 9 raw limbs; r: 8 wire words
@@ -220,6 +272,7 @@ int ht_mul_var(int curve, const uint32_t* pts, const uint32_t* scalars, uint32_t
     case CURVE_SECP256K1: ht_mul_var_t<CurveSecp, 4>(pts, scalars, out, out_inf, n); return 0;
     case CURVE_BLS12_381_G1: ht_mul_var_t<CurveG1, 3>(pts, scalars, out, out_inf, n); return 0;
     case 12: ht_mul_var_t<CurveG1E, 4>(pts, scalars, out, out_inf, n); return 0;  // subgroup points only (GLV ladder)
+    case 14: ht_mul_var_t<CurveSecpI, 4>(pts, scalars, out, out_inf, n); return 0;  // the fused-formula ladder of the inlined kernel
     case CURVE_BLS12_381_G2: ht_mul_var_t<CurveG2, 3>(pts, scalars, out, out_inf, n); return 0;
   }
   return -1;
@@ -236,6 +289,53 @@ int ht_field_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_
 }
 
 // GLV split of a 256-bit scalar: out = k1[5] k2[5] k1neg k2neg (12 words)
+int ht_fe9_fused(int field, int op, int variant, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
+                 uint32_t* r) {
+  if (field == 0) return ht_fe9_fused_t<Fe9SecpPR>(op, variant, a, b, c, d, r);
+  if (field == 1) return ht_fe9_fused_t<Fe9EdPR>(op, variant, a, b, c, d, r);
+  return -1;
+}
+
+// the negated ladder formulas of ec_sw.hpp on secp256k1 Jacobian points (27 limbs X, Y, Z at the storage bound 2):
+// op 0: out = jac_dbl_neg(P);  op 1: out = jac_madd_neg(P, qx, qy), qx at bound 2, qy at bound 3 (a negated table entry)
+int ht_jac_neg(int op, const uint32_t* p, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
+  Jac<FeSecp> P;
+  Fe9<Fe9SecpPR, 2> x;
+  Fe9<Fe9SecpPR, 3> y;
+  for (int i = 0; i < 9; i++) {
+    P.X.v[i] = p[i];
+    P.Y.v[i] = p[9 + i];
+    P.Z.v[i] = p[18 + i];
+    x.v[i] = qx[i];
+    y.v[i] = qy[i];
+  }
+  Jac<FeSecp> R;
+  if (op == 0) R = jac_dbl_neg(P);
+  else if (op == 1) R = jac_madd_neg(P, x, y);
+  else return -1;
+  for (int i = 0; i < 9; i++) {
+    out[i] = R.X.v[i];
+    out[9 + i] = R.Y.v[i];
+    out[18 + i] = R.Z.v[i];
+  }
+  return 0;
+}
+
+// secp_glv_split followed by secp_glv_make_odd; layout of ht_glv_split
+int ht_glv_split_odd(const uint32_t* k, uint32_t* out) {
+  uint32_t kk[8];
+  for (int i = 0; i < 8; i++) kk[i] = k[i];
+  GlvSplit s = secp_glv_split(kk);
+  secp_glv_make_odd(s);
+  for (int i = 0; i < 5; i++) {
+    out[i] = s.k1[i];
+    out[5 + i] = s.k2[i];
+  }
+  out[10] = s.k1neg;
+  out[11] = s.k2neg;
+  return 0;
+}
+
 int ht_glv_split(const uint32_t* k, uint32_t* out) {
   uint32_t kk[8];
   for (int i = 0; i < 8; i++) kk[i] = k[i];

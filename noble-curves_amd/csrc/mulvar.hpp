@@ -19,6 +19,8 @@
 // footprint, so wide windows and 3-4 waves/SIMD go together; the default) or in LDS (k_mul_var:
 // limb-major, lane-minor, bank-conflict free for any digit pattern; used when no scratch is given).
 #pragma once
+#include <type_traits>
+
 #include "curves.hpp"
 #include "scalar.hpp"
 
@@ -85,6 +87,13 @@ NCG_DI Jac<typename C::F> mul_var_slow(const uint32_t* __restrict__ pt_wire, con
   }
   return R;
 }
+
+// Curve traits of the ladder (absent = false).  ODD_HALVES: the GLV halves come out odd (secp_glv_make_odd), so there is no
+// was_even fix-up at the end.  FUSED_LADDER: Fe9 ladder with the negated fused formulas jac_dbl_neg / jac_madd_neg.
+template <class C, class = void> struct OddGlvHalves { static constexpr bool value = false; };
+template <class C> struct OddGlvHalves<C, std::void_t<decltype(C::ODD_HALVES)>> { static constexpr bool value = C::GLV && C::ODD_HALVES; };
+template <class C, class = void> struct FusedLadder { static constexpr bool value = false; };
+template <class C> struct FusedLadder<C, std::void_t<decltype(C::FUSED_LADDER)>> { static constexpr bool value = C::FUSED_LADDER; };
 
 template <class C, int W>
 struct MulVarCfg {
@@ -173,8 +182,10 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   // ---- scalar recoding ---------------------------------------------------------------------
   SignedOddWindows<NL, W, M> w1, w2;
   bool neg1 = false, neg2 = false;
+  constexpr bool ODD = OddGlvHalves<C>::value;
   if constexpr (C::GLV) {
     GlvSplit gs = C::glv_split(k);
+    if constexpr (ODD) secp_glv_make_odd(gs);
     w1.template init<5>(gs.k1);
     w2.template init<5>(gs.k2);
     neg1 = gs.k1neg;
@@ -185,6 +196,28 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   const auto beta = C::beta();
 
   // ---- ladder -------------------------------------------------------------------------------
+  // FUSED: every doubling and addition returns the negated result, so R holds -(running point) while `sg` is set; an addition
+  // of +-Q then adds the point with y negated once more when sg is set.  With W doublings and two additions per window the
+  // sign is static per window position; it is fixed once after the loop.
+  constexpr bool FUSED = FusedLadder<C>::value;
+  bool sg = false;
+  auto dbl = [&](const Jac<F>& r) -> Jac<F> {
+    if constexpr (FUSED) {
+      sg = !sg;
+      return jac_dbl_neg(r);
+    } else {
+      return jac_dbl(r);
+    }
+  };
+  auto madd = [&](const Jac<F>& r, const auto& qx, const F& qy, bool ng) -> Jac<F> {
+    if constexpr (FUSED) {
+      const bool s = sg;
+      sg = !sg;
+      return jac_madd_neg(r, qx, f_cneg(qy, ng != s));
+    } else {
+      return jac_madd_q(r, qx, f_cneg(qy, ng));
+    }
+  };
   Jac<F> R = Jac<F>::inf();
 #ifdef __HIP_DEVICE_COMPILE__
   if constexpr (PF && NCG_MUL_INLINE && C::GLV) {
@@ -222,7 +255,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
     for (int i = 0; i < M; i++) {
       if (i > 0) {
 #pragma unroll 1
-        for (int d = 0; d < W; d++) R = jac_dbl(R);
+        for (int d = 0; d < W; d++) R = dbl(R);
       }
 #pragma unroll 1
       for (int e = 0; e < 2; e++) {
@@ -236,14 +269,16 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
         issue(e, entry_of(dn));
         if (e == 0) d1 = dn; else d2 = dn;
         if (e == 1) qx = qx * beta;
-        R = jac_madd_q(R, qx, f_cneg(qy, (d < 0) != ng));
+        R = madd(R, qx, qy, (d < 0) != ng);
       }
     }
     {
       F qx, qy;
       fetch(0, qx, qy);   // entry 0 (both slots hold it now; vmcnt(0) covers slot 1's load too)
-      if (w1.was_even) R = jac_madd_q(R, qx, f_cneg(qy, !neg1));
-      if (w2.was_even) R = jac_madd_q(R, qx * beta, f_cneg(qy, !neg2));
+      if constexpr (!ODD) {
+        if (w1.was_even) R = madd(R, qx, qy, !neg1);
+        if (w2.was_even) R = madd(R, qx * beta, qy, !neg2);
+      }
     }
   } else
 #endif
@@ -251,7 +286,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   for (int i = 0; i < M; i++) {
     if (i > 0) {
 #pragma unroll(NCG_MUL_INLINE ? 1 : W)
-      for (int d = 0; d < W; d++) R = jac_dbl(R);
+      for (int d = 0; d < W; d++) R = dbl(R);
     }
     // one mixed addition per stream
     if constexpr (NCG_MUL_INLINE && C::GLV) {
@@ -266,7 +301,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
         F qx = FieldIO<F>::load_strided(tab + (idx * 2 * TW) * stride, stride);
         const F qy = FieldIO<F>::load_strided(tab + (idx * 2 * TW + TW) * stride, stride);
         if (e == 1) qx = qx * beta;
-        R = jac_madd_q(R, qx, f_cneg(qy, (d < 0) != ng));
+        R = madd(R, qx, qy, (d < 0) != ng);
       }
     } else {
       {
@@ -274,26 +309,29 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
         int e = ((d1 < 0 ? -d1 : d1) - 1) >> 1;
         const F qx = FieldIO<F>::load_strided(tab + (e * 2 * TW) * stride, stride);
         const F qy = FieldIO<F>::load_strided(tab + (e * 2 * TW + TW) * stride, stride);
-        R = jac_madd_q(R, qx, f_cneg(qy, (d1 < 0) != neg1));
+        R = madd(R, qx, qy, (d1 < 0) != neg1);
       }
       if constexpr (C::GLV) {
         int d2 = w2.pop();
         int e = ((d2 < 0 ? -d2 : d2) - 1) >> 1;
         const auto qx = FieldIO<F>::load_strided(tab + (e * 2 * TW) * stride, stride) * beta;
         const F qy = FieldIO<F>::load_strided(tab + (e * 2 * TW + TW) * stride, stride);
-        R = jac_madd_q(R, qx, f_cneg(qy, (d2 < 0) != neg2));
+        R = madd(R, qx, qy, (d2 < 0) != neg2);
       }
     }
   }
   // even scalars were bumped by one: take the extra point back out
-  {
+  if constexpr (!ODD) {
     const F qx = FieldIO<F>::load_strided(tab, stride);
     const F qy = FieldIO<F>::load_strided(tab + TW * stride, stride);
-    if (w1.was_even) R = jac_madd_q(R, qx, f_cneg(qy, !neg1));
+    if (w1.was_even) R = madd(R, qx, qy, !neg1);
     if constexpr (C::GLV) {
-      if (w2.was_even) R = jac_madd_q(R, qx * beta, f_cneg(qy, !neg2));
+      if (w2.was_even) R = madd(R, qx * beta, qy, !neg2);
     }
   }
+  }
+  if constexpr (FUSED) {
+    if (sg) R.Y = f_neg(R.Y);   // the one fix-up of the negated forms (f_neg keeps a literal zero literal)
   }
   // back from the isomorphic curve, then to affine (weierstrass.ts:951-969 toAffine)
   const bool ladder_inf = R.is_inf();  // tested before the product: not every field keeps 0 * Zg literal

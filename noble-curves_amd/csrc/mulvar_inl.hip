@@ -1,8 +1,8 @@
 // secp256k1 batch multiply with the field multiply INLINED into the group-law routines (no call, no
 // argument marshalling through v0..v17; the doubling loop stays rolled so the window body fits the
 // instruction cache).  A/B alternative to the out-of-line build in mulvar.hip, selected by
-// NCG_SECP_W=25x (x = waves/SIMD requested).  The curve twin gives the kernels their own names: both
-// translation units ship their own code object.
+// NCG_SECP_W=25x (x = waves/SIMD requested).  The curve twin CurveSecpI (curves.hpp) gives the kernels their own names -
+// both translation units ship their own code object - and selects the fused ladder formulas.
 #define NCG_MUL_INLINE 1
 #include "mulvar.hpp"
 #include "knobs.hpp"
@@ -11,8 +11,6 @@
 #include <cstdlib>
 
 namespace ncg {
-
-struct CurveSecpI : CurveSecp {};
 
 hipError_t mul_var_secp_inline(int minw, const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, int n,
                                uint32_t* jac_tmp, hipStream_t st) {

@@ -9,6 +9,9 @@
 // decomposition k = k1 + lambda*k2 (mod n) with |k1|,|k2| < 2^128 - and since secp256k1 has
 // cofactor 1 the resulting group element is identical (SURVEY 8a gotcha 1).
 #pragma once
+#ifndef __HIP_DEVICE_COMPILE__
+#include <cassert>
+#endif
 #include "fp.hpp"
 
 namespace ncg {
@@ -126,6 +129,58 @@ NCG_DI GlvSplit secp_glv_split(const uint32_t (&k)[8]) {
   return s;
 }
 
+// Both halves odd, for the secp256k1 ladder: SignedOddWindows then needs no "+1 now, subtract P at the end" fix-up.
+// The lattice vectors v1 = (a1, b1) and v2 = (a2, b2) of the split satisfy a + b*lambda = 0 (mod n), so adding one of them
+// to (k1, k2) keeps k = k1 + lambda*k2 (mod n).  Their parities are v1 (odd, odd), v2 (even, odd) and - with the secp256k1
+// basis, where a1 = b2 and a1 - a2 = b1 - the difference v1 - v2 = (b1, -a2) is (odd, even).  So for the parities of
+// (k1, k2): (even, even) + v1, (even, odd) + (v1 - v2), (odd, even) + v2, (odd, odd) nothing.
+// Bound: secp_glv_split gives |ki| < 2^128 (the window count of the GLV ladder rests on it), and every entry of v1, v2 and
+// v1 - v2 is below 2^128.12 in magnitude (|b1| < 2^127.84, |a2| < 2^128.12), so the adjusted |ki| < 2^128 + 2^128.12 < 2^130:
+// five limbs still hold them and SignedOddWindows<5, 4, 33> (132 bits) takes them without the +1.
+// secp_glv_split's own output is unchanged (ht_glv_split pins it); this is a separate step.
+NCG_DI void secp_glv_make_odd(GlvSplit& s) {
+  uint32_t x1[6], x2[6], va[6], vb[6];
+  const bool e1 = (s.k1[0] & 1u) == 0, e2 = (s.k2[0] & 1u) == 0;   // the parity of |k| is that of k
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    x1[i] = i < 5 ? s.k1[i] : 0u;
+    x2[i] = i < 5 ? s.k2[i] : 0u;
+  }
+  if (s.k1neg) mp_neg<6>(x1);
+  if (s.k2neg) mp_neg<6>(x2);
+  uint32_t a1[6], mb1n[6], a2[6], a2n[6], b2[6];   // a1, b1 = -MB1, a2, -a2, b2 as 6-limb two's complement
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    a1[i] = i < 5 ? SecpGlv::A1[i] : 0u;
+    mb1n[i] = i < 5 ? SecpGlv::MB1[i] : 0u;
+    a2[i] = i < 5 ? SecpGlv::A2[i] : 0u;
+    a2n[i] = a2[i];
+    b2[i] = i < 5 ? SecpGlv::B2[i] : 0u;
+  }
+  mp_neg<6>(mb1n);
+  mp_neg<6>(a2n);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    va[i] = e1 ? (e2 ? a1[i] : mb1n[i]) : (e2 ? a2[i] : 0u);
+    vb[i] = e1 ? (e2 ? mb1n[i] : a2n[i]) : (e2 ? b2[i] : 0u);
+  }
+  mp_add<6>(x1, x1, va);
+  mp_add<6>(x2, x2, vb);
+  s.k1neg = (x1[5] >> 31) != 0;
+  s.k2neg = (x2[5] >> 31) != 0;
+  if (s.k1neg) mp_neg<6>(x1);
+  if (s.k2neg) mp_neg<6>(x2);
+#ifndef __HIP_DEVICE_COMPILE__
+  assert((x1[0] & 1u) && (x2[0] & 1u));
+  assert(x1[5] == 0 && x2[5] == 0 && x1[4] < 4u && x2[4] < 4u);   // |ki| < 2^130
+#endif
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    s.k1[i] = x1[i];
+    s.k2[i] = x2[i];
+  }
+}
+
 // Signed-odd fixed-window recoding (Joye-Tunstall style, closed form).
 // For an odd integer k < 2^L (L = M*W) write k = sum_{i<M} d_i 2^(W i) with every d_i odd,
 // |d_i| <= 2^W - 1:  d_i = 2*((k~ >> (W i + 1)) & (2^W - 1)) - (2^W - 1),  k~ = k | 2^L.
@@ -143,6 +198,18 @@ struct SignedOddWindows {
     uint32_t t[NL + 1];
 #pragma unroll
     for (int i = 0; i < NL + 1; i++) t[i] = i < NK ? k[i] : 0u;
+#ifndef __HIP_DEVICE_COMPILE__
+    {  // k + 1 < 2^L, L = W*M: no bit at or above L, and not all of the L bits set
+      constexpr int L = W * M;
+      bool high = false, all = true;
+      for (int b = 0; b < 32 * (NL + 1); b++) {
+        const bool bit = (t[b / 32] >> (b % 32)) & 1u;
+        if (b >= L) high = high || bit;
+        else all = all && bit;
+      }
+      assert(!high && !all);
+    }
+#endif
     was_even = (t[0] & 1u) == 0;
     if (was_even) {  // k + 1 (k even: no carry out of bit 0)
       t[0] |= 1u;
