@@ -455,7 +455,15 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * each, values up to the top of the lazy bounds (a, c < 4096 p; b, d < 4096 p for op 0, 2048 p for op 6);
  * field 4 = the lane-paired Fp2 form: every element c0 then c1 (28 limbs), a, c < 4096 p (2048 p for op 1), b, d <
  * 2048 p (op 0) / 1024 p (op 6).  ops 0 a*b, 1 a^2, 6 a*b - c*d (the fused reduction); out = canonical wire words
- * of the result taken out of Montgomery form (12, or 12 + 12 for Fp2). */
+ * of the result taken out of Montgomery form (12, or 12 + 12 for Fp2).
+ * field 5 / 6 = the fused Fe9 expressions (fe9.hpp) over secp256k1 / ed25519 p: a = [a, c], b = [b, d], 9 RAW limbs
+ * each (18 words); ops 0 a*b + c*d, 1 a*b + c^2, 2 a*b + c, 3 a^2 + c, 4 a/2; `variant` = decimal A B C D bound digits
+ * (1111 1322 3211 2311 1123 3121 1327 7171 1771 2171; a combination the op does not admit leaves out zero); out = 9 RAW
+ * limbs of the result.
+ * field 7 = the secp256k1 ladder pieces, RAW limbs in and out: a = 27 words, b = 18 words, out = 27 words.  op 0
+ * jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) (ec_sw.hpp) with P = a (X, Y, Z at bound 2), qx = b[0..9) at bound 2,
+ * qy = b[9..18) at bound 3: out = X, Y, Z; op 2 secp_glv_split + secp_glv_make_odd (scalar.hpp) of the scalar in
+ * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg. */
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
 #ifdef __cplusplus

@@ -1864,20 +1864,23 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
 
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (field < 0 || field > 4) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 7) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   if (n == 0) return NCG_OK;
   if (n > (1u << 24) || !a || !b || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: bad arguments");
-  // words per item: fe9 9 in / 8 out; Fe29 from wire 12 / 12; Fe29 raw limbs [a, c] 28 / 12; lane-paired Fp2 raw [a, c] 56 / 24
-  const size_t in_w = field == 4 ? 56 : field == 3 ? 28 : field == 2 ? 12 : 9, out_w = field == 4 ? 24 : field >= 2 ? 12 : 8;
+  // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
+  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27
+  static const size_t wa[8] = {9, 9, 12, 28, 56, 18, 18, 27}, wb[8] = {9, 9, 12, 28, 56, 18, 18, 18},
+                      wo[8] = {8, 8, 12, 12, 24, 9, 9, 27};
+  const size_t in_wa = wa[field], in_wb = wb[field], out_w = wo[field];
   NCG_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t in_b = (n * in_w * 4 + 255) & ~(size_t)255, out_b = n * out_w * 4;
-  int rc = ensure_scratch(ctx, 2 * in_b + out_b + 1024);
+  const size_t in_ba = (n * in_wa * 4 + 255) & ~(size_t)255, in_bb = (n * in_wb * 4 + 255) & ~(size_t)255, out_b = n * out_w * 4;
+  int rc = ensure_scratch(ctx, in_ba + in_bb + out_b + 1024);
   if (rc) return rc;
   char* d_a = (char*)ctx->scratch;
-  char* d_b = d_a + in_b;
-  char* d_o = d_b + in_b;
-  NCG_HIP(ctx, hipMemcpyAsync(d_a, a, n * in_w * 4, hipMemcpyHostToDevice, ctx->stream));
-  NCG_HIP(ctx, hipMemcpyAsync(d_b, b, n * in_w * 4, hipMemcpyHostToDevice, ctx->stream));
+  char* d_b = d_a + in_ba;
+  char* d_o = d_b + in_bb;
+  NCG_HIP(ctx, hipMemcpyAsync(d_a, a, n * in_wa * 4, hipMemcpyHostToDevice, ctx->stream));
+  NCG_HIP(ctx, hipMemcpyAsync(d_b, b, n * in_wb * 4, hipMemcpyHostToDevice, ctx->stream));
   NCG_HIP(ctx, hipMemsetAsync(d_o, 0, out_b, ctx->stream));
   NCG_HIP(ctx, ncg::field_check_run(field, op, variant, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_o, (int)n, ctx->stream));
   NCG_HIP(ctx, hipMemcpyAsync(out, d_o, out_b, hipMemcpyDeviceToHost, ctx->stream));

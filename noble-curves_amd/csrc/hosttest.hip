@@ -288,7 +288,7 @@ int ht_field_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_
   return -1;
 }
 
-// GLV split of a 256-bit scalar: out = k1[5] k2[5] k1neg k2neg (12 words)
+// fused Fe9 expressions (ht_fe9_fused_t): field 0 secp256k1 p, 1 ed25519 p; a, b, c, d, r: 9 raw limbs
 int ht_fe9_fused(int field, int op, int variant, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
                  uint32_t* r) {
   if (field == 0) return ht_fe9_fused_t<Fe9SecpPR>(op, variant, a, b, c, d, r);
@@ -336,6 +336,7 @@ int ht_glv_split_odd(const uint32_t* k, uint32_t* out) {
   return 0;
 }
 
+// GLV split of a 256-bit scalar: out = k1[5] k2[5] k1neg k2neg (12 words)
 int ht_glv_split(const uint32_t* k, uint32_t* out) {
   uint32_t kk[8];
   for (int i = 0; i < 8; i++) kk[i] = k[i];

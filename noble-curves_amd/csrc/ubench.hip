@@ -267,6 +267,108 @@ __global__ void __launch_bounds__(64) k_field_check_fe29x2p(int op, const uint32
     default: break;
   }
 }
+// The fused Fe9 expressions (fe9.hpp f_mul_mul / f_mul_sqr / f_mul_add / f_sqr_add / f_half) on RAW limbs at the bound
+// combinations of hosttest.hip's ht_fe9_fused_t, with the same guards (no combination a fused op rejects is instantiated).
+// Per item: a = [a, c], b = [b, d] (9 limbs each); out = 9 raw limbs, so that the tests check the output bound as well.
+template <class PR, int A, int B, int C, int D>
+__device__ void field_check_fused(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  Fe9<PR, A> x;
+  Fe9<PR, B> y;
+  Fe9<PR, C> z;
+  Fe9<PR, D> w;
+#pragma unroll
+  for (int i = 0; i < 9; i++) {
+    x.v[i] = a[i];
+    z.v[i] = a[9 + i];
+    y.v[i] = b[i];
+    w.v[i] = b[9 + i];
+  }
+  auto put = [&](const auto& o) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) r[i] = o.v[i];
+  };
+  if constexpr (A * B + C * D <= 7) {
+    if (op == 0) put(f_mul_mul(x, y, z, w));
+  }
+  if constexpr (C <= 2 && A * B + C * C <= 7) {
+    if (op == 1) put(f_mul_sqr(x, y, z));
+  }
+  if constexpr (A * B <= 7) {
+    if (op == 2) put(f_mul_add(x, y, z));
+  }
+  if constexpr (A <= 2) {
+    if (op == 3) put(f_sqr_add(x, z));
+  }
+  if constexpr (A == 1) {
+    if (op == 4) put(f_half(x));
+  }
+}
+template <class PR>
+__global__ void __launch_bounds__(64) k_field_check_fused(int op, int variant, const uint32_t* __restrict__ a,
+                                                          const uint32_t* __restrict__ b, uint32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *pa = a + (size_t)i * 18, *pb = b + (size_t)i * 18;
+  uint32_t* r = out + (size_t)i * 9;
+  switch (variant) {  // decimal digits A B C D
+    case 1111: field_check_fused<PR, 1, 1, 1, 1>(op, pa, pb, r); break;
+    case 1322: field_check_fused<PR, 1, 3, 2, 2>(op, pa, pb, r); break;
+    case 3211: field_check_fused<PR, 3, 2, 1, 1>(op, pa, pb, r); break;
+    case 2311: field_check_fused<PR, 2, 3, 1, 1>(op, pa, pb, r); break;
+    case 1123: field_check_fused<PR, 1, 1, 2, 3>(op, pa, pb, r); break;
+    case 3121: field_check_fused<PR, 3, 1, 2, 1>(op, pa, pb, r); break;
+    case 1327: field_check_fused<PR, 1, 3, 2, 7>(op, pa, pb, r); break;
+    case 7171: field_check_fused<PR, 7, 1, 7, 1>(op, pa, pb, r); break;
+    case 1771: field_check_fused<PR, 1, 7, 7, 1>(op, pa, pb, r); break;
+    case 2171: field_check_fused<PR, 2, 1, 7, 1>(op, pa, pb, r); break;
+    default: break;
+  }
+}
+// The pieces of the secp256k1 fused ladder (CurveSecpI) on RAW limbs, as hosttest.hip's ht_jac_neg / ht_glv_split_odd:
+// op 0 jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) with P = a (27 limbs, bound 2), qx = b[0..9) (bound 2), qy = b[9..18)
+// (bound 3, a negated table entry); out = X, Y, Z.  op 2: secp_glv_split + secp_glv_make_odd of the scalar a[0..8);
+// out[0..12) = k1[5] k2[5] k1neg k2neg.  One lane per item, so a wave mixes the generic path and the exceptional branch.
+__global__ void __launch_bounds__(64) k_field_check_secp_ladder(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                                uint32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *pa = a + (size_t)i * 27, *pb = b + (size_t)i * 18;
+  uint32_t* r = out + (size_t)i * 27;
+  if (op == 2) {
+    uint32_t k[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) k[j] = pa[j];
+    GlvSplit s = secp_glv_split(k);
+    secp_glv_make_odd(s);
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+      r[j] = s.k1[j];
+      r[5 + j] = s.k2[j];
+    }
+    r[10] = s.k1neg;
+    r[11] = s.k2neg;
+    return;
+  }
+  if (op != 0 && op != 1) return;
+  Jac<FeSecp> P;
+  Fe9<Fe9SecpPR, 2> qx;
+  Fe9<Fe9SecpPR, 3> qy;
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    P.X.v[j] = pa[j];
+    P.Y.v[j] = pa[9 + j];
+    P.Z.v[j] = pa[18 + j];
+    qx.v[j] = pb[j];
+    qy.v[j] = pb[9 + j];
+  }
+  const Jac<FeSecp> R = op == 0 ? jac_dbl_neg(P) : jac_madd_neg(P, qx, qy);
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    r[j] = R.X.v[j];
+    r[9 + j] = R.Y.v[j];
+    r[18 + j] = R.Z.v[j];
+  }
+}
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
                            hipStream_t st) {
   if (n <= 0) return hipSuccess;
@@ -276,6 +378,9 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 2) hipLaunchKernelGGL(k_field_check_fe29, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else if (field == 3) hipLaunchKernelGGL(k_field_check_fe29raw, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else if (field == 4) hipLaunchKernelGGL(k_field_check_fe29x2p, dim3((2 * n + 63) / 64), block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 5) hipLaunchKernelGGL(k_field_check_fused<Fe9SecpPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
+  else if (field == 6) hipLaunchKernelGGL(k_field_check_fused<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
+  else if (field == 7) hipLaunchKernelGGL(k_field_check_secp_ladder, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -45,6 +45,9 @@ def lib():
         _lib.ht_msm_seg.argtypes = [i32, i32, i32, vp]
         _lib.ht_msm_plan_top.argtypes = [i32, i32, i32, vp]
         _lib.ht_h64_op.argtypes = [i32, vp, vp, vp, vp]
+        _lib.ht_fe9_fused.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
+        _lib.ht_jac_neg.argtypes = [i32, vp, vp, vp, vp]
+        _lib.ht_glv_split_odd.argtypes = [vp, vp]
     return _lib
 
 
@@ -74,6 +77,47 @@ def glv_split(k):
     k1 = sum(int(out[i]) << (32 * i) for i in range(5))
     k2 = sum(int(out[5 + i]) << (32 * i) for i in range(5))
     return bool(out[10]), k1, bool(out[11]), k2
+
+
+def _u32(words):
+    return np.ascontiguousarray(np.array(words, dtype=np.uint32))
+
+
+def fe9_fused(field, op, variant, a, b, c, d):
+    """fe9.hpp fused expression (0 secp256k1 p, 1 ed25519 p) on raw limbs at the bounds `variant` = decimal A B C D:
+    op 0 a*b + c*d, 1 a*b + c^2, 2 a*b + c, 3 a^2 + c, 4 a / 2; returns the 9 raw output limbs"""
+    out = np.zeros(9, dtype=np.uint32)
+    arrs = [_u32(x) for x in (a, b, c, d)]
+    assert lib().ht_fe9_fused(field, op, variant, *[x.ctypes.data for x in arrs], out.ctypes.data) == 0
+    return [int(x) for x in out]
+
+
+def jac_neg(op, pj, qx=None, qy=None):
+    """op 0 jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) on secp256k1 raw limbs (P 27 limbs at bound 2, qx at 2, qy at 3);
+    returns 27 raw limbs"""
+    out = np.zeros(27, dtype=np.uint32)
+    a, bx, by = _u32(pj), _u32(qx if qx is not None else [0] * 9), _u32(qy if qy is not None else [0] * 9)
+    assert lib().ht_jac_neg(op, a.ctypes.data, bx.ctypes.data, by.ctypes.data, out.ctypes.data) == 0
+    return [int(x) for x in out]
+
+
+def glv_split_odd_words(k):
+    """secp_glv_split + secp_glv_make_odd of k: the 12 words k1[5] k2[5] k1neg k2neg"""
+    out = np.zeros(12, dtype=np.uint32)
+    kk = np.frombuffer(int(k % (1 << 256)).to_bytes(32, "little"), dtype=np.uint32).copy()
+    assert lib().ht_glv_split_odd(kk.ctypes.data, out.ctypes.data) == 0
+    return [int(x) for x in out]
+
+
+def split_words_to_ints(w):
+    k1 = sum(int(w[i]) << (32 * i) for i in range(5))
+    k2 = sum(int(w[5 + i]) << (32 * i) for i in range(5))
+    return (-k1 if w[10] else k1), (-k2 if w[11] else k2)
+
+
+def glv_split_odd(k):
+    """the signed odd halves (k1, k2) of k"""
+    return split_words_to_ints(glv_split_odd_words(k))
 
 
 def ed_halve(k, s):

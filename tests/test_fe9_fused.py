@@ -1,52 +1,20 @@
 """CPU execution of the fused Fe9 expressions (fe9.hpp f_mul_mul / f_mul_sqr / f_mul_add / f_sqr_add / f_half), the negated
 ladder formulas built on them (ec_sw.hpp jac_dbl_neg / jac_madd_neg), the odd GLV halves (scalar.hpp secp_glv_make_odd) and
 the ladder that uses all three (CurveSecpI) against big-integer arithmetic and the oracle."""
-import ctypes
-
-import numpy as np
 import pytest
 
 import hosttest
-from helpers import ORACLE_CURVE, points_to_wire, scalars_to_wire, wire_to_affine
+from helpers import (ORACLE_CURVE, SECP_LAMBDA as LAM, U, ladder_events, ladder_exceptional_scalars, loose, points_to_wire,
+                     scalars_to_wire, secp_add, secp_from_jac, secp_jac, secp_neg, secp_rand_point, signed_odd_digits, val,
+                     wire_to_affine)
 from noble_curves_amd._native import SECP256K1
 from oracle.curves import ED25519_P, SECP256K1_N, SECP256K1_P, Secp256k1, makeRng
 
-U = (1 << 29) + (1 << 19)
-MASK = (1 << 29) - 1
-LAM = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
 CURVE_SECP_FUSED = 14   # ht_mul_var: the ladder of CurveSecpI
 
 
-def _lib():
-    lib = hosttest.lib()
-    vp, i32 = ctypes.c_void_p, ctypes.c_int
-    lib.ht_fe9_fused.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.ht_jac_neg.argtypes = [i32, vp, vp, vp, vp]
-    lib.ht_glv_split_odd.argtypes = [vp, vp]
-    return lib
-
-
-def _arr(limbs):
-    return np.ascontiguousarray(np.array(limbs, dtype=np.uint32))
-
-
-def val(l):
-    return sum(int(x) << (29 * i) for i, x in enumerate(l))
-
-
-def loose(v, B, p):
-    """limbs below B*U, each as high as possible, with value = v (mod p): (B*U - 1) in every limb minus the canonical limbs of
-    the difference"""
-    top = [B * U - 1] * 9
-    delta = (val(top) - v) % p
-    return [t - ((delta >> (29 * i)) & MASK) for i, t in enumerate(top)]
-
-
 def fused(fid, op, variant, a, b, c, d):
-    out = np.zeros(9, dtype=np.uint32)
-    arrs = [_arr(x) for x in (a, b, c, d)]
-    assert _lib().ht_fe9_fused(fid, op, variant, *[x.ctypes.data for x in arrs], out.ctypes.data) == 0
-    return [int(x) for x in out]
+    return hosttest.fe9_fused(fid, op, variant, a, b, c, d)
 
 
 # (op, variants A B C D): op 0 a*b + c*d, 1 a*b + c^2, 2 a*b + c, 3 a^2 + c, 4 a / 2
@@ -87,55 +55,8 @@ def test_fused_expressions_at_their_bounds(fid, p):
 P = SECP256K1_P
 
 
-def _aff_add(p1, p2):
-    if p1 is None:
-        return p2
-    if p2 is None:
-        return p1
-    (x1, y1), (x2, y2) = p1, p2
-    if x1 == x2:
-        if (y1 + y2) % P == 0:
-            return None
-        lam = 3 * x1 * x1 * pow(2 * y1, -1, P) % P
-    else:
-        lam = (y2 - y1) * pow(x2 - x1, -1, P) % P
-    x3 = (lam * lam - x1 - x2) % P
-    return x3, (lam * (x1 - x3) - y1) % P
-
-
-def _neg(pt):
-    return None if pt is None else (pt[0], (-pt[1]) % P)
-
-
-def _rand_point(rng):
-    q = Secp256k1.BASE.multiplyUnsafe(rng.rndBelow(SECP256K1_N - 1) + 1).toAffine()
-    return int(q[0]), int(q[1])
-
-
-def _jac(pt, z, B=2):
-    """Jacobian limbs (loose, bound B) of affine pt at Z = z; None = infinity (1, 1, 0) with a literal zero Z"""
-    if pt is None:
-        return [1] + [0] * 8 + [1] + [0] * 8 + [0] * 9
-    x, y = pt
-    return loose(x * z * z % P, B, P) + loose(y * z ** 3 % P, B, P) + loose(z, B, P)
-
-
-def _from_jac(l):
-    X, Y, Z = val(l[:9]) % P, val(l[9:18]) % P, val(l[18:])
-    if Z % P == 0:
-        assert Z == 0, "infinity must come back as a literal zero Z"
-        return None
-    zi = pow(Z, -1, P)
-    return X * zi * zi % P, Y * zi ** 3 % P
-
-
 def jac_neg(op, pj, qx=None, qy=None):
-    out = np.zeros(27, dtype=np.uint32)
-    a = _arr(pj)
-    bx = _arr(qx if qx is not None else [0] * 9)
-    by = _arr(qy if qy is not None else [0] * 9)
-    assert _lib().ht_jac_neg(op, a.ctypes.data, bx.ctypes.data, by.ctypes.data, out.ctypes.data) == 0
-    r = [int(x) for x in out]
+    r = hosttest.jac_neg(op, pj, qx, qy)
     assert max(r) < 2 * U
     return r
 
@@ -145,30 +66,24 @@ def test_negated_doubling_and_mixed_addition():
     including P = Q, P = -Q, P = infinity and Q = infinity."""
     rng = makeRng(0x5E9)
     for i in range(24):
-        p1 = _rand_point(rng)
+        p1 = secp_rand_point(rng)
         z = rng.rndBelow(P - 1) + 1
-        assert _from_jac(jac_neg(0, _jac(p1, z))) == _neg(_aff_add(p1, p1))
-        q = _rand_point(rng) if i % 4 else p1
-        assert _from_jac(jac_neg(1, _jac(p1, z), loose(q[0], 2, P), loose(q[1], 3, P))) == _neg(_aff_add(p1, q))
-    p1 = _rand_point(rng)
+        assert secp_from_jac(jac_neg(0, secp_jac(p1, z))) == secp_neg(secp_add(p1, p1))
+        q = secp_rand_point(rng) if i % 4 else p1
+        assert secp_from_jac(jac_neg(1, secp_jac(p1, z), loose(q[0], 2, P), loose(q[1], 3, P))) == secp_neg(secp_add(p1, q))
+    p1 = secp_rand_point(rng)
     z = rng.rndBelow(P - 1) + 1
     # P = Q (doubling through the exceptional branch), P = -Q (infinity)
-    assert _from_jac(jac_neg(1, _jac(p1, z), loose(p1[0], 2, P), loose(p1[1], 3, P))) == _neg(_aff_add(p1, p1))
-    assert _from_jac(jac_neg(1, _jac(p1, z), loose(p1[0], 2, P), loose(P - p1[1], 3, P))) is None
+    assert secp_from_jac(jac_neg(1, secp_jac(p1, z), loose(p1[0], 2, P), loose(p1[1], 3, P))) == secp_neg(secp_add(p1, p1))
+    assert secp_from_jac(jac_neg(1, secp_jac(p1, z), loose(p1[0], 2, P), loose(P - p1[1], 3, P))) is None
     # P = infinity: -Q;  Q = infinity (literal (0, 0)): -P;  doubling infinity stays infinity
-    assert _from_jac(jac_neg(1, _jac(None, 1), loose(p1[0], 2, P), loose(p1[1], 3, P))) == _neg(p1)
-    assert _from_jac(jac_neg(1, _jac(p1, z), [0] * 9, [0] * 9)) == _neg(p1)
-    assert _from_jac(jac_neg(0, _jac(None, 1))) is None
+    assert secp_from_jac(jac_neg(1, secp_jac(None, 1), loose(p1[0], 2, P), loose(p1[1], 3, P))) == secp_neg(p1)
+    assert secp_from_jac(jac_neg(1, secp_jac(p1, z), [0] * 9, [0] * 9)) == secp_neg(p1)
+    assert secp_from_jac(jac_neg(0, secp_jac(None, 1))) is None
 
 
 # ---- odd GLV halves
-def glv_split_odd(k):
-    out = np.zeros(12, dtype=np.uint32)
-    kk = np.frombuffer(int(k % (1 << 256)).to_bytes(32, "little"), dtype=np.uint32).copy()
-    assert _lib().ht_glv_split_odd(kk.ctypes.data, out.ctypes.data) == 0
-    k1 = sum(int(out[i]) << (32 * i) for i in range(5))
-    k2 = sum(int(out[5 + i]) << (32 * i) for i in range(5))
-    return (-k1 if out[10] else k1), (-k2 if out[11] else k2)
+glv_split_odd = hosttest.glv_split_odd
 
 
 def test_glv_odd_halves():
@@ -188,12 +103,31 @@ def test_glv_odd_halves():
     assert seen == {(0, 0), (0, 1), (1, 0), (1, 1)}
 
 
+# ---- the ladder model (helpers.ladder_events): which scalars make CurveSecpI's ladder meet R = O, R = Q or R = -Q
+def test_ladder_model():
+    """The signed-odd recoding gives back |k1|, |k2|; random scalars meet no exceptional addition before the last window (the
+    first addition, from R = O, is the ladder's start and not counted); the search over k = a + b lambda finds exactly k = 0
+    (R = -Q in the last addition: the result is O) and k = -26 lambda (R = Q in the last addition: jac_madd_neg doubles)."""
+    n = SECP256K1_N
+    rng = makeRng(0x1ADE)
+    ks = [1, 2, n - 1, LAM, n - LAM, 1 << 128, (1 << 256) - 1] + [rng.rndBelow(n) for _ in range(4000)]
+    for k in ks:
+        for h in glv_split_odd(k):
+            d = signed_odd_digits(abs(h))
+            assert sum(x << (4 * i) for i, x in enumerate(d)) == abs(h) and all(x % 2 and abs(x) < 16 for x in d)
+        assert all(w == 32 for w, _, _ in ladder_events(k, glv_split_odd)), hex(k)
+    assert ladder_events((-26 * LAM) % n, glv_split_odd) == [(32, 1, "dbl")]
+    assert ladder_events(0, glv_split_odd) == [(32, 1, "neg")]
+    assert ladder_exceptional_scalars(glv_split_odd) == {0: [(32, 1, "neg")], (-26 * LAM) % n: [(32, 1, "dbl")]}
+
+
 # ---- the fused-formula ladder on the CPU
 def test_fused_ladder_matches_oracle():
     n = SECP256K1_N
     rng = makeRng(0xF1AD)
     ks = [0, 1, 2, 3, 4, 5, n - 1, n - 2, n - 3, 1 << 128, (1 << 128) - 1, (1 << 128) + 1, LAM, LAM + 1, n - LAM, 15, 16, 17,
           (1 << 255), n // 2]
+    ks += sorted(ladder_exceptional_scalars(glv_split_odd))   # the scalars of the model's exceptional additions (0, -26 lambda)
     ks += [rng.rndBelow(n) for _ in range(60)]
     pts = [Secp256k1.BASE.multiplyUnsafe(rng.rndBelow(n - 1) + 1) for _ in ks]
     pts[3] = Secp256k1.ZERO
