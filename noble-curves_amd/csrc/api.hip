@@ -387,7 +387,7 @@ int ncg_mul_var_batch(ncg_ctx* ctx, int curve, size_t n, const void* points_affi
     // middle chunks are big, and only the first upload and the last download are exposed, so the outer ones are small.
     // (eight equal chunks: 10.7 ms for 2^20 secp256k1 pairs from pinned memory.)
     static const int k_eighths_big[4] = {1, 3, 3, 1}, k_eighths_even[4] = {2, 2, 2, 2};
-    const int* eighths = (n >= ((size_t)1 << 19) && ncg::knob("NCG_MULVAR_HOST_EVEN", 0) == 0) ? k_eighths_big : k_eighths_even;  // (knob: A/B builds only)
+    const int* eighths = n >= ((size_t)1 << 19) ? k_eighths_big : k_eighths_even;
     const int chunks = 4;
     const size_t unit = (((n + 7) / 8) + 255) & ~(size_t)255;
     hipError_t e = hipSuccess;
@@ -648,12 +648,8 @@ int ncg_msm(ncg_ctx* ctx, int curve, size_t n, const void* points_affine, const 
     rc = ensure_copy_streams(ctx);
     if (rc) return rc;
     char* d_stored = d_sc + sc_al;
-    // measured on one box (tools/host_parts_sweep.py): G1 2^20 6.0 / 5.0 / 4.5 / 4.9 ms with 1 / 2 / 4 / 8 parts, G2 2^18 5.7 / 4.3 / 4.4 / 6.2
-    int parts = n >= ((size_t)1 << 19) ? 4 : n >= ((size_t)1 << 17) ? 2 : 1;
-    {
-      const int k = ncg::knob("NCG_MSM_HOST_PARTS", 0);   // A/B builds only
-      if (k >= 1 && k <= ncg_ctx::COPY_CHUNKS) parts = k;
-    }
+    // measured on one box: G1 2^20 6.0 / 5.0 / 4.5 / 4.9 ms with 1 / 2 / 4 / 8 parts, G2 2^18 5.7 / 4.3 / 4.4 / 6.2
+    const int parts = n >= ((size_t)1 << 19) ? 4 : n >= ((size_t)1 << 17) ? 2 : 1;
     const size_t per = (((n + parts - 1) / parts) + 255) & ~(size_t)255;
     ncg::MsmPlan whole, layout;
     if (ncg::msm_make_plan(curve, (int)n, 0, &whole) != 0 || ncg::msm_make_plan(curve, (int)std::min(n, per), whole.c, &layout) != 0)

@@ -187,8 +187,7 @@ int job_local_phase(ncg_ctx* ctx, const JobRes& R, const ShardJob& J, int slot_i
     ncg::msm_shard_window_range(whole.nwin, J.part, J.nparts, &w0, &cnt);
     // one or two windows per rank: 64 sort chunks per window instead of 256 (k_msm_bucket_totals walks the chunks serially:
     // 64 -> 21 us of a 0.9 ms share; measured 0.905 -> 0.856 ms for G = 8, no difference from 4 windows per rank up)
-    static const int share_q = ncg::knob("NCG_MSM_SHARE_QBLOCKS", 128);   // A/B builds
-    ncg::msm_plan_take_windows(local, w0, cnt, cnt <= 2 ? share_q : 512);
+    ncg::msm_plan_take_windows(local, w0, cnt, cnt <= 2 ? 128 : 512);
   }
   const size_t xw = ncg::msm_acc_words(curve);
   const size_t ng = (size_t)ncg::msm_ngroups(whole.c);

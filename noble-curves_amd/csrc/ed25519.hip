@@ -16,13 +16,12 @@
 //     device memory, 2.3 KB per item), 8-bit windows for the two 128-bit halves of |u| s mod L on the shared tables
 //     of B and 2^128 B (2 x 128 precomputed affine Niels multiples): 32 + 32 + 16 + 16 additions, 3 waves/SIMD.
 //     2^18 verifications: 2.84 ms against 3.58 ms for the full-size form below (MI355X).
-//   full-size scalars, table in device memory (EdCfgGtab, A/B builds only): 4-bit windows for -A, 8-bit for B:
-//     264 doublings, 66 + 33 additions.
+//   full-size scalars, table in device memory (EdCfgGtab, measured and no longer launched for verification): 4-bit
+//     windows for -A, 8-bit for B: 264 doublings, 66 + 33 additions.
 //   fallback without scratch (EdCfgLds): 2-bit windows for -A (2-entry per-lane table in LDS, projective Niels
 //     form: 16 KB per wave, so 8-10 waves fit a CU - a 3-bit window measured 1.7x slower for that reason) and
 //     6 bits for B (32 precomputed affine Niels multiples shared by every lane): 258 doublings, 129 + 43 additions.
 #include <cstdlib>
-#include "knobs.hpp"
 #include <mutex>
 #include <vector>
 
@@ -529,32 +528,9 @@ size_t ed25519_verify_tmp_words(int n) { return ((size_t)n + 63) / 64 * 64 * 2 *
 hipError_t ed25519_verify_batch(const uint32_t* sigs, const uint32_t* pks, const uint32_t* ks, const uint32_t* btab,
                                 int zip215, uint8_t* out_ok, int n, uint32_t* gtab, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-#ifdef NCG_AB_BUILD
-  static const int variant = knob("NCG_ED_VARIANT", 5);
-#else
-  constexpr int variant = 5;  // halved scalars, 3 waves/SIMD; 2-4: full-size scalars at 2-4 waves/SIMD (A/B builds)
-#endif
-  if (gtab && variant > 0) {
-#ifdef NCG_AB_BUILD
-    if (variant == 2)
-      hipLaunchKernelGGL((k_ed25519_verify<EdCfgGtab, true, 2>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab,
-                         zip215, out_ok, gtab, n);
-    else if (variant == 3)
-      hipLaunchKernelGGL((k_ed25519_verify<EdCfgGtab, true, 3>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab,
-                         zip215, out_ok, gtab, n);
-    else if (variant == 4)
-      hipLaunchKernelGGL((k_ed25519_verify<EdCfgGtab, true, 4>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab,
-                         zip215, out_ok, gtab, n);
-    else if (variant == 6)
-      hipLaunchKernelGGL((k_ed25519_verify_half<EdCfgHalf, 2>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab, zip215,
-                         out_ok, gtab, n);
-    else if (variant == 7)
-      hipLaunchKernelGGL((k_ed25519_verify_half<EdCfgHalf, 4>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab, zip215,
-                         out_ok, gtab, n);
-    else
-#endif
-      hipLaunchKernelGGL((k_ed25519_verify_half<EdCfgHalf, 3>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab, zip215,
-                         out_ok, gtab, n);
+  if (gtab) {  // halved scalars, 3 waves/SIMD
+    hipLaunchKernelGGL((k_ed25519_verify_half<EdCfgHalf, 3>), dim3((n + 63) / 64), dim3(64), 0, st, sigs, pks, ks, btab, zip215,
+                       out_ok, gtab, n);
     return hipGetLastError();
   }
   size_t lds = (size_t)EdCfgLds::LDS_WORDS * 4;

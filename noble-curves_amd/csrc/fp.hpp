@@ -125,7 +125,7 @@ NCG_DI Fp<PR> fp_dbl(const Fp<PR>& a) {
   return a + a;
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
 // acc (96 bits: lo64 + ex) += a*b.  v_mad_u64_u32 adds the 64-bit product into lo64 and reports
 // the carry in VCC; one v_addc folds it into `ex`.  Two instructions per partial product instead of
 // three (mad + two carry adds), and no SGPR-carried chains (which cost s_nop hazard padding).
@@ -137,7 +137,7 @@ __device__ __forceinline__ void mac96(uint64_t& lo64, uint32_t& ex, uint32_t a, 
 }
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
 // Montgomery product by columns (finely integrated product scanning) on the 96-bit accumulator:
 // 2N^2 + N multiplies, one carry instruction per multiply.
 template <class PR>
@@ -274,7 +274,7 @@ NCG_DI void fp_fold_reduce(uint32_t (&r)[8], const uint32_t (&T)[16]) {
   for (int k = 0; k < PR::FINAL_SUBS; k++) fp_cond_sub_p<PR>(r, 0u);
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
 // 512-bit product by columns (product scanning): T[k] = low word of column k after carries.
 template <int N>
 __device__ __forceinline__ void mul_columns_asm(uint32_t (&T)[2 * N], const uint32_t (&a)[N], const uint32_t (&b)[N]) {
@@ -293,31 +293,6 @@ __device__ __forceinline__ void mul_columns_asm(uint32_t (&T)[2 * N], const uint
   }
   T[2 * N - 1] = (uint32_t)lo;
 }
-// Square by columns: off-diagonal products once, the 96-bit column sum doubled, then the
-// diagonal term and the carry from the previous column.
-template <int N>
-__device__ __forceinline__ void sqr_columns_asm(uint32_t (&T)[2 * N], const uint32_t (&a)[N]) {
-  uint64_t carry = 0;  // (column sum) >> 32 of the previous column, below 2^64
-#pragma unroll
-  for (int k = 0; k < 2 * N - 1; k++) {
-    uint64_t lo = 0;
-    uint32_t ex = 0;
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-      const int j = k - i;
-      if (j > i && j < N) mac96(lo, ex, a[i], a[j]);
-    }
-    // double the off-diagonal sum (below 2^67, so nothing is shifted out of ex)
-    ex = (ex << 1) | (uint32_t)(lo >> 63);
-    lo <<= 1;
-    if ((k & 1) == 0) mac96(lo, ex, a[k / 2], a[k / 2]);
-    uint64_t nl = lo + carry;
-    ex += nl < lo ? 1u : 0u;
-    T[k] = (uint32_t)nl;
-    carry = (nl >> 32) | ((uint64_t)ex << 32);
-  }
-  T[2 * N - 1] = (uint32_t)carry;
-}
 #endif
 
 template <class PR>
@@ -325,7 +300,7 @@ NCG_DI void fp_mul_fold_body(uint32_t (&r)[PR::N], const uint32_t (&a)[PR::N], c
   static_assert(PR::N == 8, "fold path is for 256-bit special primes");
   constexpr int N = 8;
   uint32_t T[2 * N];
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
   mul_columns_asm<N>(T, a, b);
 #else
 #pragma unroll
@@ -360,15 +335,6 @@ NCG_DI void fp_sqr_fold_body(uint32_t (&r)[PR::N], const uint32_t (&a)[PR::N]) {
   static_assert(PR::N == 8, "fold path is for 256-bit special primes");
   constexpr int N = 8;
   uint32_t T[2 * N];
-#if defined(__HIP_DEVICE_COMPILE__) && defined(NCG_ASM_SQR)
-#if NCG_ASM_SQR == 2
-  mul_columns_asm<N>(T, a, a);
-#else
-  sqr_columns_asm<N>(T, a);
-#endif
-  fp_fold_reduce<PR>(r, T);
-  return;
-#endif
 #pragma unroll
   for (int i = 0; i < 2 * N; i++) T[i] = 0;
 #pragma unroll
@@ -412,7 +378,7 @@ NCG_MULFN Fp<PR> fp_mul(Fp<PR> a, Fp<PR> b) {  // modular.ts:956
   if constexpr (PR::FOLD) {
     fp_mul_fold_body<PR>(r.v, a.v, b.v);
   } else {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
     fp_mul_fips_asm<PR>(r.v, a.v, b.v);
 #else
     fp_mul_body<PR>(r.v, a.v, b.v);
@@ -427,7 +393,7 @@ NCG_MULFN Fp<PR> fp_sqr(Fp<PR> a) {  // modular.ts:947
   if constexpr (PR::FOLD) {
     fp_sqr_fold_body<PR>(r.v, a.v);
   } else {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(NCG_NO_ASM_PRODUCT)
+#ifdef __HIP_DEVICE_COMPILE__
     fp_mul_fips_asm<PR>(r.v, a.v, a.v);
 #else
     fp_mul_body<PR>(r.v, a.v, a.v);

@@ -35,10 +35,7 @@ __global__ void __launch_bounds__(256) k_points_to_mont(const uint32_t* __restri
 // faster when asked to fit; the lane-paired G2 kernels are not (measured)
 template <class C> struct TailMinWaves { static constexpr int value = 1; };
 // (one wave per SIMD - 297 registers, no spills - measured again in round 5: the 2^20 G1 MSM 3.33 -> 3.48 ms; two it stays)
-#ifndef NCG_TAIL_MINW_G1
-#define NCG_TAIL_MINW_G1 2
-#endif
-template <> struct TailMinWaves<CurveG1> { static constexpr int value = NCG_TAIL_MINW_G1; };
+template <> struct TailMinWaves<CurveG1> { static constexpr int value = 2; };
 
 // ------------------------------------------------------------------ 2. signed digits
 // digits[w*n + i] = ((k_i + H') >> (c w)) & (2^c - 1)) - 2^(c-1)
@@ -319,10 +316,7 @@ static __global__ void __launch_bounds__(1024) k_msm_scatter(const int16_t* __re
 // plans keep the one-level kernels.
 constexpr int SORT2_MAX_RANGES = 256;   // ranges per window: 64, or 128 / 256 where 64 regions would not fit the staged kernel (Sort2::lgr)
 constexpr int SORT2_SLICES = 8;
-#ifndef NCG_SORT2_UNROLL
-#define NCG_SORT2_UNROLL 8
-#endif
-constexpr int SORT2_UNROLL = NCG_SORT2_UNROLL;   // entries a lane of the coarse kernels holds in flight
+constexpr int SORT2_UNROLL = 8;   // entries a lane of the coarse kernels holds in flight
 struct Sort2 {
   int lgr;                // log2(ranges per window): 6..8
   int sh, idxbits;        // log2(buckets per range), bits of an entry index
@@ -777,14 +771,12 @@ static __global__ void __launch_bounds__(1024) k_msm_sort_small(const uint32_t* 
 #endif
 }
 static bool msm_small_sort_ok(const MsmPlan& pl) {
-  static const int on = knob("NCG_MSM_SMALL_SORT", 1);   // A/B builds: 0 = the separate kernels
-  return on && !pl.endo && !pl.shared && pl.part_flags == 3 && pl.n_layout <= pl.n && pl.n <= MSM_SMALL_N && pl.nb <= MSM_SMALL_NB;
+  return !pl.endo && !pl.shared && pl.part_flags == 3 && pl.n_layout <= pl.n && pl.n <= MSM_SMALL_N && pl.nb <= MSM_SMALL_NB;
 }
 
 // does the two-level form apply to this plan?  Fills the per-plan constants.
 static bool msm_sort2_ok(const MsmPlan& pl, int n_max, Sort2* s2) {
-  static const int on = knob("NCG_MSM_SORT2", 1);   // A/B builds: 0 = the one-level kernels
-  if (!on || pl.shared || pl.nb < 1024 || pl.nb > (1 << 15)) return false;
+  if (pl.shared || pl.nb < 1024 || pl.nb > (1 << 15)) return false;
   int lg = 0;
   while ((1 << lg) < pl.nb) lg++;
   int ib = 1;
@@ -838,82 +830,22 @@ static size_t msm_sort2_words(const MsmPlan& pl) {
 // k_msm_fixup adds up.
 // (MsmSeg / msm_seg: msm_plan.hpp - host-side planning, shared with the CPU test twin)
 
-#ifndef NCG_ACCUM_MINW
-#define NCG_ACCUM_MINW 1
-#endif
 // lane-paired G2 sits 24 registers above the 2-waves/SIMD line: ask for 2 (a little scratch
 // traffic in a loop of ~17k instructions per add is cheaper than half the occupancy)
-template <class C> struct AccumMinWaves { static constexpr int value = NCG_ACCUM_MINW; };
+template <class C> struct AccumMinWaves { static constexpr int value = 1; };
 // G2: the row-wise Montgomery product needed 306 registers (one wave per SIMD; at two waves the kernel kept 79 values in
 // scratch memory: 3 % slower on most boxes and 49 % slower on the boxes of the pool whose memory path is slow,
 // profiles/r03_box_to_box.md).  With the column-wise product (fp29.hpp mont_cols29) it needs 232: two waves, no scratch.
-template <> struct AccumMinWaves<CurveG2P> { static constexpr int value = NCG_G2_ACCUM_WAVES; };
+template <> struct AccumMinWaves<CurveG2P> { static constexpr int value = G2_ACCUM_WAVES; };
 template <> struct AccumMinWaves<CurveG1> { static constexpr int value = 2; };  // 256 VGPRs + 36 B scratch: 2 % faster than 1 wave
-// Point prefetch through LDS-DMA (gfx950 global_load_lds_dwordx4: global -> LDS with no register in between).  One mixed
-// addition is ~9-10 k instructions (~20 us per lane at two waves per SIMD) and begins with a dependent pair of loads - the
-// sorted entry, then the 112 / 224-byte point it names, a random gather - that only one other wave can cover.  With the
-// prefetch the point of entry pos + 1 travels into the wave's LDS slab while the addition of entry pos runs, and the entry
-// of pos + 2 into a register; the addition starts from 7 ds_read_b128.  Holding the next point in registers instead would
-// cost 28 VGPRs that neither kernel has (256 / 232 in use).  Layout of a wave's slab: chunk j (16 bytes per lane) of every
-// lane at [j][lane] - the only layout the instruction writes (LDS address = uniform base + lane * 16).  G1: a lane's seven
-// chunks are its point (x, y).  Lane-paired G2: the even lane fetches x (c0, c1), the odd lane y (c0, c1), 112 bytes each,
-// and each lane then reads its own component of both coordinates from its own and its partner's chunks.
-#ifndef NCG_ACCUM_PREFETCH
-#define NCG_ACCUM_PREFETCH 0
-#endif
-template <class C> struct AccumPrefetch { static constexpr bool value = false; };
-template <> struct AccumPrefetch<CurveG1> { static constexpr bool value = NCG_ACCUM_PREFETCH != 0; };
-template <> struct AccumPrefetch<CurveG2P> { static constexpr bool value = NCG_ACCUM_PREFETCH != 0; };
-constexpr int ACCUM_PF_CHUNKS = 7;                          // 7 x 16 bytes per lane
-[[maybe_unused]] constexpr int ACCUM_PF_WAVE_WORDS = ACCUM_PF_CHUNKS * 64 * 4;  // one wave's slab, in words
-
-// this lane's 112 bytes starting at `src` (16-byte aligned) -> chunk slots of the wave's slab
-NCG_DI void accum_pf_issue(const uint32_t* src, uint32_t* slab) {
-#ifdef __HIP_DEVICE_COMPILE__
-#pragma unroll
-  for (int j = 0; j < ACCUM_PF_CHUNKS; j++)
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 4 * j),
-                                     (__attribute__((address_space(3))) void*)(slab + j * 256), 16, 0, 0);
-#endif
-}
-// word k (0..27) of the 112 bytes that lane `ln` of this wave fetched
-NCG_DI uint32_t accum_pf_word(const uint32_t* slab, int ln, int k) { return slab[(k >> 2) * 256 + ln * 4 + (k & 3)]; }
-
-template <class C> struct AccumPf;
-template <> struct AccumPf<CurveG1> {
-  using G = MsmGroup<CurveG1>;
-  static NCG_DI const uint32_t* src(const uint32_t* point) { return point; }
-  static NCG_DI typename G::Aff read(const uint32_t* slab, int ln) {
-    typename G::Aff q;
-#pragma unroll
-    for (int i = 0; i < 14; i++) {
-      q.x.v[i] = accum_pf_word(slab, ln, i);
-      q.y.v[i] = accum_pf_word(slab, ln, 14 + i);
-    }
-    return q;
-  }
-};
-template <> struct AccumPf<CurveG2P> {
-  using G = MsmGroup<CurveG2P>;
-  static NCG_DI const uint32_t* src(const uint32_t* point) { return point + (pair_odd() ? 28 : 0); }
-  static NCG_DI typename G::Aff read(const uint32_t* slab, int ln) {
-    const int odd = ln & 1, even_ln = ln & ~1, odd_ln = ln | 1;
-    typename G::Aff q;
-#pragma unroll
-    for (int i = 0; i < 14; i++) {
-      q.x.h.v[i] = odd ? accum_pf_word(slab, even_ln, 14 + i) : accum_pf_word(slab, even_ln, i);
-      q.y.h.v[i] = odd ? accum_pf_word(slab, odd_ln, 14 + i) : accum_pf_word(slab, odd_ln, i);
-    }
-    return q;
-  }
-};
+// (A prefetch of the next point through LDS-DMA was built and measured, and did not pay: DESIGN.md section 5.)
 
 // next non-empty bucket after b (the one that holds sorted position `pos`).  Dense windows: the neighbour, found by walking.
 // SPARSE windows (a spread top window that few scalars reach: MsmPlan::top_tb) would walk thousands of empty buckets one dependent
 // load at a time - 0.4 ms for EIGHT entries in a 16 384-bucket window - so there a second empty bucket sends the search to a
 // bisection.  The two forms are two instantiations of the kernel: the accumulate loop is register-bound (256 VGPRs + spills on
 // G1) and ANY extra instruction in it moves its code generation - the bisection in the loop, inline or out of line, cost the
-// 2^20-point G1 MSM 2-3 % (3.25 -> 3.37 ms, tools/ab_two_libs.sh), and that plan has no sparse window.
+// 2^20-point G1 MSM 2-3 % (3.25 -> 3.37 ms), and that plan has no sparse window.
 __device__ __noinline__ int msm_bisect_bucket(const uint32_t* __restrict__ bs, int b, uint32_t pos, int nb) {
   int l = b, r = nb;  // bs[l] <= pos < bs[r]
   while (r - l > 1) {
@@ -973,40 +905,6 @@ __global__ void __launch_bounds__(256, AccumMinWaves<C>::value) k_msm_accum(cons
   // earlier parts left in that bucket; every other piece starts from the identity as before
   const bool into = (pl.part_flags & 1) == 0;
   Acc acc = (into && b_start >= lo) ? G::acc_load(buckets + ((size_t)w * pl.nb + b) * XW) : G::identity();
-  if constexpr (AccumPrefetch<C>::value) {
-#ifdef __HIP_DEVICE_COMPILE__
-    __shared__ __attribute__((aligned(16))) uint32_t pf_lds[4 * ACCUM_PF_WAVE_WORDS];
-    uint32_t* slab = pf_lds + (threadIdx.x >> 6) * ACCUM_PF_WAVE_WORDS;
-    const int ln = threadIdx.x & 63;
-    uint32_t e_cur = sw[lo];
-    accum_pf_issue(AccumPf<C>::src(pts_mont + (size_t)(e_cur & 0x7fffffffu) * AFF), slab);
-    uint32_t e_next = lo + 1 < hi ? sw[lo + 1] : e_cur;
-    for (uint32_t pos = lo; pos < hi; pos++) {
-      // the point of entry pos has landed (the wave's own vmcnt is what orders its ds_read behind the DMA)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const typename G::Aff q = AccumPf<C>::read(slab, ln);
-      const bool neg = (e_cur >> 31) != 0;
-      // the slab is free again once the reads have returned: send for the next point, and for the entry after it
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (pos + 1 < hi) accum_pf_issue(AccumPf<C>::src(pts_mont + (size_t)(e_next & 0x7fffffffu) * AFF), slab);
-      e_cur = e_next;
-      if (pos + 2 < hi) e_next = sw[pos + 2];
-      if (pos == b_end) {  // bucket finished inside my range
-        if (b_start >= lo) {
-          G::acc_store(buckets + ((size_t)w * pl.nb + b) * XW, acc);
-        } else {
-          G::acc_store(hp, acc);
-          head_b = b;
-        }
-        b = msm_next_bucket<SPARSE>(bs, b, pos, pl.nb);
-        b_start = bs[b];
-        b_end = bs[b + 1];
-        acc = into ? G::acc_load(buckets + ((size_t)w * pl.nb + b) * XW) : G::identity();
-      }
-      acc = G::madd(acc, q, neg);
-    }
-#endif
-  } else
   for (uint32_t pos = lo; pos < hi; pos++) {
     if (pos == b_end) {  // bucket finished inside my range
       if (b_start >= lo) {
@@ -1151,9 +1049,6 @@ __global__ void __launch_bounds__(256) k_msm_reduce_level_coop(const uint32_t* _
 // group of four items sharing each operation (msm_coop.hpp).  Operands and results live in memory; `lds` is the
 // unit's scratch: the exchange slots of the cooperative form, then one accumulator for the grouping chain.
 constexpr int MSM_TAIL_THREADS = 512;
-#ifndef NCG_TAIL_ROUNDS
-#define NCG_TAIL_ROUNDS 1
-#endif
 template <class C, bool COOP> struct TailOps;
 template <class C>
 struct TailOps<C, false> {
@@ -1292,17 +1187,14 @@ __global__ void __launch_bounds__(256, 2) k_msm_fixup_merge_units(const uint32_t
 }
 
 // The fix-up merge of the SMALL plans (round 6): 2^MERGE_TREE_ULOG units per bucket (two: measured against four and against one
-// unit with the work-list threshold at 15, tools/ab_small_msm.sh -> profiles/r06_ab_small_msm.txt: four units idle through most of
+// unit with the work-list threshold at 15, profiles/r06_ab_small_msm.txt: four units idle through most of
 // the tree and quadruple the waves - 83 us for the 2^14-point G1 merge where two take 60).  A plan that does not fill the chip runs short lane
 // segments (msm_seg: 4-12 entries, so that the accumulate kernel's dependent chain is short), which cuts every bucket into
 // (m + 4 sqrt(m)) / seg pieces - up to 8-15 of them - and one unit adding them one after the other made the merge the longest
 // kernel of a 2^13 / 2^14-point MSM (62 us, + 35 us of work-list runs above 8 pieces).  Here unit u of the bucket's group sums the
 // pieces u, u + U, .. and a tree over the U accumulators (LDS, all in one wave) finishes: ceil(P / U) - 1 + log2 U dependent
 // additions for P pieces (two units, P = 15: 8 instead of 14).  Runs of more than run_serial heads still go to the work list.
-#ifndef NCG_MERGE_TREE_ULOG
-#define NCG_MERGE_TREE_ULOG 1
-#endif
-constexpr int MERGE_TREE_ULOG = NCG_MERGE_TREE_ULOG;
+constexpr int MERGE_TREE_ULOG = 1;
 template <class C, bool COOP>
 __global__ void __launch_bounds__(256, 2) k_msm_fixup_merge_tree(const uint32_t* __restrict__ part_pts, const int* __restrict__ part_meta,
                                                               const uint32_t* __restrict__ bucket_start, uint32_t* __restrict__ buckets,
@@ -1656,13 +1548,10 @@ static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const u
     hipLaunchKernelGGL(k_sort2_fine_place, dim3(SORT2_FALLBACK_BLOCKS), dim3(512), 0, st, tmp, region_start, oversize, fcount, bstart, sorted, pl, s2);
   } else {
     hipLaunchKernelGGL(k_msm_hist, sort_grid, dim3(1024), lds, st, digits, counts, pl);
-    {
-      static const int split_knob = knob("NCG_MSM_TOTALS_SPLIT", -1);   // A/B builds: force on (1) / off (0)
-      if (split_knob >= 0 ? split_knob != 0 : pl.Q >= 64)
-        hipLaunchKernelGGL(k_msm_bucket_totals_split, dim3((pl.nb + 31) / 32, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
-      else
-        hipLaunchKernelGGL(k_msm_bucket_totals, dim3((pl.nb + 255) / 256, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
-    }
+    if (pl.Q >= 64)
+      hipLaunchKernelGGL(k_msm_bucket_totals_split, dim3((pl.nb + 31) / 32, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
+    else
+      hipLaunchKernelGGL(k_msm_bucket_totals, dim3((pl.nb + 255) / 256, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
     if (pl.shared) {
       hipLaunchKernelGGL(k_msm_shared_totals, dim3((pl.nb + 255) / 256), dim3(256), 0, st, bstart, shared_start, pl);
       hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), (size_t)(pl.nb + pl.nb / 32 + 1) * 4, st, shared_start, pl);  // window 0 of a 1-window array
@@ -1706,11 +1595,10 @@ static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const u
       // to itself, or shares it with one other), and the dispatcher does not spread workgroups evenly: 238 workgroups on 256 CUs ran
       // 18.5 us per addition where 104 ran 12.  An LDS reservation the kernel never touches makes the placement explicit: with
       // 96 KB per workgroup a CU (160 KB) takes one, with 56 KB two.
-      static const int spread_knob = knob("NCG_MSM_ACCUM_SPREAD", 1);   // A/B builds: 0 = off
       const size_t wgs = (size_t)grid.x * grid.y;
       size_t reserve = 0;
-      if (spread_knob && wgs <= 256) reserve = 96 * 1024;
-      else if (spread_knob && wgs <= 512) reserve = 56 * 1024;
+      if (wgs <= 256) reserve = 96 * 1024;
+      else if (wgs <= 512) reserve = 56 * 1024;
       if (reserve) {
         static bool attr_done[16] = {};
         int dev = 0;
@@ -1741,16 +1629,14 @@ static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const u
     // scalars, a short top window).
     const double m_avg = (double)av.n / (double)av.nb;
     const int heads_typ = (int)std::ceil((m_avg + 4.0 * std::sqrt(m_avg) + 1.0) / (double)sg.seg);
-    const int run_serial_auto = std::max(knob("NCG_MSM_RUN_SERIAL", MSM_RUN_SERIAL), std::min(8, heads_typ));
+    const int run_serial_auto = std::max(MSM_RUN_SERIAL, std::min(8, heads_typ));
     const bool rs_forced = pl.run_serial_override >= 0;  // ncg_msm_set_tuning: exactly this many (tests force the work list)
     const int run_serial = rs_forced ? pl.run_serial_override : run_serial_auto;
     // the threshold the fix-up kernel actually runs with, decided ONCE (the trace reported another value than the launch
     // used for per-window plans on the cooperative-units kernel)
-    static const int units_knob = knob("NCG_MSM_MERGE_UNITS", -1);   // A/B builds: force on (1) / off (0)
-    const bool merge_units = (pl.shared || (units_knob >= 0 ? units_knob != 0 : run_serial_auto >= 3)) && CoopOK<D>::value;
-    static const int tree_knob = knob("NCG_MSM_MERGE_TREE", 1);   // A/B builds: 0 = one unit per bucket
+    const bool merge_units = (pl.shared || run_serial_auto >= 3) && CoopOK<D>::value;
     // short segments (plans that do not fill the chip): a tree of MERGE_TREE_U units per bucket, up to 16 pieces
-    const bool merge_tree = merge_units && tree_knob && sg.seg < 16;
+    const bool merge_tree = merge_units && sg.seg < 16;
     const int run_serial_eff = rs_forced ? run_serial : std::max(run_serial, merge_tree ? 15 : (merge_units || pl.shared) ? MSM_RUN_SERIAL_SHARED : MSM_RUN_SERIAL);
     if (pl.trace) {
       MsmTrace& tr = *pl.trace;
@@ -1807,8 +1693,7 @@ static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const u
   }
   // fold: nb -> 1 per window in c-1 levels.  Wide levels: one item per addition (throughput); levels that no longer
   // fill the chip: four items per addition (latency, msm_coop.hpp); the last levels + the grouping: k_msm_tail.
-  // cooperative form wherever the group offers it (compile-time); NCG_MSM_COOP_LEVEL=0 keeps the separate level
-  // launches on the one-item-per-addition kernel (A/B of the level kernel only)
+  // cooperative form wherever the group offers it (compile-time) and the level fits the resident lanes
   constexpr bool CAN_COOP = CoopOK<D>::value;
   constexpr bool coop = CAN_COOP;
   const int tail_units = MSM_TAIL_THREADS >> (LS + (coop ? 2 : 0));
@@ -1829,13 +1714,12 @@ static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const u
   }
   // a level that needs more than `tail_rounds` rounds of the tail workgroup's units is a launch of its own: chip-wide it costs
   // 9-13 us, inside the tail 8-12 us PER ROUND (one workgroup per window)
-  static const int tail_rounds = std::max(1, knob("NCG_MSM_TAIL_ROUNDS", NCG_TAIL_ROUNDS));
+  constexpr int tail_rounds = 1;
   while (n_in > 1 && (long)(narr + 1) * (n_in >> 1) > (long)tail_rounds * tail_units) {
     const long total = (long)(narr + 1) * av.nwin * (n_in >> 1);
     bool done = false;
     if constexpr (CAN_COOP) {
-      const bool coop_level = knob("NCG_MSM_COOP_LEVEL", 1) != 0;
-      if (coop && coop_level && total <= coop_max_tasks) {
+      if (coop && total <= coop_max_tasks) {
         using K = TailOps<D, true>;
         const size_t lds_b = (size_t)(256 >> K::UNIT_SHIFT) * COOP_SLOTS * G::FW * 4;
         hipLaunchKernelGGL(k_msm_reduce_level_coop<D>, dim3((unsigned)(((total << K::UNIT_SHIFT) + 255) / 256)), dim3(256), lds_b, st,
@@ -1905,7 +1789,7 @@ static hipError_t msm_finish_t(const MsmPlan& pl, const uint32_t* cur, uint32_t*
     e = hipMemcpyAsync(bad_host, d_bad, 4, hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return e;
   }
-  if (pl.tail_flag && FinishHelpers<C>::value && msm_host64_enabled() && msm_finish_threads_enabled() && h64::finish_threads_override() == 1) {
+  if (pl.tail_flag && FinishHelpers<C>::value && msm_finish_threads_enabled() && h64::finish_threads_override() == 1) {
     // the helper threads of the host finish take 10-50 us to come out of their sleep: wake them when the tail kernel STARTS (it
     // runs ~0.1 ms), not when the stream is done.  Polling a word of pinned memory costs what hipStreamSynchronize's own spin costs.
     volatile uint32_t* flag = pl.tail_flag;
@@ -2052,7 +1936,7 @@ hipError_t msm_enqueue(int curve, const MsmPlan& pl, const uint32_t* d_pts, cons
 }
 // Horner over [ngroups(c)][nwin] grouped window sums in HOST memory (device storage format) + canonical affine output
 void msm_finish_prewake(int curve) {
-  if ((curve == CURVE_BLS12_381_G1 || curve == CURVE_BLS12_381_G2) && msm_host64_enabled() && msm_finish_threads_enabled() &&
+  if ((curve == CURVE_BLS12_381_G1 || curve == CURVE_BLS12_381_G2) && msm_finish_threads_enabled() &&
       h64::finish_threads_override() == 1)
     h64::FinishPool::get().wake();
 }

@@ -110,7 +110,7 @@ int msm_make_plan_endo(int curve, int n_src, int c_override, MsmPlan* pl) {
   pl->n_src = n_src;
   pl->endo = E;
   pl->ls = curve == CURVE_BLS12_381_G2 ? 1 : 0;
-  pl->accum_waves = curve == CURVE_BLS12_381_G2 ? NCG_G2_ACCUM_WAVES : 2;
+  pl->accum_waves = curve == CURVE_BLS12_381_G2 ? G2_ACCUM_WAVES : 2;
   pl->c = c;
   pl->nb = 1 << (c - 1);
   pl->nwin = (bits + c - 1) / c;
@@ -121,8 +121,7 @@ int msm_make_plan_endo(int curve, int n_src, int c_override, MsmPlan* pl) {
   }
   static const uint32_t BLS_R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
   for (int i = 0; i < 8; i++) pl->order[i] = BLS_R[i];
-  static const int q_blocks = std::max(64, knob("NCG_MSM_QBLOCKS", 512));
-  int Q = std::max(1, q_blocks / pl->nwin);
+  int Q = std::max(1, 512 / pl->nwin);   // sort chunks as in msm_plan.hpp
   Q = std::min(Q, std::max(1, n / 4096));
   pl->Q = Q;
   pl->chunk = (n + Q - 1) / Q;

@@ -7,14 +7,12 @@
 
 #include "msm.hpp"
 
+namespace ncg {
+
 // waves/SIMD of the lane-paired G2 accumulate kernel (the whole library must agree: the window plan sizes the lane segment
 // for the kernel's resident-lane capacity).  2 since round 4: with the column-wise Montgomery product (fp29.hpp
-// mont_cols29, NCG_FE29_COLS in msm.o) the kernel needs 232 registers instead of 306.
-#ifndef NCG_G2_ACCUM_WAVES
-#define NCG_G2_ACCUM_WAVES 2
-#endif
-
-namespace ncg {
+// mont_cols29, NCG_FE29_COLS_PAIRED in msm.o) the kernel needs 232 registers instead of 306.
+constexpr int G2_ACCUM_WAVES = 2;
 
 inline void mp_set_bit(uint32_t* a, int bit) { a[bit >> 5] |= 1u << (bit & 31); }
 
@@ -66,8 +64,7 @@ inline int ilog2(unsigned x) {
 // buckets each, so that the region a launch writes (1 MB per window, two windows per XCD) stays in that XCD's 4 MB L2 and
 // leaves it as whole lines.  Only with at least eight windows (fewer would leave XCDs idle: the window-sharded ranks).
 inline void msm_plan_sort_locality(MsmPlan& pl) {
-  static const int xcd = knob("NCG_MSM_XCD", -1);   // A/B builds: force on / off
-  const bool on = xcd >= 0 ? xcd != 0 : pl.nwin >= 8;
+  const bool on = pl.nwin >= 8;
   pl.xcd_map = on ? 1 : 0;
   pl.scatter_passes = on ? 4 : 1;
 }
@@ -90,10 +87,9 @@ inline uint32_t msm_plan_top_vmax(const MsmPlan& pl) {
 // MsmPlan::top_tb: spread a short top window over sub-buckets (its digits are v - half in [0, vmax - half]: H' carries the
 // window's own half, so they are never negative) when it would use at most a quarter of the buckets.
 inline void msm_plan_top_spread(MsmPlan& pl) {
-  static const int on = knob("NCG_MSM_TOP_SPREAD", 1);   // A/B builds: 0 = off
   pl.top_tb = 0;
   pl.top_submask = 0;
-  if (!on || pl.endo || pl.shared) return;
+  if (pl.endo || pl.shared) return;
   const uint32_t half = 1u << (pl.c - 1), vmax = msm_plan_top_vmax(pl);
   const uint32_t maxd = vmax >= half ? vmax - half + 1u : half;   // largest digit (+ 1 of slack)
   int tb = 1;
@@ -137,16 +133,15 @@ inline int msm_make_plan_impl(int curve, int n, int c_override, MsmPlan* pl) {
   pl->n = n;
   pl->ls = curve == CURVE_BLS12_381_G2 ? 1 : 0;  // lane-paired kernels: 2 lanes per item
   // waves/SIMD the accumulate kernel runs at (registers): 4 for the 256-bit fields, 2 for bls12-381 G1, 1 for G2
-  pl->accum_waves = (curve == CURVE_SECP256K1 || curve == CURVE_ED25519) ? 4 : curve == CURVE_BLS12_381_G2 ? NCG_G2_ACCUM_WAVES : 2;
+  pl->accum_waves = (curve == CURVE_SECP256K1 || curve == CURVE_ED25519) ? 4 : curve == CURVE_BLS12_381_G2 ? G2_ACCUM_WAVES : 2;
   pl->c = c;
   pl->nb = 1 << (c - 1);
   pl->nwin = plan_windows(c, curve_order(curve), pl->hconst);
   if (pl->nwin < 0) return -1;
   for (int i = 0; i < 8; i++) pl->order[i] = curve_order(curve)[i];
-  // sort chunks: ~512 blocks per sort kernel (two per CU; measured 2 % faster than 1024 on the 2^20 G1 MSM,
-  // tools/ab_q.sh: half the per-chunk count arrays to write, prefix and read), at least 4096 points per chunk
-  static const int q_blocks = std::max(64, knob("NCG_MSM_QBLOCKS", 512));
-  int Q = std::max(1, q_blocks / pl->nwin);
+  // sort chunks: ~512 blocks per sort kernel (two per CU; measured 2 % faster than 1024 on the 2^20 G1 MSM:
+  // half the per-chunk count arrays to write, prefix and read), at least 4096 points per chunk
+  int Q = std::max(1, 512 / pl->nwin);
   Q = std::min(Q, std::max(1, n / 4096));
   pl->Q = Q;
   pl->chunk = (n + Q - 1) / Q;
@@ -164,9 +159,8 @@ struct MsmSeg {
 };
 inline MsmSeg msm_seg(const MsmPlan& pl) {
   MsmSeg sg;
-  const int seg_knob = pl.seg_override > 0 ? pl.seg_override : knob("NCG_MSM_SEG", 0);
-  if (seg_knob > 0) {
-    sg.seg = seg_knob;
+  if (pl.seg_override > 0) {   // ncg_msm_set_tuning
+    sg.seg = pl.seg_override;
   } else {
     // Every lane adds `seg` consecutive sorted entries, and the accumulate kernel keeps
     // cap = waves/SIMD x 1024 SIMDs x 64 lanes resident, so its time goes like rounds(seg) * seg with

@@ -1,10 +1,7 @@
 // Launchers for the batch variable-base multiply kernels (see mulvar.hpp).
 #include <algorithm>
 #include "mulvar.hpp"
-#include "knobs.hpp"
 #include "host_api.hpp"
-
-#include <cstdlib>
 
 namespace ncg {
 
@@ -125,7 +122,7 @@ hipError_t normalize_batch(int curve, const uint32_t* proj_wire, uint32_t* out_w
 
 size_t mul_var_tmp_bytes(int curve, int n) {
   switch (curve) {
-    // Jacobian scratch + the per-item window table of the widest variant (k_mul_var_gtab)
+    // Jacobian scratch + a per-item window table (k_mul_var_gtab), sized for 5-bit windows (the kernels use 4)
     case CURVE_SECP256K1: return pad64(n) * (3 * FieldIO<CurveSecp::F>::WORDS + gtab_words_per_item<CurveSecp, 5>()) * 4;
     case CURVE_BLS12_381_G1: return pad64(n) * (3 * FieldIO<CurveG1::F>::WORDS + gtab_words_per_item<CurveG1, 5>()) * 4;
     case CURVE_BLS12_381_G2:  // the verified-set ladder (mulvar_endo.hip) keeps a second table per lane
@@ -140,49 +137,18 @@ size_t mul_var_tmp_bytes(int curve, int n) {
 hipError_t mul_var_batch(int curve, const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf,
                          int n, uint32_t* jac_tmp, hipStream_t st) {
   switch (curve) {
-    // Window width / occupancy / table placement, chosen by A/B runs on MI355X (DESIGN.md section 5;
-    // NCG_SECP_W / NCG_G1_W / NCG_G2_W select the alternatives: 1WM = table in device memory with
-    // W-bit windows and M waves/SIMD requested, WM = table in LDS).
-    case CURVE_SECP256K1: {
-#ifdef NCG_AB_BUILD  // the measured alternatives (tools/ab_secp.sh builds with -DNCG_AB_BUILD): not in the shipped library
-      static const int w = knob("NCG_SECP_W", 243);
-      if (jac_tmp && w == 154) return launch_mul_var_gtab<CurveSecp, 5, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 153) return launch_mul_var_gtab<CurveSecp, 5, 3>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 152) return launch_mul_var_gtab<CurveSecp, 5, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w >= 252 && w <= 254) return mul_var_secp_inline(w - 250, pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w >= 243 && w <= 244) return mul_var_secp_inline(w - 230, pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 144) return launch_mul_var_gtab<CurveSecp, 4, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 133) return launch_mul_var_gtab<CurveSecp, 3, 3>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (w == 42) return launch_mul_var<CurveSecp, 4, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-#else
-      if (jac_tmp) return mul_var_secp_inline(13, pts, scalars, out, out_inf, n, jac_tmp, st);  // W = 4, 3 waves/SIMD, multiply inlined
-#endif
+    // Window width / occupancy / table placement, chosen by A/B runs on MI355X:
+    // with scratch the window table sits in device memory, without it in LDS.
+    case CURVE_SECP256K1:
+      if (jac_tmp) return mul_var_secp_inline(pts, scalars, out, out_inf, n, jac_tmp, st);  // W = 4, 3 waves/SIMD, multiply inlined
       return launch_mul_var<CurveSecp, 3, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);  // LDS table (also without scratch)
-    }
     case CURVE_ED25519: return ed25519_mul_var_batch(pts, scalars, out, out_inf, n, jac_tmp, st);
-    case CURVE_BLS12_381_G1: {
-#ifdef NCG_AB_BUILD
-      static const int w = knob("NCG_G1_W", 142);
-      if (jac_tmp && w == 141) return launch_mul_var_gtab<CurveG1, 4, 1>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 152) return launch_mul_var_gtab<CurveG1, 5, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 151) return launch_mul_var_gtab<CurveG1, 5, 1>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 132) return launch_mul_var_gtab<CurveG1, 3, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-      if (jac_tmp && w == 142) return launch_mul_var_gtab<CurveG1, 4, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-#else
+    case CURVE_BLS12_381_G1:
       if (jac_tmp) return launch_mul_var_gtab<CurveG1, 4, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
-#endif
       return launch_mul_var<CurveG1, 3, 1, 8>(pts, scalars, out, out_inf, n, jac_tmp, st);
-    }
-    case CURVE_BLS12_381_G2: {
-#ifdef NCG_AB_BUILD
-      static const int w = knob("NCG_G2_W", 142);
-      if (w == 0) return launch_mul_var<CurveG2, 3, 1, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);  // unpaired
-      if (jac_tmp && w == 142) return launch_mul_var_gtab<CurveG2P, 4, 2, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
-#else
+    case CURVE_BLS12_381_G2:
       if (jac_tmp) return launch_mul_var_gtab<CurveG2P, 4, 2, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
-#endif
       return launch_mul_var<CurveG2P, 2, 2, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
-    }
     default: return hipErrorInvalidValue;
   }
 }

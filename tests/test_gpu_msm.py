@@ -89,8 +89,8 @@ def test_msm_segment_lengths_and_skewed_buckets(monkeypatch, seg, run_serial):
     """Lane-segment boundaries cutting buckets in every possible way, including one bucket that holds every entry (all
     scalars equal) and many empty buckets; with run_serial 0 / 1 every cut bucket takes the long-run work list
     (k_msm_fixup_long), with 50 none does (k_msm_fixup_merge adds every piece serially).  The segment is set through
-    ncg_msm_set_tuning and ncg_msm_last_plan proves that the launch used it (the NCG_MSM_SEG environment
-    knob is honoured by A/B builds only, so the old form of this test ran one configuration four times)."""
+    ncg_msm_set_tuning and ncg_msm_last_plan proves that the launch used it (the old form of this test set an
+    environment variable the shipped library never read, so it ran one configuration four times)."""
     monkeypatch.setenv("NCG_MSM_C", "6")
     eng = get_engine()
     Pt = ORACLE_CURVE[BLS12_381_G1]

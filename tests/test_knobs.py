@@ -35,3 +35,37 @@ def test_only_knobs_hpp_reads_the_environment():
             continue
         text = _read(CSRC, name)
         assert "getenv" not in text, "%s reads the environment directly (use ncg::knob)" % name
+
+
+def _public_knobs():
+    m = re.search(r"pub\[\]\s*=\s*\{([^}]*)\}", _read(CSRC, "knobs.hpp"))
+    assert m, "the list of public knobs moved"
+    return set(re.findall(r'"(NCG_[A-Z0-9_]+)"', m.group(1)))
+
+
+def test_every_knob_read_is_public():
+    """A name outside pub[] would read as a runtime choice but always return its default: a dead switch."""
+    pub = _public_knobs()
+    calls = 0
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith((".hip", ".hpp")) or name == "knobs.hpp":
+            continue
+        text = _read(CSRC, name)
+        for call in re.finditer(r"\bknob(?:_set)?\s*\(", text):
+            calls += 1
+            m = re.match(r'\s*"([^"]*)"', text[call.end():])
+            assert m, "%s: knob call without a string literal name" % name
+            assert m.group(1) in pub, "%s reads %s, which is not a public knob (knobs.hpp pub[])" % (name, m.group(1))
+    assert calls >= len(pub)
+
+
+def test_no_ab_build_mode():
+    """The library has one build: nothing in csrc/, tools/ or the Makefile refers to the removed A/B build flag."""
+    paths = [os.path.join(CSRC, n) for n in sorted(os.listdir(CSRC))]
+    tools = os.path.join(ROOT, "tools")
+    paths += [os.path.join(tools, n) for n in sorted(os.listdir(tools))]
+    for p in paths:
+        if not os.path.isfile(p):
+            continue
+        with open(p, "rb") as f:
+            assert b"NCG_AB_BUILD" not in f.read(), "%s mentions NCG_AB_BUILD" % os.path.relpath(p, ROOT)
