@@ -463,7 +463,10 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * field 7 = the secp256k1 ladder pieces, RAW limbs in and out: a = 27 words, b = 18 words, out = 27 words.  op 0
  * jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) (ec_sw.hpp) with P = a (X, Y, Z at bound 2), qx = b[0..9) at bound 2,
  * qy = b[9..18) at bound 3: out = X, Y, Z; op 2 secp_glv_split + secp_glv_make_odd (scalar.hpp) of the scalar in
- * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg. */
+ * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg.
+ * field 8 = fr29.hpp, the bls12-381 Fr form of the NTT butterflies, RAW limbs in and out: a, b, out = 9 words each.
+ * ops 0 mont(a, b), 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)),
+ * 7 to_words(a) (8 words, then 0). */
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
 #ifdef __cplusplus

@@ -1860,13 +1860,13 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
 
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (field < 0 || field > 7) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 8) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   if (n == 0) return NCG_OK;
   if (n > (1u << 24) || !a || !b || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: bad arguments");
   // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
-  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27
-  static const size_t wa[8] = {9, 9, 12, 28, 56, 18, 18, 27}, wb[8] = {9, 9, 12, 28, 56, 18, 18, 18},
-                      wo[8] = {8, 8, 12, 12, 24, 9, 9, 27};
+  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9
+  static const size_t wa[9] = {9, 9, 12, 28, 56, 18, 18, 27, 9}, wb[9] = {9, 9, 12, 28, 56, 18, 18, 18, 9},
+                      wo[9] = {8, 8, 12, 12, 24, 9, 9, 27, 9};
   const size_t in_wa = wa[field], in_wb = wb[field], out_w = wo[field];
   NCG_HIP(ctx, hipSetDevice(ctx->device));
   const size_t in_ba = (n * in_wa * 4 + 255) & ~(size_t)255, in_bb = (n * in_wb * 4 + 255) & ~(size_t)255, out_b = n * out_w * 4;

@@ -16,7 +16,8 @@
 //     only every third stage and the value below 2^256 once per pass.
 // About 1 200 issue cycles per butterfly.
 //
-// Bounds (checked by tests/test_host_logic.py on the host twin with every operand at its maximum):
+// Bounds (checked with every operand at its maximum by tests/test_host_logic.py on the host twin, and by
+// tests/test_gpu_field.py on the device, where fr29_mont is the generated asm; the two share their cases):
 //   * "limb bound A": every limb below A * 2^29 (limb 8 may use the full 32 bits).
 //   * fr29_mont(b, w): b with limb bound <= 6, w with exact limbs (< 2^29): columns stay below
 //     (9*6 + 8) * 2^58 + 2^36 < 2^64.  Result: exact limbs, value below val(b) * r / 2^261 + r.

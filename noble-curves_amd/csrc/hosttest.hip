@@ -4,6 +4,7 @@
 // Built into tests/_build/libncg_hosttest.so; never linked into libncg.so, never a fallback.
 #include <vector>
 
+#include "../../include/ncg.h"  // NCG_NTT_MAX_LOG2N
 #include "mulvar.hpp"
 #include "ed25519.hip"  // single-TU inclusion: lane function + host table builder
 #include "decode.hip"
@@ -424,6 +425,19 @@ int ht_fr29_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
   for (int i = 0; i < 9; i++) r[i] = z.v[i];
   return fr29_overflows();
 }
+// the pass schedule of ntt_run (the shipped ntt_schedule with the device's pass limits and table): 11 ints per pass,
+// T logC colhi dit inverse brp_store scale canon s_lo in out (buffers 0 src, 1 dst, 2 ws); returns the number of passes
+int ht_ntt_schedule(int n, int flags, int* out) {
+  if (n < 0 || n > NCG_NTT_MAX_LOG2N || flags < 0 || flags > 7) return -1;
+  const NttSchedule sc = ntt_schedule(n, n, flags);
+  for (int k = 0; k < sc.np; k++) {
+    const NttPass& ps = sc.ps[k];
+    const int row[11] = {ps.T, ps.logC, ps.colhi, ps.dit, ps.inverse, ps.brp_store, ps.scale, ps.canon, ps.s_lo, sc.in[k], sc.out[k]};
+    for (int i = 0; i < 11; i++) out[11 * k + i] = row[i];
+  }
+  return sc.np;
+}
+int ht_ntt_max_log2n() { return NCG_NTT_MAX_LOG2N; }
 // the pass planner of ntt_run: writes s_lo/T pairs, returns the number of passes
 int ht_ntt_plan(int n, int* out) {
   int s_lo[8], T[8];

@@ -3,6 +3,7 @@
 // not on the product path.
 #include "curves.hpp"
 #include "fp29.hpp"
+#include "fr29.hpp"
 
 namespace ncg {
 
@@ -369,6 +370,48 @@ __global__ void __launch_bounds__(64) k_field_check_secp_ladder(int op, const ui
     r[18 + j] = R.Z.v[j];
   }
 }
+// fr29.hpp (the NTT butterflies' form of bls12-381 Fr) on RAW limbs, ops numbered as hosttest.hip's ht_fr29_op: 0 mont(a, b),
+// 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)), 7 to_words(a) (8 words, then 0).
+// a, b, out: 9 words per item, so that the tests check the output limbs as well as the value.
+__global__ void __launch_bounds__(64) k_field_check_fr29(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                         uint32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t *pa = a + (size_t)i * 9, *pb = b + (size_t)i * 9;
+  uint32_t* r = out + (size_t)i * 9;
+  Fr29 x, y, z;
+#pragma unroll
+  for (int j = 0; j < 9; j++) {
+    x.v[j] = pa[j];
+    y.v[j] = pb[j];
+    z.v[j] = 0;
+  }
+  switch (op) {
+    case 0: z = fr29_mont(x, y); break;
+    case 1: z = fr29_add(x, y); break;
+    case 2: z = fr29_sub(x, y); break;
+    case 3: z = fr29_weak(x); break;
+    case 4: z = fr29_reduce256(x); break;
+    case 5: z = fr29_cond_sub(x); break;
+    case 6: {
+      uint32_t w[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) w[j] = pa[j];
+      z = fr29_from_words(w);
+      break;
+    }
+    case 7: {
+      uint32_t w[8];
+      fr29_to_words(w, x);
+#pragma unroll
+      for (int j = 0; j < 8; j++) z.v[j] = w[j];
+      break;
+    }
+    default: return;
+  }
+#pragma unroll
+  for (int j = 0; j < 9; j++) r[j] = z.v[j];
+}
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
                            hipStream_t st) {
   if (n <= 0) return hipSuccess;
@@ -381,6 +424,7 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 5) hipLaunchKernelGGL(k_field_check_fused<Fe9SecpPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 6) hipLaunchKernelGGL(k_field_check_fused<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 7) hipLaunchKernelGGL(k_field_check_secp_ladder, grid, block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 8) hipLaunchKernelGGL(k_field_check_fr29, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 """Shared helpers for parity tests: wire-format marshalling between oracle points and the
-C-ABI byte layout (include/ncg.h); raw Fe9 limbs and secp256k1 affine / Jacobian references for the
+C-ABI byte layout (include/ncg.h); the NTT sweep's size bound; raw Fe9 limbs and secp256k1 affine / Jacobian references for the
 fused-ladder tests; a model of the secp256k1 ladder's exceptional events."""
 import json
 import os
@@ -12,6 +12,9 @@ from oracle.curves import SECP256K1_N, SECP256K1_P, BlsG1, BlsG2, Ed25519, Secp2
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 ORACLE_CURVE = {SECP256K1: Secp256k1, BLS12_381_G1: BlsG1, BLS12_381_G2: BlsG2, ED25519: Ed25519}
+# the largest transform test_gpu_ntt.py's sweep runs: every NTT pass shape (ntt.hip ntt_schedule) occurs at or below it,
+# which test_host_logic.py's test_ntt_sweep_reaches_every_pass_shape checks against the planner
+NTT_SWEEP_MAX_LOG2N = 24
 
 
 def load_golden(name):

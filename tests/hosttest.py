@@ -29,6 +29,7 @@ def lib():
         _lib.ht_map_to_curve.argtypes = [i32, vp, i32, vp, vp, i32]
         _lib.ht_ntt.argtypes = [i32, vp, vp, vp, i32]
         _lib.ht_ntt_plan.argtypes = [i32, vp]
+        _lib.ht_ntt_schedule.argtypes = [i32, i32, vp]
         _lib.ht_ntt_small_passes.argtypes = [i32, vp, vp, vp, i32, i32, i32]
         _lib.ht_fr29_op.argtypes = [i32, vp, vp, vp]
         _lib.ht_fe9_op.argtypes = [i32, i32, i32, vp, vp, vp]
@@ -193,6 +194,24 @@ def ntt(log2n, values, omega, flags, passes=None):
                                          passes[0], passes[1]) == 0
     b = out.tobytes()
     return [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(n)]
+
+
+NTT_PASS_FIELDS = ("T", "logC", "colhi", "dit", "inverse", "brp_store", "scale", "canon", "s_lo", "src", "dst")
+
+
+def ntt_max_log2n():
+    """NCG_NTT_MAX_LOG2N (include/ncg.h): the largest transform the library takes."""
+    return lib().ht_ntt_max_log2n()
+
+
+def ntt_schedule(log2n, flags):
+    """The passes ntt_run launches for (log2n, flags) - ntt.hip's ntt_schedule itself - as dicts of NTT_PASS_FIELDS;
+    src / dst name the buffer a pass reads / writes: 0 the input, 1 the output, 2 the workspace."""
+    out = np.zeros(8 * len(NTT_PASS_FIELDS), dtype=np.int32)
+    np_ = lib().ht_ntt_schedule(log2n, flags, out.ctypes.data)
+    assert 0 <= np_ <= 8, (log2n, flags)
+    rows = out[:np_ * len(NTT_PASS_FIELDS)].reshape(np_, len(NTT_PASS_FIELDS))
+    return [dict(zip(NTT_PASS_FIELDS, (int(x) for x in row))) for row in rows]
 
 
 def fr29_op(op, a_limbs, b_limbs=None):

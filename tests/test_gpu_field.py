@@ -2,7 +2,7 @@
 inline-asm multiply-add chains, interleaved fold, bound-typed lazy add / sub / normalise / zero test /
 addition-chain inversion for secp256k1 and ed25519, and the radix-2^29 Montgomery code for bls12-381 -
 against big-int arithmetic (modular.ts:940-982 values), with operands at the top of what each bound type
-admits and at the special values of each prime."""
+admits and at the special values of each prime; the Fr form of the NTT butterflies (fr29.hpp) on raw limbs."""
 import numpy as np
 import pytest
 
@@ -168,3 +168,20 @@ def test_lane_paired_fp2_raw_limbs_at_the_bounds(op):
     out = eng.field_check(4, op, 0, np.array(A, dtype=np.uint32), np.array(B, dtype=np.uint32))
     for i in range(len(exp)):
         assert (_words(out[i][:12]), _words(out[i][12:])) == exp[i], (op, i)
+
+
+@pytest.mark.parametrize("op", range(8))
+def test_fr29_on_device_at_the_bounds(op):
+    """fr29.hpp - the NTT butterflies' Fr form, whose Montgomery product is the generated asm of fr29_asm_gen.hpp on the
+    device and plain C++ on the host twin - through ncg_field_check field 8 on the cases of the host test (operands at the
+    bounds each op admits: the 64-bit columns of fr29_mont are tight only for a left operand at 6 * 2^29 with limb 8 all
+    ones), the same value and output-limb assertions; 120 rows and more per launch, so a full wave and a partial one."""
+    from test_host_logic import _fr29_cases
+    rows_a, rows_b, check = _fr29_cases()[op]
+    assert len(rows_a) >= 120
+    out = get_engine().field_check(8, op, 0, np.array(rows_a, dtype=np.uint32), np.array(rows_b, dtype=np.uint32))
+    for i, (a, b) in enumerate(zip(rows_a, rows_b)):
+        try:
+            check(a, b, [int(x) for x in out[i]])
+        except AssertionError as e:
+            raise AssertionError("op %d row %d: a %s b %s out %s" % (op, i, a, b, [int(x) for x in out[i]])) from e

@@ -1,14 +1,16 @@
-"""GPU parity for the NTT over bls12-381 Fr through the C ABI (`ncg_ntt`)."""
+"""GPU parity for the NTT over bls12-381 Fr through the C ABI (`ncg_ntt`, `ncg_ntt_dev`)."""
 import numpy as np
 import pytest
+import torch
 
 from noble_curves_amd import fft as G
 from noble_curves_amd import get_engine
 from noble_curves_amd._native import ints_to_le, le_to_ints
+from oracle import cport
 from oracle.curves import Fr_bls, makeRng
 from oracle.fft import FFT, RootsOfUnity, bitReversalPermutation
 
-from helpers import load_golden
+from helpers import NTT_SWEEP_MAX_LOG2N, load_golden
 
 pytestmark = pytest.mark.gpu
 R = Fr_bls.ORDER
@@ -82,7 +84,7 @@ def test_ntt_three_pass_size_matches_oracle():
 
 
 def test_ntt_extreme_values_at_the_bench_size():
-    """2^22 (the bench's size: 8 + 7 + 7 stages natural -> natural, 10 + 6 + 6 otherwise) on the inputs that build up the
+    """2^22 (the bench's size: three passes of 8 + 7 + 7 stages in every ordering) on the inputs that build up the
     largest lazily reduced values the fr29 butterflies can meet - every coefficient r - 1, and r - 1 / 0 alternating - whose
     transforms are known in closed form: N (r - 1) at index 0 (and N/2 (r - 1) at 0 and N/2), zero elsewhere.  Raw arrays
     in and out; natural and bit-reversed output, inverse round trip."""
@@ -198,3 +200,200 @@ def test_fft_is_evaluation_at_roots_gpu():
         assert f.direct(a) == exp
         assert f.direct(a, False, True) == G.bitReversalPermutation(exp)
         assert roots.inverse(bits)[1:] == om[1:][::-1] and roots.inverse(bits)[0] == 1
+
+
+# ---- every pass shape of the schedule on the device.  ntt_schedule (ntt.hip) turns (log2n, flags) into passes that differ in
+# what k_ntt_pass branches on (stages per tile, tile columns, DIT / DIF, inverse, bit-reversed store, 1/N scale, canonical
+# store, src / ws / dst hand-over); every shape the planner can produce occurs at 2^NTT_SWEEP_MAX_LOG2N or below
+# (test_host_logic.py checks that), so the sweep runs every size up to it in all 8 orderings, out of place on a side stream.
+ORDERINGS = [dict(inverse=bool(f & 1), brp_input=bool(f & 2), brp_output=bool(f & 4)) for f in range(8)]
+ORACLE_MAX_LOG2N = 22           # oracle/c transforms up to here (about 5 s at 2^22); above, identities and sampled outputs
+
+
+def _le(v):
+    return np.frombuffer(int(v).to_bytes(32, "little"), dtype=np.uint8)
+
+
+def _below_r(c):
+    """rows of uint8 [k, 32] (little-endian) that are below r"""
+    w = c.view("<u8").reshape(-1, 4)
+    lt, eq = np.zeros(len(w), dtype=bool), np.ones(len(w), dtype=bool)
+    for i in (3, 2, 1, 0):
+        ri = np.uint64((R >> (64 * i)) & ((1 << 64) - 1))
+        lt |= eq & (w[:, i] < ri)
+        eq &= w[:, i] == ri
+    return lt
+
+
+def _input_a(bits, seed):
+    """uniform canonical residues with 0, 1, r - 1 at the front and then r - 1 - j, j < 64"""
+    n = 1 << bits
+    gen = np.random.default_rng(seed)
+    out, filled = np.empty((n, 32), dtype=np.uint8), 0
+    while filled < n:
+        c = gen.integers(0, 256, size=(n - filled + (n - filled) // 4 + 16, 32), dtype=np.uint8)
+        c[:, 31] &= 0x7F
+        c = c[_below_r(c)][:n - filled]
+        out[filled:filled + len(c)] = c
+        filled += len(c)
+    for i, v in enumerate([0, 1, R - 1] + [R - 1 - j for j in range(64)][:n]):
+        if i < n:
+            out[i] = _le(v)
+    return out
+
+
+def _brev_index(bits, dev):
+    i = torch.arange(1 << bits, device=dev, dtype=torch.int64)
+    rev = torch.zeros_like(i)
+    for b in range(bits):
+        rev |= ((i >> b) & 1) << (bits - 1 - b)
+    return rev
+
+
+def _sum_mod_r(t):
+    """sum of the residues of a uint8 [n, 32] tensor mod r (64-bit column sums of the 32-bit words)"""
+    w = t.cpu().numpy().view("<u4").reshape(-1, 8)
+    cols = w.sum(axis=0, dtype=np.uint64)
+    return sum(int(c) << (32 * j) for j, c in enumerate(cols)) % R
+
+
+class _Dev:
+    """ncg_ntt_dev out of place on a non-default stream; the input must come back unchanged"""
+
+    def __init__(self, eng):
+        self.eng, self.dev = eng, torch.device("cuda", 0)
+        self.stream = torch.cuda.Stream(device=self.dev)
+
+    def __call__(self, bits, om, x, batch=1, **kw):
+        y = torch.full_like(x, 0xFF)                # not a residue: an element the transform does not write shows
+        keep = x.clone()
+        torch.cuda.synchronize()
+        self.eng.ntt_dev(bits, batch, om, x.data_ptr(), y.data_ptr(), self.stream.cuda_stream, **kw)
+        self.stream.synchronize()
+        assert torch.equal(x, keep), ("ncg_ntt_dev wrote its input", bits, kw)
+        return y
+
+
+@pytest.mark.parametrize("bits", range(NTT_SWEEP_MAX_LOG2N + 1))
+def test_ntt_sweep_every_schedule(bits):
+    """log2n = bits in all 8 (inverse, brpInput, brpOutput) orderings through ncg_ntt_dev (out of place, side stream) and
+    ncg_ntt (host buffers, in place), which must agree byte for byte.  (a) uniform residues with 0, 1, r - 1 and a run of
+    r - 1 - j: against oracle/c's FFT up to 2^22 (one oracle call: y = D(x); direct orderings map x or brp(x) to y or
+    brp(y), inverse ones y or brp(y) back to x or brp(x)), above it against the device's own natural-order transform
+    (all orderings agree under bit reversal and round-trip) pinned by y[0] = sum x and sum y = N x[0] and by a sparse
+    input whose transform is checked at 1024 sampled outputs.  (b) all r - 1 and (c) r - 1, 0 alternating - the largest
+    lazily reduced values - against their closed forms."""
+    eng = get_engine()
+    dev = torch.device("cuda", 0)
+    run = _Dev(eng)
+    n = 1 << bits
+    om = G.rootsOfUnity(G.bls12_381_Fr, 7).omega(bits)
+    rev = _brev_index(bits, dev)
+
+    def check_all(x, y, what, host=False):
+        """x, y: natural-order pair with y = D(x) (device tensors)"""
+        for kw in ORDERINGS:
+            src, exp = (y, x) if kw["inverse"] else (x, y)
+            inp = src[rev] if kw["brp_input"] else src
+            want = exp[rev] if kw["brp_output"] else exp
+            got = run(bits, om, inp, **kw)
+            if not torch.equal(got, want):
+                bad = (got != want).any(dim=1).nonzero().flatten()
+                raise AssertionError("2^%d %s %s: %d wrong elements, first at %s" % (bits, what, kw, len(bad), bad[:8].tolist()))
+            if host:
+                h = eng.ntt(bits, inp.cpu().numpy(), om, **kw)
+                assert np.array_equal(h, got.cpu().numpy()), ("ncg_ntt != ncg_ntt_dev", bits, what, kw)
+
+    # (a) random residues
+    xa_np = _input_a(bits, 0x5EE9 + bits)
+    xa = torch.from_numpy(xa_np).to(dev)
+    if bits <= ORACLE_MAX_LOG2N:
+        ya = torch.from_numpy(cport.fft_fr(bits, xa_np, om)).to(dev)
+    else:
+        ya = run(bits, om, xa)
+        assert int.from_bytes(ya[0].cpu().numpy().tobytes(), "little") == _sum_mod_r(xa)
+        assert _sum_mod_r(ya) == n * int.from_bytes(xa_np[0].tobytes(), "little") % R
+    check_all(xa, ya, "random", host=True)
+    del xa, ya, xa_np
+
+    # (b) all r - 1: D = N (r - 1) at 0; (c) r - 1 / 0 alternating: D = N/2 (r - 1) at 0 and N/2
+    top = torch.from_numpy(_le(R - 1).copy()).to(dev)
+    xb = top.repeat(n, 1)
+    yb = torch.zeros_like(xb)
+    yb[0] = torch.from_numpy(_le(n * (R - 1) % R).copy()).to(dev)
+    check_all(xb, yb, "all r - 1")
+    xc = xb.clone()
+    xc[1::2] = 0
+    yc = torch.zeros_like(xc)
+    half = torch.from_numpy(_le(max(n // 2, 1) * (R - 1) % R).copy()).to(dev)
+    yc[0] = half
+    yc[n // 2] = half
+    check_all(xc, yc, "r - 1, 0 alternating")
+    del xb, yb, xc, yc
+
+    if bits > ORACLE_MAX_LOG2N:   # sparse input: y[k] = sum c_t w^(j_t k), sampled at k = 0, 1, N/2, N - 1 and 1020 more
+        rng = makeRng(0x5A75E + bits)
+        pos = [0, n - 1] + [rng.rndBelow(n) for _ in range(6)]
+        cs = [R - 1 - rng.rndBelow(1 << 20) for _ in pos]
+        xs = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+        coef = {}
+        for j, c in zip(pos, cs):
+            coef[j] = (coef.get(j, 0) + c) % R
+        for j, c in coef.items():
+            xs[j] = torch.from_numpy(_le(c).copy()).to(dev)
+        ks = [0, 1, n // 2, n - 1] + [rng.rndBelow(n) for _ in range(1020)]
+        ninv = pow(n, -1, R)
+        fwd = [sum(c * pow(om, j * k % n, R) for j, c in coef.items()) % R for k in ks]
+        bwd = [sum(c * pow(om, -j * k % n, R) for j, c in coef.items()) * ninv % R for k in ks]
+        kt = torch.tensor(ks, dtype=torch.int64, device=dev)
+        for kw in ORDERINGS:
+            got = run(bits, om, xs[rev] if kw["brp_input"] else xs, **kw)
+            rows = got[rev[kt] if kw["brp_output"] else kt].cpu().numpy()
+            vals = [int.from_bytes(r.tobytes(), "little") for r in rows]
+            assert vals == (bwd if kw["inverse"] else fwd), ("sparse", bits, kw)
+
+
+@pytest.mark.parametrize("bits", [9, 13, 19])
+def test_ntt_batch_of_three_every_ordering(bits):
+    """blockIdx.y carries the polynomial: batch 3 at one size per pass count (1, 2 and 3 passes) in every ordering ==
+    each polynomial's own transform"""
+    eng = get_engine()
+    dev = torch.device("cuda", 0)
+    run = _Dev(eng)
+    n = 1 << bits
+    om = G.rootsOfUnity(G.bls12_381_Fr, 7).omega(bits)
+    x = torch.from_numpy(np.concatenate([_input_a(bits, 0xBA7 + 7 * bits + i) for i in range(3)])).to(dev)
+    for kw in ORDERINGS:
+        out = run(bits, om, x, batch=3, **kw)
+        for b in range(3):
+            one = run(bits, om, x[b * n:(b + 1) * n].contiguous(), **kw)
+            assert torch.equal(out[b * n:(b + 1) * n], one), (bits, b, kw)
+
+
+def test_ntt_workspace_regrow_and_twiddle_cache_on_one_context():
+    """On a fresh context: a small folded multi-pass transform, then a larger batch that regrows the workspace
+    (ncg_ntt_dev), then a smaller one that reuses it; and, at one size, the twiddle table alternating between three
+    primitive roots of the same order (w, w^(N-1), w^3) - the table is cached per size and rebuilt when the root
+    changes.  Every result against oracle/c with the root in use."""
+    from noble_curves_amd._native import Engine
+    eng = Engine(0)
+    try:
+        dev = torch.device("cuda", 0)
+        run = _Dev(eng)
+        roots = G.rootsOfUnity(G.bls12_381_Fr, 7)
+        for bits, batch, flags in ((11, 1, 0), (13, 3, 0), (14, 2, 6), (12, 2, 7)):
+            om = roots.omega(bits)
+            kw = ORDERINGS[flags]
+            xs = [_input_a(bits, 0x3E6 + 31 * bits + i) for i in range(batch)]
+            out = run(bits, om, torch.from_numpy(np.concatenate(xs)).to(dev), batch=batch, **kw).cpu().numpy()
+            for b, x in enumerate(xs):
+                assert np.array_equal(out[b << bits:(b + 1) << bits], cport.fft_fr(bits, x, om, **kw)), (bits, batch, flags, b)
+        bits = 12
+        n = 1 << bits
+        w = roots.omega(bits)
+        x = _input_a(bits, 0x7C4C)
+        for i, om in enumerate((w, pow(w, n - 1, R), w, pow(w, 3, R), pow(w, n - 1, R), pow(w, 3, R), w)):
+            kw = ORDERINGS[(0, 1, 4, 3, 6, 5, 7)[i]]
+            assert np.array_equal(eng.ntt(bits, x, om, **kw), cport.fft_fr(bits, x, om, **kw)), (i, om == w, kw)
+    finally:
+        eng.close()

@@ -357,17 +357,29 @@ def _fr29_limbs(x):
     return [(x >> (29 * i)) & ((1 << 29) - 1) for i in range(8)] + [x >> 232]
 
 
-def test_fr29_butterfly_arithmetic_at_the_bounds():
-    """fr29.hpp (the NTT butterflies' radix-2^29 lazy form of Fr, modular.ts:940-982 values at the pass
-    boundaries): Montgomery product with the left operand at the loosest limbs it admits (6 * 2^29, limb 8
-    all ones) and the right one at r - 1 / all-ones limbs, the fold below 2^256 from 33 r, the final
-    conditional subtraction and the word <-> limb conversions, against big-int arithmetic; the host
-    twin counts every 64-bit column and 32-bit limb overflow (must be none)."""
+# Fr29PR::BIAS (consts_gen.hpp): 3 r with every limb above what an exact limb (limb 8: a value below 2.99 r) can hold
+_FR29_BIAS = [0x20000003, 0x3FFFFFE7, 0x3EC4FF3E, 0x31D811FE, 0x3880FFB2, 0x240C0E71, 0x3F6266B5, 0x3F2F9B0D, 0x015BC8F4]
+
+
+def _fr29_cases():
+    """The operands of fr29.hpp's ops at the bounds they admit, shared by the host twin (below) and the device
+    (test_gpu_field.py, where fr29_mont is the generated asm): {op: (a rows, b rows, check)}, rows of 9 raw words
+    numbered as ht_fr29_op / ncg_field_check field 8, check(a, b, out) asserting the value and the output limbs of
+    one row.  Montgomery product with the left operand at the loosest limbs it admits (6 * 2^29, limb 8 all ones) and
+    the right one at r - 1 / all-ones limbs, the fold below 2^256 from 33 r, the final conditional subtraction, the
+    word <-> limb conversions, a - t through the 3 r bias, a + t and the weak normalisation, 120 rows per op or more."""
     from oracle.curves import Fr_bls
     r = Fr_bls.ORDER
     M = (1 << 29) - 1
     rinv = pow(1 << 261, -1, r)
+    assert _fr29_val(_FR29_BIAS) == 3 * r
     rng = makeRng(0xF29)
+    cases = {op: ([], [], None) for op in range(8)}
+
+    def add(op, a, b=None):
+        cases[op][0].append(list(a))
+        cases[op][1].append(list(b) if b is not None else [0] * 9)
+
     for trial in range(120):
         a = [rng.rndBelow(6 << 29) for _ in range(8)] + [rng.rndBelow(1 << 32)]
         w = _fr29_limbs(rng.rndBelow(r))
@@ -377,35 +389,64 @@ def test_fr29_butterfly_arithmetic_at_the_bounds():
             w = _fr29_limbs(r - 1)
         if trial == 2:
             a, w = [(6 << 29) - 1] * 8 + [(1 << 32) - 1], [M] * 8 + [(1 << 23) - 1]
-        out, ovf = hosttest.fr29_op(0, a, w)
-        assert ovf == 0
-        assert _fr29_val(out) % r == _fr29_val(a) * _fr29_val(w) * rinv % r
-        assert all(x <= M for x in out[:8]) and _fr29_val(out) < _fr29_val(a) * _fr29_val(w) // (1 << 261) + r + 1
+        add(0, a, w)
     for trial in range(120):
         v = rng.rndBelow(33 * r) if trial else 33 * r - 1
-        out, ovf = hosttest.fr29_op(4, _fr29_limbs(v))
-        assert ovf == 0 and _fr29_val(out) % r == v % r and _fr29_val(out) < (1 << 256) and all(x <= M for x in out[:8])
-        a = [rng.rndBelow(7 << 29) for _ in range(8)] + [rng.rndBelow(1 << 28)]     # loose limbs, value < 33 r
-        out, ovf = hosttest.fr29_op(4, a)
-        assert ovf == 0 and _fr29_val(out) % r == _fr29_val(a) % r and _fr29_val(out) < (1 << 256)
-    for trial in range(60):
+        add(4, _fr29_limbs(v))
+        add(4, [rng.rndBelow(7 << 29) for _ in range(8)] + [rng.rndBelow(1 << 28)])     # loose limbs, value < 33 r
+    for trial in range(120):
         v = [0, r - 1, r, 2 * r - 1][trial] if trial < 4 else rng.rndBelow(2 * r)
-        out, _ = hosttest.fr29_op(5, _fr29_limbs(v))
-        assert _fr29_val(out) == v % r
-        out, _ = hosttest.fr29_op(6, [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] + [0])
-        assert _fr29_val(out) == v and all(x <= M for x in out[:8])
-        out, _ = hosttest.fr29_op(7, _fr29_limbs(v))
-        assert sum(x << (32 * i) for i, x in enumerate(out[:8])) == v
-    # a - t through the 3 r bias, a + t, and the weak normalisation keep the value
-    for trial in range(60):
+        add(5, _fr29_limbs(v))
+        add(6, [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] + [0])
+        add(7, _fr29_limbs(v))
+    for trial in range(120):
         a = [rng.rndBelow(5 << 29) for _ in range(8)] + [rng.rndBelow(1 << 28)]
         t = _fr29_limbs(rng.rndBelow(29 * r // 10) if trial else (0x015BC8F4 << 232) + (1 << 232) - 1)  # limb 8 at BIAS[8]
-        d, ovf = hosttest.fr29_op(2, a, t)
-        assert ovf == 0 and _fr29_val(d) == _fr29_val(a) + 3 * r - _fr29_val(t)
-        sm, ovf = hosttest.fr29_op(1, a, t)
-        assert ovf == 0 and _fr29_val(sm) == _fr29_val(a) + _fr29_val(t)
-        wk, ovf = hosttest.fr29_op(3, d)
-        assert ovf == 0 and _fr29_val(wk) == _fr29_val(d) and all(x < (1 << 29) + 8 for x in wk[:8])
+        add(2, a, t)
+        add(1, a, t)
+        add(3, [x + k - y for x, k, y in zip(a, _FR29_BIAS, t)])     # the limbs a - t leaves (checked under op 2)
+
+    def mont(a, w, out):
+        assert _fr29_val(out) % r == _fr29_val(a) * _fr29_val(w) * rinv % r
+        assert all(x <= M for x in out[:8]) and _fr29_val(out) < _fr29_val(a) * _fr29_val(w) // (1 << 261) + r + 1
+
+    def reduce256(a, _, out):
+        assert _fr29_val(out) % r == _fr29_val(a) % r and _fr29_val(out) < (1 << 256) and all(x <= M for x in out[:8])
+
+    def cond_sub(a, _, out):
+        assert _fr29_val(out) == _fr29_val(a) % r and all(x <= M for x in out[:8])
+
+    def from_words(a, _, out):
+        assert _fr29_val(out) == sum(x << (32 * i) for i, x in enumerate(a[:8])) and all(x <= M for x in out[:8])
+
+    def to_words(a, _, out):
+        assert sum(x << (32 * i) for i, x in enumerate(out[:8])) == _fr29_val(a) and out[8] == 0
+
+    def sub(a, t, out):
+        assert _fr29_val(out) == _fr29_val(a) + 3 * r - _fr29_val(t)
+        assert list(out) == [x + k - y for x, k, y in zip(a, _FR29_BIAS, t)]
+
+    def add_(a, t, out):
+        assert _fr29_val(out) == _fr29_val(a) + _fr29_val(t)
+
+    def weak(d, _, out):
+        assert _fr29_val(out) == _fr29_val(d) and all(x < (1 << 29) + 8 for x in out[:8])
+
+    for op, check in enumerate((mont, add_, sub, weak, reduce256, cond_sub, from_words, to_words)):
+        cases[op] = (cases[op][0], cases[op][1], check)
+    return cases
+
+
+def test_fr29_butterfly_arithmetic_at_the_bounds():
+    """fr29.hpp (the NTT butterflies' radix-2^29 lazy form of Fr, modular.ts:940-982 values at the pass
+    boundaries) on the cases of _fr29_cases against big-int arithmetic; the host twin counts every 64-bit column
+    and 32-bit limb overflow (must be none)."""
+    for op, (rows_a, rows_b, check) in _fr29_cases().items():
+        assert len(rows_a) >= 120
+        for a, b in zip(rows_a, rows_b):
+            out, ovf = hosttest.fr29_op(op, a, b)
+            assert ovf == 0, (op, a, b)
+            check(a, b, out)
 
 
 def test_ntt_multi_pass_schedules_and_full_size_passes():
@@ -442,6 +483,27 @@ def test_ntt_pass_plan_covers_every_stage_once():
             s += t
         assert s == n + 1
     assert hosttest.ntt_plan(0) == []
+
+
+def test_ntt_sweep_reaches_every_pass_shape():
+    """test_gpu_ntt.py runs every size up to NTT_SWEEP_MAX_LOG2N in all 8 orderings on the device; every pass shape
+    the planner can produce up to NCG_NTT_MAX_LOG2N - what k_ntt_pass branches on, with the buffers a pass reads and
+    writes - must occur there.  Every schedule runs each stage once and chains its buffers input -> (workspace ->) output."""
+    from helpers import NTT_SWEEP_MAX_LOG2N
+    shape_keys = [k for k in hosttest.NTT_PASS_FIELDS if k != "s_lo"]
+    first = {}
+    for n in range(hosttest.ntt_max_log2n() + 1):
+        for flags in range(8):
+            passes = hosttest.ntt_schedule(n, flags)
+            assert sorted(st for ps in passes for st in range(ps["s_lo"], ps["s_lo"] + ps["T"])) == list(range(1, n + 1))
+            for k, ps in enumerate(passes):
+                assert ps["src"] == (0 if k == 0 else passes[k - 1]["dst"]), (n, flags, k)
+                assert ps["dst"] in (1, 2) and (ps["dst"] == 1) >= (k == len(passes) - 1), (n, flags, k)
+                first.setdefault(tuple(ps[f] for f in shape_keys), (n, flags))
+    missing = sorted({nf for nf in first.values() if nf[0] > NTT_SWEEP_MAX_LOG2N})
+    assert not missing, "pass shapes first met above 2^%d: add these (log2n, flags) to test_gpu_ntt.py's sweep: %s" % (
+        NTT_SWEEP_MAX_LOG2N, missing)
+    assert len(first) >= 172
 
 
 def h2c_cases(m, count, n):
