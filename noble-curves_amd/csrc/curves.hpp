@@ -19,8 +19,12 @@ struct CurveSecp {  // src/secp256k1.ts:48-64
 };
 // The same curve with the ladder-local fused formulas (ec_sw.hpp jac_dbl_neg / jac_madd_neg) in mul_var_lane: the batch
 // multiply with the field multiply inlined (mulvar_inl.hip).  Its own name gives its kernels their own symbols.
+// K1_ODD: secp_glv_make_k1_odd instead of secp_glv_make_odd - both halves below 2^128, so 32 windows of 4 bits per half instead
+// of 33, and one subtraction of psi(P) after the ladder for an even k2.
 struct CurveSecpI : CurveSecp {
   static constexpr bool FUSED_LADDER = true;
+  static constexpr bool ODD_HALVES = false;
+  static constexpr bool K1_ODD = true;
 };
 struct CurveG1 {  // src/bls12-381.ts:134-148; no endomorphism in the reference (and inputs are
   using F = FeBls;  // not subgroup-checked), so none here either (SURVEY 8a gotcha 1)

@@ -337,6 +337,21 @@ int ht_glv_split_odd(const uint32_t* k, uint32_t* out) {
   return 0;
 }
 
+// secp_glv_split followed by secp_glv_make_k1_odd (the split of CurveSecpI's ladder); layout of ht_glv_split
+int ht_glv_split_k1_odd(const uint32_t* k, uint32_t* out) {
+  uint32_t kk[8];
+  for (int i = 0; i < 8; i++) kk[i] = k[i];
+  GlvSplit s = secp_glv_split(kk);
+  secp_glv_make_k1_odd(s);
+  for (int i = 0; i < 5; i++) {
+    out[i] = s.k1[i];
+    out[5 + i] = s.k2[i];
+  }
+  out[10] = s.k1neg;
+  out[11] = s.k2neg;
+  return 0;
+}
+
 // GLV split of a 256-bit scalar: out = k1[5] k2[5] k1neg k2neg (12 words)
 int ht_glv_split(const uint32_t* k, uint32_t* out) {
   uint32_t kk[8];

@@ -89,9 +89,12 @@ NCG_DI Jac<typename C::F> mul_var_slow(const uint32_t* __restrict__ pt_wire, con
 }
 
 // Curve traits of the ladder (absent = false).  ODD_HALVES: the GLV halves come out odd (secp_glv_make_odd), so there is no
-// was_even fix-up at the end.  FUSED_LADDER: Fe9 ladder with the negated fused formulas jac_dbl_neg / jac_madd_neg.
+// was_even fix-up at the end.  K1_ODD: k1 odd and both halves below 2^128 (secp_glv_make_k1_odd): a 128-bit window register and
+// one was_even fix-up, for k2.  FUSED_LADDER: Fe9 ladder with the negated fused formulas jac_dbl_neg / jac_madd_neg.
 template <class C, class = void> struct OddGlvHalves { static constexpr bool value = false; };
 template <class C> struct OddGlvHalves<C, std::void_t<decltype(C::ODD_HALVES)>> { static constexpr bool value = C::GLV && C::ODD_HALVES; };
+template <class C, class = void> struct OddK1Half { static constexpr bool value = false; };
+template <class C> struct OddK1Half<C, std::void_t<decltype(C::K1_ODD)>> { static constexpr bool value = C::GLV && C::K1_ODD; };
 template <class C, class = void> struct FusedLadder { static constexpr bool value = false; };
 template <class C> struct FusedLadder<C, std::void_t<decltype(C::FUSED_LADDER)>> { static constexpr bool value = C::FUSED_LADDER; };
 
@@ -102,9 +105,9 @@ struct MulVarCfg {
   static constexpr int TW = FieldIO<F>::LANE_WORDS;  // words per field element in this lane's LDS table
   static constexpr int WW = FieldWire<F>::WORDS;  // wire words per field element (HBM in/out)
   static constexpr int TS = 1 << (W - 1);                 // table entries: 1,3,..,2^W-1
-  static constexpr int KBITS = C::GLV ? 129 : 257;        // bound on |k|+1 per stream
+  static constexpr int KBITS = OddK1Half<C>::value ? 128 : C::GLV ? 129 : 257;   // bound on |k|+1 per stream
   static constexpr int M = (KBITS + W - 1) / W;           // windows
-  static constexpr int NL = C::GLV ? 5 : 9;               // limbs of the window register
+  static constexpr int NL = (KBITS + 31) / 32;            // limbs of the window register
   static constexpr int LDS_WORDS = TS * 2 * TW * 64;      // per 64-lane block
 };
 
@@ -180,9 +183,11 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   SignedOddWindows<NL, W, M> w1, w2;
   bool neg1 = false, neg2 = false;
   constexpr bool ODD = OddGlvHalves<C>::value;
+  constexpr bool K1ODD = OddK1Half<C>::value;
   if constexpr (C::GLV) {
     GlvSplit gs = C::glv_split(k);
     if constexpr (ODD) secp_glv_make_odd(gs);
+    if constexpr (K1ODD) secp_glv_make_k1_odd(gs);
     w1.template init<5>(gs.k1);
     w2.template init<5>(gs.k2);
     neg1 = gs.k1neg;
@@ -253,11 +258,14 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
       }
     }
   }
-  // even scalars were bumped by one: take the extra point back out
+  // even scalars were bumped by one: take the extra point back out (K1ODD: k1 is odd, only k2 can have been bumped; P is
+  // entry 0 of the table and psi(P) = (beta x, y).  In the fused ladder `sg` then flips in the lanes that add: it is per lane.)
   if constexpr (!ODD) {
     const F qx = FieldIO<F>::load_strided(tab, stride);
     const F qy = FieldIO<F>::load_strided(tab + TW * stride, stride);
-    if (w1.was_even) R = madd(R, qx, qy, !neg1);
+    if constexpr (!K1ODD) {
+      if (w1.was_even) R = madd(R, qx, qy, !neg1);
+    }
     if constexpr (C::GLV) {
       if (w2.was_even) R = madd(R, qx * beta, qy, !neg2);
     }

@@ -181,6 +181,53 @@ NCG_DI void secp_glv_make_odd(GlvSplit& s) {
   }
 }
 
+// k1 odd and both halves below 2^128, for the secp256k1 ladder with 32 windows per half (CurveSecpI): k2 keeps its parity, and an
+// even k2 takes SignedOddWindows' +1 with one subtraction of psi(P) after the ladder.  An even k1 gets s v1 = s (a1, b1) added,
+// s = +-1 with the sign that shrinks |k2| (b1 < 0: s = +1 for k2 >= 0).  Babai's bound on secp_glv_split gives
+// |k1| < (|a1| + |a2|) / 2 < 0.64 2^128 and |k2| < (|b1| + |b2|) / 2 < 0.54 2^128 < |b1|, so afterwards |k1| < 0.64 2^128 + |a1|
+// < 0.83 2^128 and |k2| <= |b1| - |k2| <= |b1| < 0.9 2^128: |k1| and |k2| + 1 stay below 2^128.  (No lattice vector flips only
+// k2's parity with both coordinates that small, so k2 cannot be made odd this way.)  secp_glv_split's output is unchanged.
+NCG_DI void secp_glv_make_k1_odd(GlvSplit& s) {
+  uint32_t x1[6], x2[6], va[6], vb[6];
+  const bool e1 = (s.k1[0] & 1u) == 0;
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    x1[i] = i < 5 ? s.k1[i] : 0u;
+    x2[i] = i < 5 ? s.k2[i] : 0u;
+  }
+  if (s.k1neg) mp_neg<6>(x1);
+  if (s.k2neg) mp_neg<6>(x2);
+  uint32_t a1[6], a1n[6], mb1[6], mb1n[6];   // +-a1 and +-MB1 = -+b1 as 6-limb two's complement
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    a1[i] = a1n[i] = i < 5 ? SecpGlv::A1[i] : 0u;
+    mb1[i] = mb1n[i] = i < 5 ? SecpGlv::MB1[i] : 0u;
+  }
+  mp_neg<6>(a1n);
+  mp_neg<6>(mb1n);
+#pragma unroll
+  for (int i = 0; i < 6; i++) {   // s = +1 (k2 >= 0): (a1, -MB1);  s = -1: (-a1, MB1)
+    va[i] = e1 ? (s.k2neg ? a1n[i] : a1[i]) : 0u;
+    vb[i] = e1 ? (s.k2neg ? mb1[i] : mb1n[i]) : 0u;
+  }
+  mp_add<6>(x1, x1, va);
+  mp_add<6>(x2, x2, vb);
+  s.k1neg = (x1[5] >> 31) != 0;
+  s.k2neg = (x2[5] >> 31) != 0;
+  if (s.k1neg) mp_neg<6>(x1);
+  if (s.k2neg) mp_neg<6>(x2);
+#ifndef __HIP_DEVICE_COMPILE__
+  assert(x1[0] & 1u);
+  assert(x1[5] == 0 && x1[4] == 0 && x2[5] == 0 && x2[4] == 0);                                   // |k1|, |k2| < 2^128
+  assert(!(x2[0] == ~0u && x2[1] == ~0u && x2[2] == ~0u && x2[3] == ~0u));                         // |k2| + 1 < 2^128
+#endif
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    s.k1[i] = x1[i];
+    s.k2[i] = x2[i];
+  }
+}
+
 // Signed-odd fixed-window recoding (Joye-Tunstall style, closed form).
 // For an odd integer k < 2^L (L = M*W) write k = sum_{i<M} d_i 2^(W i) with every d_i odd,
 // |d_i| <= 2^W - 1:  d_i = 2*((k~ >> (W i + 1)) & (2^W - 1)) - (2^W - 1),  k~ = k | 2^L.

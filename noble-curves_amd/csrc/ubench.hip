@@ -328,19 +328,21 @@ __global__ void __launch_bounds__(64) k_field_check_fused(int op, int variant, c
 // The pieces of the secp256k1 fused ladder (CurveSecpI) on RAW limbs, as hosttest.hip's ht_jac_neg / ht_glv_split_odd:
 // op 0 jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) with P = a (27 limbs, bound 2), qx = b[0..9) (bound 2), qy = b[9..18)
 // (bound 3, a negated table entry); out = X, Y, Z.  op 2: secp_glv_split + secp_glv_make_odd of the scalar a[0..8);
-// out[0..12) = k1[5] k2[5] k1neg k2neg.  One lane per item, so a wave mixes the generic path and the exceptional branch.
+// out[0..12) = k1[5] k2[5] k1neg k2neg.  op 3: secp_glv_split + secp_glv_make_k1_odd, the same layout.  One lane per item, so a
+// wave mixes the generic path and the exceptional branch.
 __global__ void __launch_bounds__(64) k_field_check_secp_ladder(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                                 uint32_t* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t *pa = a + (size_t)i * 27, *pb = b + (size_t)i * 18;
   uint32_t* r = out + (size_t)i * 27;
-  if (op == 2) {
+  if (op == 2 || op == 3) {
     uint32_t k[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) k[j] = pa[j];
     GlvSplit s = secp_glv_split(k);
-    secp_glv_make_odd(s);
+    if (op == 2) secp_glv_make_odd(s);
+    else secp_glv_make_k1_odd(s);
 #pragma unroll
     for (int j = 0; j < 5; j++) {
       r[j] = s.k1[j];
