@@ -12,7 +12,7 @@
 const native = require('./noble_gpu.node');
 const crypto = require('crypto');
 
-const CURVE = { SECP256K1: 0, ED25519: 1, BLS12_381_G1: 2, BLS12_381_G2: 3 };
+const CURVE = { SECP256K1: 0, ED25519: 1, BLS12_381_G1: 2, BLS12_381_G2: 3, BN254_G1: 5 };
 const registry = new Map();
 let inited = false;
 function init(device) { if (!inited) { native.init(device || 0); inited = true; } }

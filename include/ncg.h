@@ -7,7 +7,7 @@
  *
  * Wire format:
  *   - field elements: canonical residues (NOT Montgomery), little-endian bytes, fixed width:
- *       secp256k1 / ed25519 Fp: 32 bytes;  bls12-381 Fp: 48 bytes;  Fp2 = c0 || c1 (96 bytes)
+ *       secp256k1 / ed25519 / bn254 Fp: 32 bytes;  bls12-381 Fp: 48 bytes;  Fp2 = c0 || c1 (96 bytes)
  *   - affine points: x || y.  Infinity is (0,0) on Weierstrass curves
  *       (reference src/abstract/weierstrass.ts:716 fromAffine, :966 toAffine) and (0,1) on
  *       Edwards (src/abstract/edwards.ts:606); outputs also carry a separate is_inf byte.
@@ -47,7 +47,8 @@ enum ncg_curve {
   NCG_SECP256K1 = 0,     /* src/secp256k1.ts:48-64   */
   NCG_ED25519 = 1,       /* src/ed25519.ts:49-65     */
   NCG_BLS12_381_G1 = 2,  /* src/bls12-381.ts:134-148 */
-  NCG_BLS12_381_G2 = 3   /* src/bls12-381.ts:321-345 */
+  NCG_BLS12_381_G2 = 3,  /* src/bls12-381.ts:321-345 */
+  NCG_BN254_G1 = 5       /* src/bn254.ts G1 (alt_bn128, EIP-196); id 4 is unassigned */
 };
 
 enum ncg_status {
@@ -466,7 +467,16 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg.
  * field 8 = fr29.hpp, the bls12-381 Fr form of the NTT butterflies, RAW limbs in and out: a, b, out = 9 words each.
  * ops 0 mont(a, b), 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)),
- * 7 to_words(a) (8 words, then 0). */
+ * 7 to_words(a) (8 words, then 0).
+ * field 9 = the bn254 base field (fe9m.hpp: radix 2^29, Montgomery R = 2^261), RAW limbs in and out: a, b, out = 9 words
+ * each, `variant` = 10 A + B names the operand bound types (11 12 22 23 32 17 71 33 77; a bound-B element has limbs below
+ * B 2^29 and a value below 2 B p).  ops 0 a*b, 1 a^2, 2 a + b, 3 a - b, 4 -a, 5 1/a, 6 weak normalisation, 7 to wire
+ * (8 canonical LE words of a / R, then 0), 8 from wire (a[0..8) canonical LE words -> a R).  An op the bounds do not admit
+ * leaves out zero.
+ * bn254 G1 (NCG_BN254_G1) takes the MSM (every entry point, resident / precomputed / async / split / sharded), the batch
+ * variable-base multiply, the pairwise add and normalize_batch; the reference has no byte format for it, so decode /
+ * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch
+ * and points_verify_subgroup. */
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
 #ifdef __cplusplus

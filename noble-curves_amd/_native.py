@@ -12,9 +12,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
-SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2 = 0, 1, 2, 3
-POINT_BYTES = {SECP256K1: 64, ED25519: 64, BLS12_381_G1: 96, BLS12_381_G2: 192}
-FIELD_BYTES = {SECP256K1: 32, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 48}
+SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1 = 0, 1, 2, 3, 5
+POINT_BYTES = {SECP256K1: 64, ED25519: 64, BLS12_381_G1: 96, BLS12_381_G2: 192, BN254_G1: 64}
+FIELD_BYTES = {SECP256K1: 32, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 48, BN254_G1: 32}
 FIELD_BLS12_381_FR = 0
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
@@ -714,14 +714,15 @@ class Engine:
         """Device field code on raw operands (ncg_field_check): a_words, b_words uint32 [n, 9] (fields 0/1),
         [n, 12] (field 2), [n, 28] (field 3: raw Fe29 limbs [a, c]), [n, 56] (field 4: lane-paired Fp2 raw limbs),
         [n, 18] (fields 5/6: fused Fe9 expressions, raw limbs [a, c] and [b, d]), a [n, 27] and b [n, 18] (field 7:
-        secp256k1 ladder pieces) or [n, 9] (field 8: fr29 raw limbs) -> uint32 [n, 8 | 8 | 12 | 12 | 24 | 9 | 9 | 27 | 9]."""
+        secp256k1 ladder pieces) or [n, 9] (field 8: fr29 raw limbs; field 9: bn254 Montgomery raw limbs) -> uint32
+        [n, 8 | 8 | 12 | 12 | 24 | 9 | 9 | 27 | 9 | 9]."""
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)
         n = a.shape[0]
         wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18)}.get(field, (9, 9))
         if a.shape != (n, wa) or b.shape != (n, wb):   # the library reads n * wa and n * wb words
             raise ValueError("field_check: field %d takes a [n, %d] and b [n, %d]" % (field, wa, wb))
-        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9}.get(field, 8)), dtype=np.uint32)
+        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9}.get(field, 8)), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_field_check(self.h, field, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out

@@ -181,6 +181,7 @@ int ncg_point_bytes(int curve) {
     case NCG_ED25519: return 64;
     case NCG_BLS12_381_G1: return 96;
     case NCG_BLS12_381_G2: return 192;
+    case NCG_BN254_G1: return 64;
     default: return 0;
   }
 }
@@ -293,7 +294,7 @@ static int ensure_mul_ws(ncg_ctx* ctx, int curve, size_t n, hipStream_t st) {
 int ncg_mul_var_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* points_affine_dev, const void* scalars_dev,
                           void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2)
+  if ((curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2) && curve != NCG_BN254_G1)
     return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_var_batch: unsupported curve %d", curve);
   if (n == 0) return NCG_OK;
   if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
@@ -442,7 +443,7 @@ int ncg_mul_var_batch(ncg_ctx* ctx, int curve, size_t n, const void* points_affi
 int ncg_add_pairs_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* a_dev, const void* b_dev, int subtract,
                             void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2)
+  if ((curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2) && curve != NCG_BN254_G1)
     return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: add_pairs_batch: unsupported curve %d", curve);
   if (n == 0) return NCG_OK;
   if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
@@ -534,7 +535,8 @@ int ncg_mul_base_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* scalar
 int ncg_mul_base_batch(ncg_ctx* ctx, int curve, size_t n, const void* scalars, void* out_affine, uint8_t* out_is_inf) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
   int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_base_batch: unsupported curve %d", curve);
+  if (pb == 0 || curve == NCG_BN254_G1)  // no fixed-base table for bn254 G1
+    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_base_batch: unsupported curve %d", curve);
   if (n == 0) return NCG_OK;
   if (!scalars || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_base_batch: NULL buffer");
   NCG_HIP(ctx, hipSetDevice(ctx->device));
@@ -1860,13 +1862,14 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
 
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out) {
   if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (field < 0 || field > 8) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 9) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   if (n == 0) return NCG_OK;
   if (n > (1u << 24) || !a || !b || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: bad arguments");
   // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
-  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9
-  static const size_t wa[9] = {9, 9, 12, 28, 56, 18, 18, 27, 9}, wb[9] = {9, 9, 12, 28, 56, 18, 18, 18, 9},
-                      wo[9] = {8, 8, 12, 12, 24, 9, 9, 27, 9};
+  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
+  // bn254 Fe9 Montgomery raw limbs 9 / 9 / 9
+  static const size_t wa[10] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9}, wb[10] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9},
+                      wo[10] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9};
   const size_t in_wa = wa[field], in_wb = wb[field], out_w = wo[field];
   NCG_HIP(ctx, hipSetDevice(ctx->device));
   const size_t in_ba = (n * in_wa * 4 + 255) & ~(size_t)255, in_bb = (n * in_wb * 4 + 255) & ~(size_t)255, out_b = n * out_w * 4;

@@ -6,7 +6,7 @@
 
 namespace ncg {
 
-enum CurveId : int { CURVE_SECP256K1 = 0, CURVE_ED25519 = 1, CURVE_BLS12_381_G1 = 2, CURVE_BLS12_381_G2 = 3 };
+enum CurveId : int { CURVE_SECP256K1 = 0, CURVE_ED25519 = 1, CURVE_BLS12_381_G1 = 2, CURVE_BLS12_381_G2 = 3, CURVE_BN254_G1 = 5 };
 
 struct CurveSecp {  // src/secp256k1.ts:48-64
   using F = FeSecp;  // radix-2^29 lazy form (fe9.hpp)
@@ -59,6 +59,12 @@ struct CurveG1E : CurveG1 {
     s.k2neg = !k2neg;  // the stream multiplies (beta x, y) = -(z^2 P)
     return s;
   }
+};
+struct CurveBn254 {  // src/bn254.ts G1: y^2 = x^3 + 3, h = 1
+  using F = FeBn254;  // radix-2^29 Montgomery form (fe9m.hpp)
+  static constexpr bool GLV = false;  // the reference has no endomorphism on bn254 G1
+  static constexpr int SCALAR_BITS = 254;
+  static NCG_DI F beta() { return F::one(); }
 };
 struct CurveG2 {  // src/bls12-381.ts:321-345
   using F = FeBls2;

@@ -23,10 +23,15 @@
 
 #include "fp.hpp"
 #include "fe9_asm_gen.hpp"
+#include "fe9m.hpp"
 
 namespace ncg {
 
 constexpr uint32_t FE9_MASK = (1u << 29) - 1u;
+
+// PR::MONT: the Montgomery kind (fe9m.hpp, bn254) - the same type and bound rules, Montgomery products, other constants
+template <class PR, class = void> struct Fe9IsMont : std::false_type {};
+template <class PR> struct Fe9IsMont<PR, std::void_t<decltype(PR::MONT)>> : std::integral_constant<bool, PR::MONT> {};
 
 template <class PR>
 struct Fe9Raw {
@@ -238,7 +243,8 @@ NCG_MULFN Fe9Raw<PR> fe9_mul_raw_s(T... limbs) {
     b[i] = v[9 + i];
   }
   Fe9Raw<PR> r;
-  fe9_mul_limbs<PR>(r.v, a, b);
+  if constexpr (Fe9IsMont<PR>::value) fe9m_mont_limbs<false>(r.v, a, b);
+  else fe9_mul_limbs<PR>(r.v, a, b);
   return r;
 }
 template <class PR, class... T>
@@ -246,7 +252,14 @@ NCG_MULFN Fe9Raw<PR> fe9_sqr_raw_s(T... limbs) {
   static_assert(sizeof...(T) == 9, "one operand of 9 limbs");
   const uint32_t a[9] = {limbs...};
   Fe9Raw<PR> r;
-  fe9_sqr_limbs<PR>(r.v, a);
+  if constexpr (Fe9IsMont<PR>::value) {
+    uint32_t a2[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) a2[i] = a[i] << 1;
+    fe9m_mont_limbs<true>(r.v, a, a2);
+  } else {
+    fe9_sqr_limbs<PR>(r.v, a);
+  }
   return r;
 }
 template <class PR>
@@ -273,6 +286,8 @@ struct Fe9 {
     if constexpr (B2 < B) {
 #pragma unroll
       for (int i = 0; i < 9; i++) v[i] = o.v[i];
+    } else if constexpr (Fe9IsMont<PR>::value) {
+      fe9m_reduce(v, o.v);
     } else {
       const uint32_t h = o.v[8] >> 29;  // below 8
       v[0] = (o.v[0] & FE9_MASK) + h * PR::C0;
@@ -289,7 +304,12 @@ struct Fe9 {
   }
   static NCG_DI Fe9 one() {
     Fe9 r = zero();
-    r.v[0] = 1;
+    if constexpr (Fe9IsMont<PR>::value) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) r.v[i] = PR::ONE[i];  // R mod p
+    } else {
+      r.v[0] = 1;
+    }
     return r;
   }
   template <class ARR>
@@ -467,7 +487,20 @@ NCG_DI Fe9<PR, 1> fe9_sqr_n(Fe9<PR, 1> a, int n) {
 // canonical residue in [0, p) as 9 x 29-bit limbs: sequential carries, two folds of the bits at and
 // above the width of p, then conditional subtractions.  Boundary / rare-path code.
 template <class PR, int A>
+NCG_DI void fe9_canon_limbs_sf(uint32_t (&o)[9], const Fe9<PR, A>& a);
+template <class PR, int A>
 NCG_DI void fe9_canon_limbs(uint32_t (&o)[9], const Fe9<PR, A>& a) {
+  if constexpr (Fe9IsMont<PR>::value) {  // canonical Montgomery residue: below 2p, then one conditional subtraction
+    uint32_t t[9];
+    fe9m_reduce(t, a.v);
+    fe9m_cond_sub(o, t);
+  } else {
+    fe9_canon_limbs_sf<PR, A>(o, a);
+  }
+}
+// the special-form primes (secp256k1, ed25519)
+template <class PR, int A>
+NCG_DI void fe9_canon_limbs_sf(uint32_t (&o)[9], const Fe9<PR, A>& a) {
   // value below 7*U*2^232*(1+2^-29) < 2^264.  Write v = lo + hi * 2^261 and fold: twice.
   uint64_t cy = 0;
   uint32_t t[9];
@@ -559,6 +592,11 @@ NCG_DI bool f_eq(const Fe9<PR, A>& a, const Fe9<PR, B>& b) {
 // ---- wire format (8 x 32-bit LE limbs, canonical residue) <-> Fe9
 template <class PR>
 NCG_DI Fe9<PR, 1> fe9_from_wire(const uint32_t* __restrict__ p) {
+  if constexpr (Fe9IsMont<PR>::value) {
+    Fe9<PR, 1> r;
+    fe9m_from_wire(r.v, p);
+    return r;
+  }
   uint32_t w[10];
 #pragma unroll
   for (int i = 0; i < 8; i++) w[i] = p[i];
@@ -575,6 +613,12 @@ NCG_DI Fe9<PR, 1> fe9_from_wire(const uint32_t* __restrict__ p) {
 }
 template <class PR, int A>
 NCG_DI void fe9_to_wire(uint32_t* __restrict__ p, const Fe9<PR, A>& a) {
+  if constexpr (Fe9IsMont<PR>::value) {
+    uint32_t c[9];
+    fe9m_canon_plain(c, fe9_norm(a).v);
+    fe9m_words_from_limbs(p, c);
+    return;
+  }
   uint32_t l[11];
   uint32_t c[9];
   fe9_canon_limbs<PR, A>(c, a);
@@ -599,7 +643,21 @@ template <class PR, int A>
 NCG_DI Fe9<PR, 1> f_inv(const Fe9<PR, A>& a_in) {
   using F = Fe9<PR, 1>;
   const F x = fe9_norm(a_in);
-  if constexpr (PR::C1 != 0) {  // secp256k1
+  if constexpr (Fe9IsMont<PR>::value) {  // bn254: x^(p - 2) by 4-bit windows, 252 squarings + 63 + 14 multiplications
+    F tab[16];
+    tab[0] = F::one();
+    tab[1] = x;
+#pragma unroll
+    for (int i = 2; i < 16; i++) tab[i] = tab[i - 1] * x;
+    F t = tab[PR::PM2_NIB[63]];
+#pragma unroll
+    for (int i = 62; i >= 0; i--) {  // unrolled: the table index is a constant, the table stays in registers
+      t = fe9_sqr_n(t, 4);
+      const int d = PR::PM2_NIB[i];
+      if (d) t = t * tab[d];
+    }
+    return t;
+  } else if constexpr (PR::C1 != 0) {  // secp256k1
     F x2 = f_sqr(x) * x;
     F x3 = f_sqr(x2) * x;
     F x6 = fe9_sqr_n(x3, 3) * x3;
@@ -635,5 +693,6 @@ NCG_DI Fe9<PR, 1> f_inv(const Fe9<PR, A>& a_in) {
 // storage types used by the curve templates: coordinates are kept with limbs below 2*U
 using FeSecp = Fe9<Fe9SecpPR, 2>;
 using FeEd = Fe9<Fe9EdPR, 2>;
+using FeBn254 = Fe9<Bn254PR, 2>;
 
 }  // namespace ncg

@@ -13,6 +13,7 @@
 #include "endo.hpp"
 #include "ecdsa.hip"
 #include "msm_shard.hpp"
+#include "fe9m_check.hpp"
 
 using namespace ncg;
 
@@ -204,6 +205,7 @@ static int ht_shard_combine_t(int curve, int n_max, int nparts, const uint8_t* s
     case CURVE_ED25519: return CALL(CurveEd);         \
     case CURVE_BLS12_381_G1: return CALL(CurveG1);    \
     case CURVE_BLS12_381_G2: return CALL(CurveG2);    \
+    case CURVE_BN254_G1: return CALL(CurveBn254);     \
     default: return -1;                               \
   }
 
@@ -275,6 +277,7 @@ int ht_mul_var(int curve, const uint32_t* pts, const uint32_t* scalars, uint32_t
     case 12: ht_mul_var_t<CurveG1E, 4>(pts, scalars, out, out_inf, n); return 0;  // subgroup points only (GLV ladder)
     case 14: ht_mul_var_t<CurveSecpI, 4>(pts, scalars, out, out_inf, n); return 0;  // the fused-formula ladder of the inlined kernel
     case CURVE_BLS12_381_G2: ht_mul_var_t<CurveG2, 3>(pts, scalars, out, out_inf, n); return 0;
+    case CURVE_BN254_G1: ht_mul_var_t<CurveBn254, 4>(pts, scalars, out, out_inf, n); return 0;
   }
   return -1;
 }
@@ -439,6 +442,13 @@ int ht_fr29_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
   }
   for (int i = 0; i < 9; i++) r[i] = z.v[i];
   return fr29_overflows();
+}
+// fe9m.hpp (bn254 base field, Montgomery radix 2^29) on RAW limbs: fe9m_check (fe9m_check.hpp), the same code as
+// ncg_field_check field 9.  Returns the overflow count of the call, or -1 for an unknown op / variant.
+int ht_fe9m_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  fe9m_overflows() = 0;
+  if (fe9m_check(op, variant, a, b, r) != 0) return -1;
+  return fe9m_overflows();
 }
 // the pass schedule of ntt_run (the shipped ntt_schedule with the device's pass limits and table): 11 ints per pass,
 // T logC colhi dit inverse brp_store scale canon s_lo in out (buffers 0 src, 1 dst, 2 ws); returns the number of passes

@@ -1907,6 +1907,7 @@ hipError_t msm_points_to_stored_t<CurveG1>(const uint32_t* d_pts_wire, int n, ui
     case CURVE_BLS12_381_G1: return CALL(CurveG1);          \
     case CURVE_BLS12_381_G2: return CALL(CurveG2);          \
     case CURVE_ED25519: return CALL(CurveEd);               \
+    case CURVE_BN254_G1: return CALL(CurveBn254);           \
     default: return hipErrorInvalidValue;                   \
   }
 
@@ -1946,6 +1947,7 @@ void msm_finish_host(int curve, int c, int nwin, const uint32_t* fin_host, uint3
     case CURVE_BLS12_381_G1: return msm_host_finish_any<CurveG1>(fin_host, c, nwin, out_affine_host, out_inf_host);
     case CURVE_BLS12_381_G2: return msm_host_finish_any<CurveG2>(fin_host, c, nwin, out_affine_host, out_inf_host);
     case CURVE_ED25519: return msm_host_finish_any<CurveEd>(fin_host, c, nwin, out_affine_host, out_inf_host);
+    case CURVE_BN254_G1: return msm_host_finish_any<CurveBn254>(fin_host, c, nwin, out_affine_host, out_inf_host);
     default: return;
   }
 }
@@ -1955,6 +1957,7 @@ size_t msm_fin_words(int curve, const MsmPlan& pl) {
     case CURVE_BLS12_381_G1: return msm_fin_words_t<CurveG1>(pl);
     case CURVE_BLS12_381_G2: return msm_fin_words_t<CurveG2>(pl);
     case CURVE_ED25519: return msm_fin_words_t<CurveEd>(pl);
+    case CURVE_BN254_G1: return msm_fin_words_t<CurveBn254>(pl);
     default: return 0;
   }
 }
@@ -1964,6 +1967,7 @@ size_t msm_acc_words(int curve) {
     case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::ACC_WORDS;
     case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::ACC_WORDS;
     case CURVE_ED25519: return MsmGroup<CurveEd>::ACC_WORDS;
+    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::ACC_WORDS;
     default: return 0;
   }
 }
@@ -1974,6 +1978,7 @@ size_t msm_workspace_bytes(int curve, const MsmPlan& pl) {
     case CURVE_BLS12_381_G1: return msm_layout<CurveG1>(pl).total;
     case CURVE_BLS12_381_G2: return msm_layout<CurveG2>(pl).total;
     case CURVE_ED25519: return msm_layout<CurveEd>(pl).total;
+    case CURVE_BN254_G1: return msm_layout<CurveBn254>(pl).total;
     default: return 0;
   }
 }
@@ -1984,6 +1989,7 @@ size_t msm_stored_words_per_point(int curve) {
     case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::AFF_WORDS;
     case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::AFF_WORDS;
     case CURVE_ED25519: return MsmGroup<CurveEd>::AFF_WORDS;
+    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::AFF_WORDS;
     default: return 0;
   }
 }
@@ -2004,6 +2010,7 @@ hipError_t msm_run(int curve, const MsmPlan& pl, const uint32_t* d_pts, const ui
     case CURVE_BLS12_381_G1: return msm_run_t<CurveG1>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
     case CURVE_BLS12_381_G2: return msm_run_t<CurveG2>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
     case CURVE_ED25519: return msm_run_t<CurveEd>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
+    case CURVE_BN254_G1: return msm_run_t<CurveBn254>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
     default: return hipErrorInvalidValue;
   }
 }

@@ -45,10 +45,14 @@ inline int plan_windows(int c, const uint32_t* order8, uint32_t* hconst10) {
   return -1;
 }
 
+// bn254 G1 group order r (src/bn254.ts Fr), little-endian words
+constexpr uint32_t BN254_R[8] = {0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};
+
 inline const uint32_t* curve_order(int curve) {
   switch (curve) {
     case CURVE_SECP256K1: return Orders::SECP_N;
     case CURVE_ED25519: return Orders::ED_L;
+    case CURVE_BN254_G1: return BN254_R;
     default: return Orders::BLS_R;
   }
 }
@@ -133,7 +137,8 @@ inline int msm_make_plan_impl(int curve, int n, int c_override, MsmPlan* pl) {
   pl->n = n;
   pl->ls = curve == CURVE_BLS12_381_G2 ? 1 : 0;  // lane-paired kernels: 2 lanes per item
   // waves/SIMD the accumulate kernel runs at (registers): 4 for the 256-bit fields, 2 for bls12-381 G1, 1 for G2
-  pl->accum_waves = (curve == CURVE_SECP256K1 || curve == CURVE_ED25519) ? 4 : curve == CURVE_BLS12_381_G2 ? G2_ACCUM_WAVES : 2;
+  pl->accum_waves = (curve == CURVE_SECP256K1 || curve == CURVE_ED25519 || curve == CURVE_BN254_G1) ? 4
+                    : curve == CURVE_BLS12_381_G2 ? G2_ACCUM_WAVES : 2;
   pl->c = c;
   pl->nb = 1 << (c - 1);
   pl->nwin = plan_windows(c, curve_order(curve), pl->hconst);
@@ -216,6 +221,7 @@ inline size_t msm_acc_words_inl(int curve) {
     case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::ACC_WORDS;
     case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::ACC_WORDS;
     case CURVE_ED25519: return MsmGroup<CurveEd>::ACC_WORDS;
+    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::ACC_WORDS;
     default: return 0;
   }
 }

@@ -68,6 +68,7 @@ hipError_t msm_shift_levels(int curve, uint32_t* d_levels, int m, int nlev, int 
       case CURVE_SECP256K1: e = shift_level_t<CurveSecp, 16>(curve, prev, m, c, d_jac, d_wire, d_inf, out, st); break;
       case CURVE_BLS12_381_G1: e = shift_level_t<CurveG1, 8>(curve, prev, m, c, d_jac, d_wire, d_inf, out, st); break;
       case CURVE_BLS12_381_G2: e = shift_level_t<CurveG2P, 4>(curve, prev, m, c, d_jac, d_wire, d_inf, out, st); break;
+      case CURVE_BN254_G1: e = shift_level_t<CurveBn254, 16>(curve, prev, m, c, d_jac, d_wire, d_inf, out, st); break;
       default: return hipErrorInvalidValue;
     }
     if (e != hipSuccess) return e;

@@ -88,6 +88,7 @@ hipError_t pair_add_batch(int curve, const uint32_t* a, const uint32_t* b, int s
     case CURVE_SECP256K1: return pair_add_t<CurveSecp, 8>(a, b, subtract, out, out_inf, n, jac_tmp, st);
     case CURVE_BLS12_381_G1: return pair_add_t<CurveG1, 8>(a, b, subtract, out, out_inf, n, jac_tmp, st);
     case CURVE_BLS12_381_G2: return pair_add_t<CurveG2P, 4>(a, b, subtract, out, out_inf, n, jac_tmp, st);
+    case CURVE_BN254_G1: return pair_add_t<CurveBn254, 8>(a, b, subtract, out, out_inf, n, jac_tmp, st);
     case CURVE_ED25519:
       hipLaunchKernelGGL(k_pair_add_ed, dim3((n + 255) / 256), dim3(256), 0, st, a, b, subtract, jac_tmp, n);
       return ed25519_proj_to_affine(jac_tmp, out, out_inf, n, st);
@@ -111,6 +112,10 @@ hipError_t normalize_batch(int curve, const uint32_t* proj_wire, uint32_t* out_w
       hipLaunchKernelGGL((k_proj_batch_affine<FeBls, 8>), dim3(((n + 7) / 8 + 255) / 256), dim3(256), 0, st, proj_wire,
                          out_wire, out_inf, n);
       break;
+    case CURVE_BN254_G1:
+      hipLaunchKernelGGL((k_proj_batch_affine<FeBn254, 8>), dim3(((n + 7) / 8 + 255) / 256), dim3(256), 0, st, proj_wire,
+                         out_wire, out_inf, n);
+      break;
     case CURVE_BLS12_381_G2:
       hipLaunchKernelGGL((k_proj_batch_affine<FeBls2, 4>), dim3(((n + 3) / 4 + 255) / 256), dim3(256), 0, st, proj_wire,
                          out_wire, out_inf, n);
@@ -125,6 +130,7 @@ size_t mul_var_tmp_bytes(int curve, int n) {
     // Jacobian scratch + a per-item window table (k_mul_var_gtab), sized for 5-bit windows (the kernels use 4)
     case CURVE_SECP256K1: return pad64(n) * (3 * FieldIO<CurveSecp::F>::WORDS + gtab_words_per_item<CurveSecp, 5>()) * 4;
     case CURVE_BLS12_381_G1: return pad64(n) * (3 * FieldIO<CurveG1::F>::WORDS + gtab_words_per_item<CurveG1, 5>()) * 4;
+    case CURVE_BN254_G1: return pad64(n) * (3 * FieldIO<CurveBn254::F>::WORDS + gtab_words_per_item<CurveBn254, 5>()) * 4;
     case CURVE_BLS12_381_G2:  // the verified-set ladder (mulvar_endo.hip) keeps a second table per lane
       return std::max(pad64(n) * (3 * FieldIO<CurveG2::F>::WORDS + 2 * gtab_words_per_item<CurveG2P, 4>()) * 4,
                       mul_var_g2_subgroup_tmp_bytes(n));
@@ -146,6 +152,9 @@ hipError_t mul_var_batch(int curve, const uint32_t* pts, const uint32_t* scalars
     case CURVE_BLS12_381_G1:
       if (jac_tmp) return launch_mul_var_gtab<CurveG1, 4, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
       return launch_mul_var<CurveG1, 3, 1, 8>(pts, scalars, out, out_inf, n, jac_tmp, st);
+    case CURVE_BN254_G1:  // W = 4, no GLV; the table in the multiply scratch (always given by the API)
+      if (jac_tmp) return launch_mul_var_gtab<CurveBn254, 4, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
+      return launch_mul_var<CurveBn254, 3, 2>(pts, scalars, out, out_inf, n, jac_tmp, st);
     case CURVE_BLS12_381_G2:
       if (jac_tmp) return launch_mul_var_gtab<CurveG2P, 4, 2, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);
       return launch_mul_var<CurveG2P, 2, 2, 4>(pts, scalars, out, out_inf, n, jac_tmp, st);

@@ -4,6 +4,7 @@
 #include "curves.hpp"
 #include "fp29.hpp"
 #include "fr29.hpp"
+#include "fe9m_check.hpp"
 
 namespace ncg {
 
@@ -375,6 +376,20 @@ __global__ void __launch_bounds__(64) k_field_check_secp_ladder(int op, const ui
 // fr29.hpp (the NTT butterflies' form of bls12-381 Fr) on RAW limbs, ops numbered as hosttest.hip's ht_fr29_op: 0 mont(a, b),
 // 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)), 7 to_words(a) (8 words, then 0).
 // a, b, out: 9 words per item, so that the tests check the output limbs as well as the value.
+// fe9m.hpp (the bn254 base field, Montgomery radix 2^29) on RAW limbs: fe9m_check (fe9m_check.hpp, the host twin's code);
+// a, b, out: 9 words per item.
+__global__ void __launch_bounds__(64) k_field_check_fe9m(int op, int variant, const uint32_t* __restrict__ a,
+                                                         const uint32_t* __restrict__ b, uint32_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x[9], y[9], r[9];
+  for (int j = 0; j < 9; j++) {
+    x[j] = a[(size_t)i * 9 + j];
+    y[j] = b[(size_t)i * 9 + j];
+  }
+  fe9m_check(op, variant, x, y, r);
+  for (int j = 0; j < 9; j++) out[(size_t)i * 9 + j] = r[j];
+}
 __global__ void __launch_bounds__(64) k_field_check_fr29(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                          uint32_t* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -427,6 +442,7 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 6) hipLaunchKernelGGL(k_field_check_fused<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 7) hipLaunchKernelGGL(k_field_check_secp_ladder, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else if (field == 8) hipLaunchKernelGGL(k_field_check_fr29, grid, block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 9) hipLaunchKernelGGL(k_field_check_fe9m, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _native
 from .field import Field
-from ._native import BLS12_381_G1, BLS12_381_G2, ED25519, FIELD_BYTES, POINT_BYTES, SECP256K1, get_engine
+from ._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, FIELD_BYTES, POINT_BYTES, SECP256K1, get_engine
 
 _BLS_P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
 _BLS_R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
@@ -597,6 +597,11 @@ bls12_381_G2_Point = _make_point_class(
      0x13E02B6052719F607DACD3A088274F65596BD0D09920B61AB5DA61BBDC7F5049334CF11213945D57E5AC7D055D042B7E),
     (0x0CE5D527727D6E118CC9CDC6DA2E351AADFD9BAA8CBDD3A76D429A695160D12C923AC9CC3BACA289E193548608B82801,
      0x0606C4A02EA734CC32ACD2B02BC28B99CB3E287E85A763AF267492AB572E99AB3F370D275CEC1DA1AAA9075FF05F79BE))  # bls12-381.ts:321-345
+bn254_G1_Point = _make_point_class(
+    "bn254_G1", BN254_G1,
+    _Field(0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47),
+    _Field(0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001),
+    1, 2)                                                                             # bn254.ts G1: y^2 = x^3 + 3
 ed25519_Point = _make_edwards_point_class(
     "ed25519", ED25519, _Field((1 << 255) - 19, isLE=True),         # curve.ts:1036: Edwards fields are little-endian
     _Field(0x1000000000000000000000000000000014DEF9DEA2F79CD65812631A5CF5D3ED, isLE=True),

@@ -15,7 +15,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from noble_curves_amd import get_engine  # noqa: E402
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, SECP256K1  # noqa: E402
+from bn254_helpers import BN254_R, Bn254  # noqa: E402
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, SECP256K1  # noqa: E402
 from oracle.curves import BLS_R, BlsG1, BlsG2, ED25519_L, Ed25519, SECP256K1_N, Secp256k1, makeRng  # noqa: E402
 
 
@@ -220,6 +221,29 @@ def main():
     torch.cuda.synchronize()
     assert bool((g2o == g2).all().item()) and int(ok[:m].sum().item()) == m, "G2 decode mismatch"
     rate("bls12-381 G2 decode + subgroup check", m, timeit(fg2, 2), "points")
+    # ---- bn254 G1 against bls12-381 G1: the same pipelines, 10 timed steps each for the compared rows
+    bsc = bench.gen_scalars(n, 253, 8, dev)
+    rng = makeRng(17)
+    a, b = rng.rndBelow(BN254_R - 1) + 1, rng.rndBelow(BN254_R - 1) + 1
+    bpts, _ = bench.gen_points(eng, BN254_G1, Bn254, n, a, b, dev, s)
+    rate("bn254 G1 MSM 2^16", 1 << 16, timeit(lambda: eng.msm_dev(BN254_G1, 1 << 16, P(bpts), P(bsc), s), 10), "points")
+    rate("bn254 G1 MSM", n, timeit(lambda: eng.msm_dev(BN254_G1, n, P(bpts), P(bsc), s), 10), "points")
+    g1n, _ = bench.gen_points(eng, BLS12_381_G1, BlsG1, n, a, b, dev, s)
+    g1sc = bench.gen_scalars(n, 254, 9, dev)
+    rate("bls12-381 G1 MSM", n, timeit(lambda: eng.msm_dev(BLS12_381_G1, n, P(g1n), P(g1sc), s), 10), "points")
+    del g1n, g1sc
+    bo = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    rate("bn254 G1 variable-base multiply", m, timeit(lambda: eng.mul_var_batch_dev(BN254_G1, m, P(bpts), P(bsc), P(bo), P(inf), s), 10), "scalar-mults")
+    rate("bls12-381 G1 variable-base multiply (10 steps)", m,
+         timeit(lambda: eng.mul_var_batch_dev(BLS12_381_G1, m, P(g1), P(gsc), P(g1o), P(inf), s), 10), "scalar-mults")
+    bshift = torch.roll(bpts, 1, 0).contiguous()
+    bpadd = lambda: eng._check(eng.lib.ncg_add_pairs_batch_dev(eng.h, BN254_G1, n, P(bpts), P(bshift), 0, P(bo), P(inf), s))  # noqa: E731
+    rate("bn254 G1 pairwise point add", n, timeit(bpadd), "points")
+    bproj = torch.cat([bpts, torch.zeros((n, 32), dtype=torch.uint8, device=dev)], dim=1)
+    bproj[:, 64] = 1                                                       # Z = 1
+    fn = lambda: eng._check(eng.lib.ncg_normalize_batch_dev(eng.h, BN254_G1, n, P(bproj), P(bo), P(inf), s))  # noqa: E731
+    rate("bn254 G1 normalizeZ batch", n, timeit(fn), "points")
+    del bpts, bshift, bproj, bo, bsc
     # ---- hash-to-curve (device part): 2 field elements per point -> SWU, isogeny, add, clearCofactor
     hm = 1 << 18
     u1 = torch.randint(0, 256, (hm, 2 * 48), dtype=torch.uint8, device=dev)

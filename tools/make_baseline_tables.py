@@ -159,6 +159,19 @@ def main():
     for k, v in ex.items():
         o = ex1.get(k)
         out.append("| %s | 2^%d | %s | %.2f ms | %.3g %s/s |" % (k, v["n"].bit_length() - 1, ("%.2f ms" % o["ms"]) if o else "—", v["ms"], v["per_s"], v["unit"]))
+    ex7 = load("r07_bench_extra.json")
+    rows = ["bn254 G1 MSM 2^16", "bn254 G1 MSM", "bls12-381 G1 MSM", "bn254 G1 variable-base multiply",
+            "bls12-381 G1 variable-base multiply (10 steps)", "bn254 G1 pairwise point add", "bn254 G1 normalizeZ batch"]
+    out.append("\nbn254 G1 beside bls12-381 G1, one run on one box (`profiles/r07_bench_extra.json`; the compared rows timed over 10 steps).  The\n"
+               "bn254 2^20 MSM takes %.2f of the bls12-381 G1 one and the 2^18 batch multiply %.2f of G1's: the same pipelines, each bn254 product\n"
+               "about 0.44 of the multiply-adds (DESIGN §3).\n"
+               % (ex7["bn254 G1 MSM"]["ms"] / ex7["bls12-381 G1 MSM"]["ms"],
+                  ex7["bn254 G1 variable-base multiply"]["ms"] / ex7["bls12-381 G1 variable-base multiply (10 steps)"]["ms"]))
+    out.append("| entry point | N | r07 | throughput |")
+    out.append("|---|---|---|---|")
+    for k in rows:
+        v = ex7[k]
+        out.append("| %s | 2^%d | %.2f ms | %.3g %s/s |" % (k, v["n"].bit_length() - 1, v["ms"], v["per_s"], v["unit"]))
     out.append("\n### End to end from JavaScript (`addon/bench_js.js`, Node 12 on the GPU box, secp256k1, `profiles/r05_js_bench.jsonl`)\n")
     out.append("BigInt marshalling + N-API + H2D/D2H + kernels.  Every BigInt that crosses N-API costs ~100 ns (`napi_get_element` + "
                "`napi_get_value_bigint_words`), and a reference-shaped `pippenger(c, points, scalars)` call on `Point` objects spends its time in "
