@@ -6,12 +6,13 @@ import os
 
 import numpy as np
 
-from noble_curves_amd._native import (BLS12_381_G1, BLS12_381_G2, ED25519, FIELD_BYTES, POINT_BYTES, SECP256K1,
+from bn254_helpers import Bn254
+from noble_curves_amd._native import (BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, FIELD_BYTES, POINT_BYTES, SECP256K1,
                                       ints_to_le, le_to_ints)
 from oracle.curves import SECP256K1_N, SECP256K1_P, BlsG1, BlsG2, Ed25519, Secp256k1
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-ORACLE_CURVE = {SECP256K1: Secp256k1, BLS12_381_G1: BlsG1, BLS12_381_G2: BlsG2, ED25519: Ed25519}
+ORACLE_CURVE = {SECP256K1: Secp256k1, BLS12_381_G1: BlsG1, BLS12_381_G2: BlsG2, ED25519: Ed25519, BN254_G1: Bn254}
 # the largest transform test_gpu_ntt.py's sweep runs: every NTT pass shape (ntt.hip ntt_schedule) occurs at or below it,
 # which test_host_logic.py's test_ntt_sweep_reaches_every_pass_shape checks against the planner
 NTT_SWEEP_MAX_LOG2N = 24

@@ -188,6 +188,8 @@ def test_shard_range_covers_everything():
     ("BLS12_381_G2", (9, 4)),
     ("SECP256K1", (16, 0)),           # an empty shard contributes identities
     ("ED25519", (5, 12)),
+    ("BN254_G1", (33, 31)),           # bn254 G1 (curve 5): Montgomery window sums in the slots
+    ("BN254_G1", (0, 21)),
 ])
 def test_msm_sharded_two_ranks_gloo_native_combine_twin(curve_name, sizes):
     res = _run(curve_name, sizes)
@@ -208,6 +210,7 @@ def test_msm_sharded_rejects_disagreeing_plans():
     ("BLS12_381_G1", 40, 2),          # c = 2: 128 windows, 64 per rank
     ("SECP256K1", 24, 3),             # uneven ranges
     ("ED25519", 11, 2),
+    ("BN254_G1", 24, 3),              # c = 2: 127 windows -> 43, 42, 42
 ])
 def test_msm_window_sharded_ranks_gloo_native_assembly_twin(curve_name, n, world):
     """Strong-scaling mode: rank r computes windows [w0, w0 + cnt) of ALL points, the slots are concatenated by the
@@ -242,7 +245,7 @@ def test_window_ranges_of_the_bench_plans_over_eight_ranks():
     try:
         for curve, c, nparts, want in ((_native.BLS12_381_G1, 16, 8, [2] * 8), (_native.BLS12_381_G2, 13, 8, [3, 3, 3, 3, 2, 2, 2, 2]),
                                        (_native.BLS12_381_G1, 16, 24, [1] * 16 + [0] * 8), (_native.SECP256K1, 16, 8, None),
-                                       (_native.ED25519, 14, 8, None)):
+                                       (_native.ED25519, 14, 8, None), (_native.BN254_G1, 16, 8, [2] * 8)):
             os.environ["NCG_MSM_C"] = str(c)
             Pt = ORACLE_CURVE[curve]
             order = Pt.Fn.ORDER
@@ -286,6 +289,7 @@ def test_window_ranges_of_the_bench_plans_over_eight_ranks():
     ("BLS12_381_G1", 24, 16, False),      # the 2^20 plan: 16 windows, 2 per rank, concatenated
     ("BLS12_381_G2", 10, 13, False),      # the 2^18 plan: 20 windows, 3,3,3,3,2,2,2,2
     ("BLS12_381_G1", 12, 16, True),       # precomputed set: every rank's slot is ONE grouped-sum array, the 8 slots are added
+    ("BN254_G1", 24, 16, False),          # bn254's 2^20 plan: 16 windows, 2 per rank
 ])
 def test_msm_window_sharded_eight_ranks_gloo(curve_name, n, c_forced, shared):
     res = _run_windows(curve_name, n, 8, c_forced=c_forced, shared=shared)
@@ -299,6 +303,7 @@ def test_msm_window_sharded_eight_ranks_gloo(curve_name, n, c_forced, shared):
     ("BLS12_381_G2", (2, 3, 0, 1, 4, 1, 0, 2), 13),
     ("SECP256K1", (3, 3, 3, 3, 3, 3, 3, 2), 0),
     ("ED25519", (0, 0, 0, 9, 0, 0, 0, 0), 0),            # seven ranks contribute identities only
+    ("BN254_G1", (4, 0, 7, 1, 0, 6, 2, 5), 16),           # bn254's 2^20 plan over ragged shards
 ])
 def test_msm_point_sharded_eight_ranks_gloo(curve_name, sizes, c_forced):
     res = _run(curve_name, sizes, c_forced=c_forced)

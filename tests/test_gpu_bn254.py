@@ -289,3 +289,163 @@ def test_python_mirror():
         if cc is c:
             ref = errs
     assert errs == ref
+
+
+# ---- batch multiply, pairwise add and normalize at the block and wave edges ------------------------------------------
+# k_mul_var_gtab runs 64 lanes per block; the pairwise add and normalize_batch take K = 8 items per lane (one inversion per 8).
+EDGE_SCALARS = [BN254_R, BN254_R + 1, 2 * BN254_R - 1, 1 << 255, (1 << 256) - 1, 5 * BN254_R + 3, BN254_R - 1, 0, 1, 2,
+                1 << 254, (1 << 256) - BN254_R]
+
+
+class _Comb:
+    """k G for many k with the oracle's group law: 32 tables of j 2^(8 w) G (j < 256), 32 additions per multiple"""
+
+    def __init__(self):
+        self.tab = []
+        Q = Bn254.BASE
+        for _ in range(32):
+            row = [Bn254.ZERO]
+            for _ in range(255):
+                row.append(row[-1].add(Q))
+            self.tab.append(row)
+            Q = row[-1].add(Q)
+
+    def mul(self, k):
+        k %= BN254_R
+        acc = Bn254.ZERO
+        for w in range(32):
+            acc = acc.add(self.tab[w][(k >> (8 * w)) & 255])
+        return acc
+
+
+def _progression_points(a, b, n):
+    """(a + i b) G for i < n, by additions, normalised together"""
+    from oracle import curve as OC
+    P, step, out = Bn254.BASE.multiplyUnsafe(a), Bn254.BASE.multiplyUnsafe(b), []
+    for _ in range(n):
+        out.append(P)
+        P = P.add(step)
+    return OC.normalizeZ(Bn254, out)
+
+
+def _affine_all(pts):
+    from oracle import curve as OC
+    return [p.toAffine() for p in OC.normalizeZ(Bn254, pts)]
+
+
+def test_batch_multiply_empty_and_block_edges():
+    """n = 0 through the C ABI; n = 63, 64, 65 and 64 k +- 1 over several blocks, as slices of one pool at shifted offsets so
+    that every edge scalar (r, r + 1, 2r - 1, 2^255, 2^256 - 1, ... : the C ABI takes any k < 2^256, the value is (k mod r) P)
+    and ZERO point meets other lane positions; the first wave of the pool has only even scalars and the second every other one
+    (the ladder's was_even fix-up at every lane position)."""
+    eng = get_engine()
+    L = eng.lib
+    assert L.ncg_mul_var_batch(eng.h, BN254_G1, 0, None, None, None, None) == 0
+    assert L.ncg_add_pairs_batch(eng.h, BN254_G1, 0, None, None, 0, None, None) == 0
+    assert L.ncg_normalize_batch(eng.h, BN254_G1, 0, None, None, None) == 0
+    out, inf = eng.mul_var_batch(BN254_G1, np.zeros((0, 64), np.uint8), np.zeros((0, 32), np.uint8))
+    assert out.shape == (0, 64) and inf.shape == (0,)
+    rng = makeRng(0x254B)
+    npool = 700
+    a0, b0 = rng.rndBelow(BN254_R - 1) + 1, rng.rndBelow(BN254_R - 1) + 1
+    pts = _progression_points(a0, b0, npool)
+    ks = []
+    for i in range(npool):
+        k = rng.rndBelow(1 << 256)
+        if i < 64 or (i < 128 and i % 2 == 0) or i % 5 == 0:
+            k &= ~1
+        ks.append(k)
+    for j, k in enumerate(EDGE_SCALARS):
+        ks[3 + j] = k                                   # the first lanes of the pool
+        ks[60 + j] = k                                  # across the first block boundary
+        ks[npool - 1 - j] = k                           # the last lanes
+    for i in (7, 64, 129, 400):
+        pts[i] = Bn254.ZERO
+    comb = _Comb()
+    exp = _affine_all([Bn254.ZERO if p.is0() else comb.mul(k * (a0 + i * b0)) for i, (p, k) in enumerate(zip(pts, ks))])
+    pw, sw = to_wire(pts), scalars_wire(ks)
+    for n, off in ((63, 0), (64, 0), (65, 0), (64, 37), (127, 1), (129, 0), (191, 60), (193, 5), (575, 125), (577, 0),
+                   (64 * 10 - 1, 0), (64 * 10 + 1, npool - 641)):
+        out, inf = eng.mul_var_batch(BN254_G1, pw[off:off + n], sw[off:off + n])
+        for i in range(n):
+            e = exp[off + i]
+            assert from_wire(out[i]) == e and bool(inf[i]) == (e == (0, 0)), (n, off, i, hex(ks[off + i]))
+
+
+def test_batch_multiply_2_18_identity_and_sample():
+    """2^18 pairs (the bench size): P_i = (a + i b) G from the device, k_i uniform below 2^256 with the edge scalars planted;
+    sum_i c_i (k_i P_i) for random 62-bit c_i through the MSM equals (sum_i c_i k_i (a + i b) mod r) G, and 4096 items (the
+    first and last waves among them) equal the oracle's (k_i (a + i b) mod r) G."""
+    import bench
+    eng = get_engine()
+    dev = torch.device("cuda", 0)
+    n = 1 << 18
+    rng = makeRng(0x254C18)
+    a, b = rng.rndBelow(BN254_R - 1) + 1, rng.rndBelow(BN254_R - 1) + 1
+    pts, pks = bench.gen_points(eng, BN254_G1, Bn254, n, a, b, dev, None)
+    sc = bench.gen_scalars(n, 256, 0x254, dev, edge_order=BN254_R)
+    for j, k in enumerate(EDGE_SCALARS):
+        for i in (100 + j, n // 2 + 64 * j, n - 1 - j):
+            sc[i] = torch.from_numpy(scalars_wire([k])[0].copy()).to(dev)
+    out = torch.empty((n, 64), dtype=torch.uint8, device=dev)
+    inf = torch.empty((n,), dtype=torch.uint8, device=dev)
+    eng.mul_var_batch_dev(BN254_G1, n, pts.data_ptr(), sc.data_ptr(), out.data_ptr(), inf.data_ptr())
+    torch.cuda.synchronize()
+    ks = bench.scalars_to_ints(sc)
+    assert max(ks) == (1 << 256) - 1
+    zero = [i for i, k in enumerate(ks) if k % BN254_R == 0]
+    inf_h = inf.cpu().numpy()
+    assert sorted(np.nonzero(inf_h)[0].tolist()) == zero
+    cr = np.random.RandomState(0x254).randint(1, 1 << 62, size=n, dtype=np.int64)
+    cw = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+    cw[:, :8] = torch.from_numpy(cr.view(np.uint8).reshape(n, 8)).to(dev)
+    tot, _ = eng.msm_dev(BN254_G1, n, out.data_ptr(), cw.data_ptr())
+    expect = sum(int(c) * k * p for c, k, p in zip(cr, ks, pks)) % BN254_R
+    assert from_wire(tot) == _aff(Bn254.BASE.multiplyUnsafe(expect))
+    idx = np.unique(np.concatenate([np.arange(64), np.arange(n - 64, n), np.random.RandomState(2).randint(0, n, 4096 - 128)]))
+    comb = _Comb()
+    want = _affine_all([comb.mul(ks[i] * pks[i]) for i in idx])
+    out_h = out.cpu().numpy()
+    for j, i in enumerate(idx):
+        assert from_wire(out_h[i]) == want[j], (int(i), hex(ks[i]))
+
+
+def test_add_pairs_and_normalize_over_waves():
+    """K = 8 items per lane, 256 lanes per block: two full blocks, three full waves and a partial one (n = 2 * 2048 + 3 * 512 + 43);
+    P + Q, P + P, P + (-P) and ZERO operands at scattered positions; normalize with Z = 0 (any X, Y) at every position of a group
+    of 8, and a whole group of Z = 0."""
+    eng = get_engine()
+    n = 2 * 2048 + 3 * 512 + 43
+    rng = makeRng(0x254A)
+    A = _progression_points(rng.rndBelow(BN254_R - 1) + 1, rng.rndBelow(BN254_R - 1) + 1, n)
+    B = _progression_points(rng.rndBelow(BN254_R - 1) + 1, rng.rndBelow(BN254_R - 1) + 1, n)
+    for i in range(n):
+        kind = (i * 7 + i // 8) % 11
+        if kind == 1:
+            B[i] = A[i]
+        elif kind == 2:
+            B[i] = A[i].negate()
+        elif kind == 3:
+            A[i] = Bn254.ZERO
+        elif kind == 4:
+            B[i] = Bn254.ZERO
+    A[n - 1], B[n - 1] = Bn254.ZERO, Bn254.ZERO
+    for sub in (False, True):
+        out, inf = eng.add_pairs_batch(BN254_G1, to_wire(A), to_wire(B), subtract=sub)
+        exp = _affine_all([p.subtract(q) if sub else p.add(q) for p, q in zip(A, B)])
+        for i, e in enumerate(exp):
+            assert from_wire(out[i]) == e and bool(inf[i]) == (e == (0, 0)), (sub, i)
+    rows, exp = [], []
+    for i in range(n):
+        x, y = A[i].toAffine() if not A[i].is0() else B[i].toAffine()
+        z = rng.rndBelow(BN254_P - 1) + 1
+        g, j = divmod(i, 8)
+        if (g % 300 < 8 and j == g % 300) or g == 100 or i == n - 1:   # Z = 0 at position g of group g (every block), group 100, the last item
+            rows.append(b"".join(v.to_bytes(32, "little") for v in ((x * z % BN254_P, y * z % BN254_P, 0) if i % 2 else (0, 1, 0))))
+            exp.append((0, 0))
+        else:
+            rows.append(b"".join(v.to_bytes(32, "little") for v in (x * z % BN254_P, y * z % BN254_P, z)))
+            exp.append((x, y))
+    out, inf = eng.normalize_batch(BN254_G1, np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(n, 96))
+    for i, e in enumerate(exp):
+        assert from_wire(out[i]) == e and bool(inf[i]) == (e == (0, 0)), i

@@ -11,13 +11,14 @@ import torch
 import bench
 from helpers import ORACLE_CURVE, wire_to_affine
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, POINT_BYTES, SECP256K1
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, POINT_BYTES, SECP256K1
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("curve,n", [(BLS12_381_G1, (1 << 17) + 1000), (BLS12_381_G1, (1 << 19) + 5), (SECP256K1, (1 << 17) + 3),
-                                     (ED25519, 1 << 17), (BLS12_381_G2, (1 << 17) + 9), (BLS12_381_G1, (1 << 16) + 1)])
+                                     (ED25519, 1 << 17), (BLS12_381_G2, (1 << 17) + 9), (BLS12_381_G1, (1 << 16) + 1),
+                                     (BN254_G1, (1 << 17) + 1000)])
 def test_host_pointer_msm_in_parts_equals_device_msm(curve, n):
     eng = get_engine()
     dev = torch.device("cuda", 0)
@@ -66,7 +67,8 @@ def test_host_pointer_msm_in_parts_equals_device_msm(curve, n):
     assert np.array_equal(got, eng.msm_dev(curve, n, d_pts.data_ptr(), torch.from_numpy(cases[0]).to(dev).data_ptr())[0])
 
 
-@pytest.mark.parametrize("curve,n", [(SECP256K1, (1 << 17) + 77), (BLS12_381_G1, 1 << 17), (SECP256K1, (1 << 19) + 1)])
+@pytest.mark.parametrize("curve,n", [(SECP256K1, (1 << 17) + 77), (BLS12_381_G1, 1 << 17), (SECP256K1, (1 << 19) + 1),
+                                     (BN254_G1, (1 << 17) + 77)])
 def test_host_pointer_batch_multiply_in_chunks_equals_device_batch(curve, n):
     eng = get_engine()
     dev = torch.device("cuda", 0)

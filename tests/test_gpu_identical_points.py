@@ -16,7 +16,7 @@ import torch
 import bench
 from helpers import ORACLE_CURVE, points_to_wire, wire_to_affine
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, POINT_BYTES
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, POINT_BYTES
 from oracle.curves import BLS_R
 
 pytestmark = pytest.mark.gpu
@@ -34,7 +34,7 @@ def _identical(curve, n, k_point=POW1, s=POW2):
     P = Pt.BASE.multiplyUnsafe(k_point)
     pw = np.tile(points_to_wire(curve, [P]), (n, 1))
     sw = np.tile(np.frombuffer(int(s).to_bytes(32, "little"), dtype=np.uint8), (n, 1))
-    exp = P.multiplyUnsafe(n * s % BLS_R)
+    exp = P.multiplyUnsafe(n * s % Pt.Fn.ORDER)
     return pw, sw, exp.toAffine(), exp.is0()
 
 
@@ -61,7 +61,8 @@ def _resident_stages(eng, curve, pw, sw, exp, tag):
     n = pw.shape[0]
     ds = _dev(sw)
     rs = eng.upload_points(curve, pw)
-    for stage in ("generic", "endo", "precomputed"):
+    # bn254 G1 has no subgroup check (h = 1) and so no endomorphism plan
+    for stage in ("generic", "precomputed") if curve == BN254_G1 else ("generic", "endo", "precomputed"):
         if stage == "endo":
             assert rs.verify_subgroup() == -1 and rs.in_subgroup
         if stage == "precomputed":
@@ -78,7 +79,7 @@ def _resident_stages(eng, curve, pw, sw, exp, tag):
     rs.free()
 
 
-@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2])
+@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2, BN254_G1])
 def test_benchmark_msm_32768_identical_points(curve):
     """pippenger(G1, 32768 x (2^235 G), 32768 x 2^241) exactly as benchmark/bls12-381.ts:77-79 builds it."""
     eng = get_engine()
@@ -106,32 +107,50 @@ def test_benchmark_msm_32768_identical_points(curve):
                     rs = eng.upload_points(curve, pw)
                     got, _ = rs.msm_dev(ds.data_ptr())
                     assert wire_to_affine(curve, got) == exp, (tag, "resident")
-                    assert rs.verify_subgroup() == -1
+                    if curve == BN254_G1:
+                        assert rs.precompute()
+                    else:
+                        assert rs.verify_subgroup() == -1
                     got, _ = rs.msm_dev(ds.data_ptr())
-                    assert wire_to_affine(curve, got) == exp, (tag, "endo")
+                    assert wire_to_affine(curve, got) == exp, (tag, "precomputed" if curve == BN254_G1 else "endo")
                     rs.free()
     finally:
         eng.msm_set_tuning(0, -1)
 
 
-@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2])
+@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2, BN254_G1])
 def test_identical_points_whose_sum_is_zero_or_flips_sign(curve):
     """n identical points with a scalar s such that n*s = 0 mod r cannot be built with n a power of two (r is odd), so
     the ZERO result comes from pairs: half the scalars s, half r - s.  Every bucket pair cancels at the very top."""
     eng = get_engine()
+    order = ORACLE_CURVE[curve].Fn.ORDER
     pw, sw, _, _ = _identical(curve, AMOUNT)
-    neg = np.frombuffer(int(BLS_R - POW2).to_bytes(32, "little"), dtype=np.uint8)
+    neg = np.frombuffer(int(order - POW2).to_bytes(32, "little"), dtype=np.uint8)
     sw = sw.copy()
     sw[AMOUNT // 2:] = neg
     got, inf = eng.msm(curve, pw, sw)
     assert inf and not got.any()
     rs = eng.upload_points(curve, pw)
-    assert rs.verify_subgroup() == -1
-    got, inf = rs.msm(sw)
-    assert inf and not got.any()
+    if curve != BN254_G1:
+        assert rs.verify_subgroup() == -1
+        got, inf = rs.msm(sw)
+        assert inf and not got.any()
     assert rs.precompute()
     got, inf = rs.msm(sw)
     assert inf and not got.any()
+    if curve == BN254_G1:
+        # one more s than r - s: the sum flips from ZERO to s P, and with the halves swapped to -(s P)
+        P = ORACLE_CURVE[curve].BASE.multiplyUnsafe(POW1)
+        for s_odd in (POW2, order - POW2):
+            sw2 = sw.copy()
+            sw2[AMOUNT // 2 - 1] = np.frombuffer(int(s_odd).to_bytes(32, "little"), dtype=np.uint8)
+            sw2[AMOUNT // 2] = sw2[AMOUNT // 2 - 1]
+            # indices 0 .. n/2 - 2 hold s, n/2 + 1 .. n - 1 hold r - s: they cancel; the two middle ones leave 2 s_odd P
+            exp = P.multiplyUnsafe(2 * s_odd % order)
+            got, inf = rs.msm(sw2)
+            assert wire_to_affine(curve, got) == exp.toAffine() and not inf, hex(s_odd)
+            got, inf = eng.msm(curve, pw, sw2)
+            assert wire_to_affine(curve, got) == exp.toAffine() and not inf, hex(s_odd)
     rs.free()
 
 
@@ -186,3 +205,26 @@ def test_identical_points_g2_2_18():
     got, _ = rs.msm_dev(ds.data_ptr())
     assert wire_to_affine(BLS12_381_G2, got) == exp
     rs.free()
+
+
+def test_one_million_identical_points_bn254():
+    """2^20 copies of 2^235 G on bn254 G1 (c = 16): one bucket of 2^20 entries per window, merged by the single-lane fix-up
+    (bn254 has no cooperative units) over the longest runs any test gives it."""
+    eng = get_engine()
+    n = 1 << 20
+    pw, sw, exp, _ = _identical(BN254_G1, n)
+    dp, ds = _dev(pw), _dev(sw)
+    got, _ = eng.msm_dev(BN254_G1, n, dp.data_ptr(), ds.data_ptr())
+    assert wire_to_affine(BN254_G1, got) == exp
+    assert eng.msm_last_plan()["c"] == 16
+    got, _ = eng.msm_split_windows_dev(BN254_G1, n, 8, dp.data_ptr(), ds.data_ptr())
+    assert wire_to_affine(BN254_G1, got) == exp
+    rs = eng.upload_points(BN254_G1, pw)
+    got, _ = rs.msm_dev(ds.data_ptr())
+    assert wire_to_affine(BN254_G1, got) == exp
+    assert rs.precompute()
+    got, _ = rs.msm_dev(ds.data_ptr())
+    assert wire_to_affine(BN254_G1, got) == exp
+    rs.free()
+    got, _ = eng.msm(BN254_G1, pw, sw)
+    assert wire_to_affine(BN254_G1, got) == exp

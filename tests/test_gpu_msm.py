@@ -4,14 +4,14 @@ import numpy as np
 import pytest
 
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, SECP256K1
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, SECP256K1
 from oracle import curve as C
 from oracle.curves import makeRng
 
 from helpers import ORACLE_CURVE, points_to_wire, scalars_to_wire, wire_to_affine
 
 pytestmark = pytest.mark.gpu
-CURVES = [SECP256K1, BLS12_381_G1, BLS12_381_G2]
+CURVES = [SECP256K1, BLS12_381_G1, BLS12_381_G2, BN254_G1]
 
 
 def gpu_msm(curve, pts, scalars):
@@ -58,7 +58,7 @@ def test_msm_edge_cases(curve):
     assert gpu_msm(curve, [G.double()] * 70, [k] * 70) == G.multiplyUnsafe(2 * 70 * k % order).toAffine()
 
 
-@pytest.mark.parametrize("curve,n", [(SECP256K1, 300), (BLS12_381_G1, 300), (BLS12_381_G2, 120)])
+@pytest.mark.parametrize("curve,n", [(SECP256K1, 300), (BLS12_381_G1, 300), (BLS12_381_G2, 120), (BN254_G1, 300)])
 def test_msm_matches_oracle_pippenger(curve, n):
     Pt = ORACLE_CURVE[curve]
     pts, sc, exp = progression(Pt, n, 0x6D736D00 + curve)
@@ -66,7 +66,7 @@ def test_msm_matches_oracle_pippenger(curve, n):
     assert gpu_msm(curve, pts, sc) == exp.toAffine()
 
 
-@pytest.mark.parametrize("curve,n", [(BLS12_381_G1, 5000), (SECP256K1, 3000), (BLS12_381_G2, 1500)])
+@pytest.mark.parametrize("curve,n", [(BLS12_381_G1, 5000), (SECP256K1, 3000), (BLS12_381_G2, 1500), (BN254_G1, 3000)])
 def test_msm_progression_medium(curve, n):
     """Sizes past what the oracle's pippenger finishes quickly: pinned by the progression identity."""
     Pt = ORACLE_CURVE[curve]
@@ -84,22 +84,45 @@ def test_msm_non_normalised_inputs_and_window_override(monkeypatch):
         assert gpu_msm(BLS12_381_G1, pts, sc) == exp.toAffine()
 
 
-@pytest.mark.parametrize("seg,run_serial", [(1, 0), (1, 2), (3, 0), (3, 1), (64, -1), (100000, -1), (7, 50)])
+def test_msm_window_override_bn254(monkeypatch):
+    """bn254 G1 under forced widths, among them the c = 3, 4, 6, 13 and 14 that none of its default plans uses."""
+    Pt = ORACLE_CURVE[BN254_G1]
+    pts, sc, exp = progression(Pt, 700, 0x254)
+    for c in (2, 3, 4, 6, 7, 11, 13, 14, 16):
+        monkeypatch.setenv("NCG_MSM_C", str(c))
+        assert gpu_msm(BN254_G1, pts, sc) == exp.toAffine(), c
+        assert get_engine().msm_last_plan()["c"] == c
+
+
+SEGMENT_GRID = [(1, 0), (1, 2), (3, 0), (3, 1), (64, -1), (100000, -1), (7, 50)]
+
+
+@pytest.mark.parametrize("seg,run_serial", SEGMENT_GRID)
 def test_msm_segment_lengths_and_skewed_buckets(monkeypatch, seg, run_serial):
     """Lane-segment boundaries cutting buckets in every possible way, including one bucket that holds every entry (all
     scalars equal) and many empty buckets; with run_serial 0 / 1 every cut bucket takes the long-run work list
     (k_msm_fixup_long), with 50 none does (k_msm_fixup_merge adds every piece serially).  The segment is set through
     ncg_msm_set_tuning and ncg_msm_last_plan proves that the launch used it (the old form of this test set an
     environment variable the shipped library never read, so it ran one configuration four times)."""
+    _segment_lengths_and_skewed_buckets(monkeypatch, BLS12_381_G1, seg, run_serial)
+
+
+@pytest.mark.parametrize("seg,run_serial", SEGMENT_GRID)
+def test_msm_segment_lengths_and_skewed_buckets_bn254(monkeypatch, seg, run_serial):
+    """The same cuts on bn254 G1, which has no cooperative fix-up units: its cut buckets go through the single-lane fix-up."""
+    _segment_lengths_and_skewed_buckets(monkeypatch, BN254_G1, seg, run_serial)
+
+
+def _segment_lengths_and_skewed_buckets(monkeypatch, curve, seg, run_serial):
     monkeypatch.setenv("NCG_MSM_C", "6")
     eng = get_engine()
-    Pt = ORACLE_CURVE[BLS12_381_G1]
+    Pt = ORACLE_CURVE[curve]
     pts, sc, exp = progression(Pt, 900, 0x5E6)
     k = 0x1F                                            # every point lands in the same low bucket
     tot = C.normalizeZ(Pt, [sum_points(Pt, pts)])[0]
     try:
         eng.msm_set_tuning(seg, run_serial)
-        assert gpu_msm(BLS12_381_G1, pts, sc) == exp.toAffine()
+        assert gpu_msm(curve, pts, sc) == exp.toAffine()
         lp = eng.msm_last_plan()
         assert lp["seg"] == seg and lp["c"] == 6 and lp["nb"] == 32
         if run_serial >= 0:
@@ -108,23 +131,23 @@ def test_msm_segment_lengths_and_skewed_buckets(monkeypatch, seg, run_serial):
             assert lp["long_runs"] >= 32, lp
         if run_serial == 50:
             assert lp["long_runs"] == 0, lp
-        assert gpu_msm(BLS12_381_G1, pts, [k] * 900) == tot.multiplyUnsafe(k).toAffine()
+        assert gpu_msm(curve, pts, [k] * 900) == tot.multiplyUnsafe(k).toAffine()
         lp = eng.msm_last_plan()
         assert lp["seg"] == seg
         if seg < 900 and run_serial in (0, 1, 2):
             assert lp["long_runs"] >= 1, lp             # the one bucket of window 0 is a single long run
         # the other pipelines under the same cut: sharded by points and by windows, shared-bucket sets need >= 4096 points
-        pw, sw = points_to_wire(BLS12_381_G1, pts), scalars_to_wire(sc)
+        pw, sw = points_to_wire(curve, pts), scalars_to_wire(sc)
         import torch
         dp, ds = torch.from_numpy(pw).cuda(), torch.from_numpy(sw).cuda()
         for parts in (2, 5):
-            got, _ = eng.msm_split_windows_dev(BLS12_381_G1, 900, parts, dp.data_ptr(), ds.data_ptr())
-            assert wire_to_affine(BLS12_381_G1, got) == exp.toAffine(), ("windows", parts)
-            got, _ = eng.msm_split_dev(BLS12_381_G1, 900, parts, dp.data_ptr(), ds.data_ptr())
-            assert wire_to_affine(BLS12_381_G1, got) == exp.toAffine(), ("points", parts)
+            got, _ = eng.msm_split_windows_dev(curve, 900, parts, dp.data_ptr(), ds.data_ptr())
+            assert wire_to_affine(curve, got) == exp.toAffine(), ("windows", parts)
+            got, _ = eng.msm_split_dev(curve, 900, parts, dp.data_ptr(), ds.data_ptr())
+            assert wire_to_affine(curve, got) == exp.toAffine(), ("points", parts)
     finally:
         eng.msm_set_tuning(0, -1)
-    gpu_msm(BLS12_381_G1, pts[:50], sc[:50])
+    gpu_msm(curve, pts[:50], sc[:50])
     assert eng.msm_last_plan()["seg"] != 100000          # the defaults are back
 
 

@@ -24,11 +24,15 @@ import torch
 import bench
 from helpers import ORACLE_CURVE, wire_to_affine
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, SECP256K1
+from bn254_helpers import BN254_P
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, SECP256K1
 
 pytestmark = pytest.mark.gpu
 
-NMAX = {SECP256K1: 1 << 17, ED25519: 1 << 17, BLS12_381_G1: 1 << 17, BLS12_381_G2: 1 << 15}
+NMAX = {SECP256K1: 1 << 17, ED25519: 1 << 17, BLS12_381_G1: 1 << 17, BLS12_381_G2: 1 << 15, BN254_G1: 1 << 17}
+# bn254 G1 runs 15 more trials after the common 72, one per width c = 2 .. 16 forced (its default plans are c = log2(n) - 4, and
+# no other test forces a width on its 254-bit order); they come after the common draws, so the other curves' sequences are the same
+FORCED_C = {BN254_G1: list(range(2, 17))}
 
 
 def _scalars(rnd, shape, n, order):
@@ -56,7 +60,7 @@ def _scalars(rnd, shape, n, order):
 
 
 SHAPES = ["uniform", "small", "top", "few", "one", "sparse_top", "zeros", "pow2"]
-FIELD_P = {SECP256K1: (1 << 256) - (1 << 32) - 977, ED25519: (1 << 255) - 19}
+FIELD_P = {SECP256K1: (1 << 256) - (1 << 32) - 977, ED25519: (1 << 255) - 19, BN254_G1: BN254_P}
 
 
 def _neg_row(curve, row):
@@ -128,7 +132,7 @@ def _mutate(rnd, curve, Pt, n, ks, sc, rows):
     return k_eff, tors
 
 
-@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2, SECP256K1, ED25519])
+@pytest.mark.parametrize("curve", [BLS12_381_G1, BLS12_381_G2, SECP256K1, ED25519, BN254_G1])
 def test_randomised_msm_shapes_and_window_widths(curve):
     eng = get_engine()
     dev = torch.device("cuda", 0)
@@ -142,11 +146,17 @@ def test_randomised_msm_shapes_and_window_widths(curve):
     sizes = [1, 2, 63, 64, 65, 1000, 4095, 4096, 4097, 20479, 20481, 32768, 65537, nmax]
     old = os.environ.get("NCG_MSM_C")
     done = 0
+    forced = FORCED_C.get(curve, [])
     try:
-        for trial in range(72):
-            n = min(nmax, sizes[trial % len(sizes)] if trial < 14 else rnd.randrange(1, nmax + 1))
-            shape = SHAPES[trial % len(SHAPES)] if trial < 16 else rnd.choice(SHAPES)
-            c = rnd.choice([0, 0, 11, 12, 13, 14, 15, 16]) if n >= 32 else 0
+        for trial in range(72 + len(forced)):
+            if trial < 72:
+                n = min(nmax, sizes[trial % len(sizes)] if trial < 14 else rnd.randrange(1, nmax + 1))
+                shape = SHAPES[trial % len(SHAPES)] if trial < 16 else rnd.choice(SHAPES)
+                c = rnd.choice([0, 0, 11, 12, 13, 14, 15, 16]) if n >= 32 else 0
+            else:                                     # narrow windows meet at most 2^(c + 6) points: 2^c / 2 buckets per window
+                c = forced[trial - 72]
+                n = rnd.randrange(32, min(nmax, 1 << (c + 6)) + 1)
+                shape = rnd.choice(SHAPES)
             if c:
                 os.environ["NCG_MSM_C"] = str(c)
             else:
@@ -199,6 +209,6 @@ def test_randomised_msm_shapes_and_window_widths(curve):
             os.environ.pop("NCG_MSM_C", None)
         else:
             os.environ["NCG_MSM_C"] = old
-    assert done == 72 and n_mutated >= 30
+    assert done == 72 + len(forced) and n_mutated >= 30
     if curve in (BLS12_381_G1, BLS12_381_G2):
         assert n_torsion >= 10

@@ -18,7 +18,7 @@ import pytest
 
 from helpers import ORACLE_CURVE, points_to_wire, scalars_to_wire, wire_to_affine
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, POINT_BYTES, SECP256K1, Engine, MultiEngine
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, POINT_BYTES, SECP256K1, Engine, MultiEngine
 from oracle import curve as OC
 from oracle.curves import makeRng
 
@@ -45,7 +45,7 @@ def _dev(arr):
     return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
 
 
-@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2])
+@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1])
 def test_split_pipeline_matches_oracle(curve):
     eng = get_engine()
     n = 150 if curve != BLS12_381_G2 else 70
@@ -109,7 +109,7 @@ def test_rccl_communicator_single_rank():
         eng.close()
 
 
-@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2])
+@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1])
 def test_host_staged_exchange_native_combine(curve):
     """ncg_msm_shard_local_dev per shard -> slots concatenated on the host -> ncg_msm_shard_combine: the code path of G
     ranks with a non-RCCL transport, here with the shards of one process."""
@@ -139,7 +139,7 @@ def test_host_staged_exchange_native_combine(curve):
     assert inf
 
 
-@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2])
+@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1])
 def test_window_sharded_pipeline_matches_oracle(curve):
     """Strong-scaling mode (include/ncg.h "WINDOW-sharded mode"): part r runs a range of the windows of ALL points
     (curve.ts:886-902), the slots are concatenated, every part count incl. more parts than windows; the host-staged
@@ -251,7 +251,7 @@ def test_multi_engine_one_device():
     m = MultiEngine([0])
     try:
         assert m.devices() == 1
-        for curve in (SECP256K1, BLS12_381_G1, BLS12_381_G2, ED25519):
+        for curve in (SECP256K1, BLS12_381_G1, BLS12_381_G2, ED25519, BN254_G1):
             pw, sw, exp = _case(curve, 60, 0xBEEF + curve)
             got, inf = m.msm(curve, pw, sw)
             assert wire_to_affine(curve, got) == exp.toAffine() and inf == exp.is0()

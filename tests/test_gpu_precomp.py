@@ -11,7 +11,7 @@ import torch
 import bench
 from helpers import ORACLE_CURVE, wire_to_affine
 from noble_curves_amd import get_engine
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, SECP256K1
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, SECP256K1
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +20,7 @@ def _ints_to_dev(vals, dev):
     return torch.from_numpy(bench.ints_to_le_bytes(vals).copy()).to(dev)
 
 
-@pytest.mark.parametrize("curve,lg", [(SECP256K1, 13), (BLS12_381_G1, 14), (BLS12_381_G2, 12)])
+@pytest.mark.parametrize("curve,lg", [(SECP256K1, 13), (BLS12_381_G1, 14), (BLS12_381_G2, 12), (BN254_G1, 13)])
 def test_precomputed_set_equals_generic_path_and_identity(curve, lg):
     eng = get_engine()
     dev = torch.device("cuda", 0)

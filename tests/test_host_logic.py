@@ -722,16 +722,37 @@ def test_short_top_window_spreading_keeps_every_digit_weight():
     and extreme scalars below the group order the weight of the bucket is the digit, the bucket exists, the spread digit fits the
     int16 the kernel stores, and sum_w digit_w 2^(c w) - H' gives the scalar back (the reference's window sum, curve.ts:886-902)."""
     import random
-    from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, ED25519, SECP256K1
+    from bn254_helpers import BN254_R
+    from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, SECP256K1
     from oracle.curves import BLS_R, ED25519_L, SECP256K1_N
     rnd = random.Random(0x5EED)
     cases = [(BLS12_381_G2, 1 << 18, 0, BLS_R, True), (BLS12_381_G1, 1 << 18, 0, BLS_R, True), (BLS12_381_G1, 1 << 20, 0, BLS_R, False),
              (BLS12_381_G1, 1 << 16, 0, BLS_R, True), (SECP256K1, 1 << 20, 0, SECP256K1_N, True), (ED25519, 1 << 20, 0, ED25519_L, False),
              (BLS12_381_G1, 1 << 15, 0, BLS_R, True), (BLS12_381_G2, 1 << 12, 14, BLS_R, True), (BLS12_381_G1, 4096, 12, BLS_R, True)]
+    # bn254 G1 (c = log2(n) - 4 by default): every forced width at a small n, and the default plans of 2^0 .. 2^20 points.  Its
+    # spread decision is the rule of msm_plan_top_spread restated (None below), so the top windows of every width are pinned.
+    cases += [(BN254_G1, 64, c, BN254_R, None) for c in range(2, 17)]
+    cases += [(BN254_G1, 1 << lg, 0, BN254_R, None) for lg in range(21)]
+    bn_widths = set()
     for curve, n, c_over, order, expect_spread in cases:
         p = hosttest.msm_plan_top(curve, n, c_over)
         c, nwin, tb, sub, nb, hp = p["c"], p["nwin"], p["top_tb"], p["top_submask"], p["nb"], p["hprime"]
-        assert (tb > 0) == expect_spread, (curve, n, p)
+        if curve == BN254_G1:
+            assert c == (c_over or max(2, min(16, n.bit_length() - 1 - 4)))     # the default plan: c = log2(n) - 4
+        else:
+            assert c_over == 0 or c == c_over
+        if expect_spread is None:
+            # plan_windows: the fewest windows from floor(252 / c) on with (r - 1) + H' < 2^(c nwin)
+            assert nwin == min(w for w in range(max(1, 252 // c), 300 // c + 3) if order - 1 + sum(1 << (c * v + c - 1) for v in range(w)) < 1 << (c * w))
+            vmax = ((order + hp) >> (c * (nwin - 1))) & ((1 << c) - 1)
+            assert p["vmax"] == vmax
+            maxd = vmax - (1 << (c - 1)) + 1 if vmax >= 1 << (c - 1) else 1 << (c - 1)
+            want_tb = max(1, (maxd - 1).bit_length())
+            subs = (nb if nb < 32768 else 16384) >> want_tb
+            assert (tb, sub) == ((want_tb, subs - 1) if subs >= 8 else (0, 0)), (curve, n, c_over, p)
+            bn_widths.add(c)
+        else:
+            assert (tb > 0) == expect_spread, (curve, n, p)
         half = 1 << (c - 1)
         assert hp == sum(1 << (c * w + c - 1) for w in range(nwin)) and nb == half
         ks = [0, 1, order - 1, order - 2, order >> 1, (1 << (order.bit_length() - 1)) - 1, 1 << (order.bit_length() - 1)]
@@ -754,6 +775,7 @@ def test_short_top_window_spreading_keeps_every_digit_weight():
                 assert sub + 1 >= 8
         if tb:
             assert top_max <= 1 << tb
+    assert bn_widths == set(range(2, 17))
 
 
 def test_msm_lane_segment_small_plans_are_priced_by_latency():

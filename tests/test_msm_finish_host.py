@@ -2,7 +2,9 @@
 `sum = sum.add(resI); sum = sum.double() x c` chain (src/abstract/curve.ts:901-902) and weierstrass.ts:951-969.
 bls12-381 runs the 64-bit-limb Jacobian form (csrc/bls_host64.hpp); variant 0 is the device templates compiled for
 the host.  Both must reproduce the oracle's group element bit for bit - including infinity entries and the
-exceptional additions P + P / P + (-P), which the Horner chain meets when window sums repeat."""
+exceptional additions P + P / P + (-P), which the Horner chain meets when window sums repeat.  secp256k1, ed25519 and
+bn254 G1 run msm_host_finish<C> (the device templates over the 9-limb Fe9 forms) on every curve's stored window sums,
+canonical and at the loosest limbs their storage bound admits."""
 import os
 import sys
 
@@ -11,9 +13,10 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hosttest  # noqa: E402
-from helpers import ORACLE_CURVE, affine_to_wire  # noqa: E402
-from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, POINT_BYTES  # noqa: E402
-from oracle.curves import BLS_P, makeRng  # noqa: E402
+from bn254_helpers import BN254_P, MONT_R, spread  # noqa: E402
+from helpers import ORACLE_CURVE, affine_to_wire, limbs, loose  # noqa: E402
+from noble_curves_amd._native import BLS12_381_G1, BLS12_381_G2, BN254_G1, ED25519, POINT_BYTES, SECP256K1  # noqa: E402
+from oracle.curves import BLS_P, ED25519_P, SECP256K1_P, makeRng  # noqa: E402
 
 R29 = 1 << 406   # Montgomery radix of the device storage format (14 limbs of 29 bits)
 G = 3            # MSM_GROUP
@@ -88,6 +91,78 @@ def test_host_finish_matches_oracle(curve, c, nwin):
                 assert inf == exp.is0(), (variant, lazy)
                 want = bytes(POINT_BYTES[curve]) if exp.is0() else affine_to_wire(curve, exp.toAffine())
                 assert out.tobytes() == want, (variant, lazy)
+
+
+# The Fe9 storage of the other curves (csrc/msm.hpp MsmGroup<C>::acc_load, FieldIO<Fe9<PR, B>>: 9 raw limbs of 29 bits per
+# coordinate, four coordinates): secp256k1 Xyzz over Fe9<Fe9SecpPR, 2> (plain residues, limbs below 2 U); ed25519 extended
+# (X, Y, Z, T) over Fe9<Fe9EdPR, 1> (limbs below U); bn254 Xyzz over Fe9<Bn254PR, 2> (Montgomery, R = 2^261: limbs below
+# 2 * 2^29 and a value below 4 p, fe9m.hpp).  All-zero words are the identity on every curve.
+FE9_STORE = {SECP256K1: (SECP256K1_P, 2), ED25519: (ED25519_P, 1), BN254_G1: (BN254_P, 2)}
+
+
+def fe9_words(curve, v, rng, loosest):
+    """one stored coordinate of residue v: canonical, or at the loosest limbs the curve's storage bound admits"""
+    p, B = FE9_STORE[curve]
+    if curve == BN254_G1:
+        m = v * MONT_R % p
+        return spread(m + 3 * p, B, rng, loosest=True) if loosest else limbs(m)   # m + 3 p < 4 p: the largest value
+    return loose(v, B, p) if loosest else limbs(v)
+
+
+def fe9_acc_words(curve, P, rng, loosest):
+    """one stored accumulator of P for a random z: Xyzz (x z^2, y z^3, z^2, z^3), ed25519 (x z, y z, z, x y z)"""
+    p, _ = FE9_STORE[curve]
+    if P.is0():
+        if curve == ED25519 and loosest:                  # the extended identity (0, z, z, 0) of a nonzero z
+            z = rng.rndBelow(p - 1) + 1
+            return [w for c in (0, z, z, 0) for w in fe9_words(curve, c, rng, True)]
+        return [0] * 36
+    x, y = P.toAffine()
+    z = rng.rndBelow(p - 1) + 1
+    if curve == ED25519:
+        coords = [x * z % p, y * z % p, z, x * y * z % p]
+    else:
+        coords = [x * z * z % p, y * z ** 3 % p, z * z % p, z ** 3 % p]
+    return [w for c in coords for w in fe9_words(curve, c, rng, loosest)]
+
+
+@pytest.mark.parametrize("curve", [SECP256K1, ED25519, BN254_G1])
+@pytest.mark.parametrize("c,nwin", [(2, 2), (2, 127), (4, 3), (7, 5), (16, 16), (13, 20), (5, 52)])
+def test_host_finish_fe9_curves_match_oracle(curve, c, nwin):
+    """msm_host_finish<C> for the curves without a 64-bit host form; (2, 2) forces P + P and P + (-P) in the Horner chain,
+    (2, 127) is bn254's c = 2 plan with window sums that repeat (equal and opposite members of consecutive windows)"""
+    Pt = ORACLE_CURVE[curve]
+    assert hosttest.msm_plan(curve, 1 << 10)["acc_words"] == 36
+    rng = makeRng(0xF1A19 + 31 * c + nwin + 1000 * curve)
+    ng = (c - 1 + G - 1) // G if c >= 2 else 1
+    base = Pt.BASE.multiplyUnsafe(rng.rndBelow(1 << 64) + 2)
+    V = [[(Pt.ZERO if (j + w) % 5 == 4 else base.multiplyUnsafe(rng.rndBelow(1 << 40) + 1)) for w in range(nwin)] for j in range(ng)]
+    if (c, nwin) == (2, 2):
+        cases = [V, [[V[0][1].double().double(), V[0][1]]], [[V[0][1].double().double().negate(), V[0][1]]],
+                 [[Pt.ZERO, Pt.ZERO]], [[base.negate(), Pt.ZERO]]]
+    elif (c, nwin) == (2, 127):
+        # acc = 4 acc' + V_w: V_w = 4 acc' doubles, V_w = -4 acc' cancels, in the middle of a long chain
+        W = [base.multiplyUnsafe(rng.rndBelow(1 << 20) + 1) for _ in range(nwin)]
+        acc = Pt.ZERO
+        for w in range(nwin - 1, -1, -1):
+            acc = acc.double().double()
+            if w in (100, 60):
+                W[w] = acc
+            elif w in (80, 30):
+                W[w] = acc.negate()
+            acc = acc.add(W[w])
+        cases = [[W]]
+    else:
+        cases = [V]
+    for Vs in cases:
+        exp = expected(Pt, Vs, c, nwin, ng)
+        want = affine_to_wire(curve, exp.toAffine())
+        for loosest in (False, True):
+            fin = [wd for j in range(ng) for w in range(nwin) for wd in fe9_acc_words(curve, Vs[j][w], rng, loosest)]
+            for variant in (0, 1):
+                out, inf = hosttest.msm_finish(curve, c, nwin, np.array(fin, dtype=np.uint32), POINT_BYTES[curve], variant)
+                assert inf == exp.is0(), (variant, loosest)
+                assert out.tobytes() == want, (variant, loosest)
 
 
 def test_plan_twin_matches_expectation():
