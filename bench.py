@@ -2,6 +2,13 @@
 """Benchmark of the MI355X hot path (BASELINE.json metric: EC scalar-mults/s and MSM points/s).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full
+
+A plain run sets up, times the K steps of each workload below, verifies what they computed (the checksums and the
+samples against the CPU oracle described below), writes --dump-outputs and prints the line.  Everything else this
+script can measure runs with --full only: the rocprofv3 counter passes, the CPU baselines (the C port, the reference's
+own code, configs[0]), the power_state legs, the slow host-side cross-checks, the host-pointer, in-flight,
+window-share and resident-set timings of one GPU and, with several ranks, the strong-scaling blocks.
 
 Primary line (`value`): configs[1] - secp256k1 batch variable-base scalar multiplication
 (Point.multiplyUnsafe semantics, GLV), 2^20 (P_i, k_i) pairs per GPU, inputs resident in HBM.
@@ -697,10 +704,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log2n", type=int, default=20, help="items per GPU (2^log2n)")
     ap.add_argument("--workload", default="all", choices=["all", "secp256k1", "msm_g1", "msm_g2", "ed25519", "ntt"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: counter passes, CPU baselines, power_state, slow cross-checks, "
+                         "host-pointer / in-flight / window-share / resident-set timings, strong-scaling blocks (see the docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU-baseline legs")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline leg (1 thread, then all threads)")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not run the rocprofv3 counter passes in this run")
-    ap.add_argument("--quick-verify", action="store_true", help="(PMC child runs) skip the slow host-side cross-checks")
+    ap.add_argument("--no-live-pmc", action="store_true", help="(--full) do not run the rocprofv3 counter passes in this run")
+    ap.add_argument("--quick-verify", action="store_true",
+                    help="(--full) skip the slow host-side cross-checks, the power_state legs and the host-pointer / in-flight / window-share timings")
     ap.add_argument("--out", default=None, help="where the FULL result object goes (default gpurun_out/bench_full.json); stdout gets the compact line")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
     ap.add_argument("--dist-dry-run", action="store_true",
@@ -764,19 +775,20 @@ def main():
     assert stream != 0
     n = 1 << args.log2n
     K, W = args.steps, args.warmup
-    cpu_leg = rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_leg = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    side_legs = args.full and not args.quick_verify       # power_state, slow cross-checks, host-pointer / in-flight / share timings
     live = None
-    if rank == 0 and world == 1 and not args.no_live_pmc and not args.quick_verify:
+    if rank == 0 and world == 1 and not args.no_live_pmc and side_legs:
         live = pmc_live(args.workload, args.log2n)
     pmc = Pmc(live)
     native_multi = init_comm(eng, device, single_ok=args.dist_dry_run) if dist_on else False
     result = {}
     extra = {}
-    host = cpu_info() if rank == 0 else {}
+    host = cpu_info() if (args.full and rank == 0) else {}
     dump = OutputDump(args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     from oracle import refjs
-    ref_ok = rank == 0 and refjs.available()
+    ref_ok = cpu_leg and refjs.available()
 
     def with_reference(port_entry, ref_info, unit, sample):
         """cpu_baseline = the REFERENCE's own TypeScript code on this host's Node (oracle/_ref/refjs.bundle: /root/reference/src type-stripped
@@ -813,7 +825,7 @@ def main():
         if dump:
             dump.add_rows("secp256k1_points", out)          # affine wire format, 64 bytes per point
             dump.add_rows("secp256k1_infinity", inf)
-        pstate = power_state(step, dev_index) if (rank == 0 and world == 1 and not args.quick_verify) else None
+        pstate = power_state(step, dev_index) if (rank == 0 and world == 1 and side_legs) else None
         wall = max_over_ranks(wall, dist_on, device)
         ev_ms = max_over_ranks(ev_ms, dist_on, device)
         # ---- verification (outside the timed region)
@@ -851,7 +863,7 @@ def main():
         if pstate:
             pstate["ms_per_step_x_sclk"] = wall / K * 1e3 * pstate["sclk_mhz"][1]
             result["power_state"] = pstate
-        if not dist_on and not args.quick_verify:   # (the PMC / kernel-stats child runs keep to the headline launches)
+        if not dist_on and side_legs:   # (the PMC / kernel-stats child runs keep to the headline launches)
             # end to end through the host-pointer entry point (ncg_mul_var_batch): pinned-once host buffers, chunked H2D / kernels / D2H
             e_p, e_s = pts.cpu().numpy(), sc.cpu().numpy()
             e_o, e_i = np.zeros((n, 64), np.uint8), np.zeros((n,), np.uint8)
@@ -948,7 +960,7 @@ def main():
         if dump:
             dump.add("msm_%s_point" % cname, holder["r"][0])
             dump.add("msm_%s_infinity" % cname, [holder["r"][1]])
-        pstate_m = power_state(step, dev_index, 0.9) if (rank == 0 and world == 1 and not args.quick_verify) else None
+        pstate_m = power_state(step, dev_index, 0.9) if (rank == 0 and world == 1 and side_legs) else None
         wall = max_over_ranks(wall, dist_on, device)
         expect = sum_over_ranks_bigint(local_expect, BLS_R, dist_on, device)
         got, got_inf = holder["r"]
@@ -973,7 +985,7 @@ def main():
         if pstate_m:
             pstate_m["ms_per_msm_x_sclk"] = wall / K * 1e3 * pstate_m["sclk_mhz"][1]
             entry["power_state"] = pstate_m
-        if not dist_on and not args.quick_verify:   # (the PMC / kernel-stats child runs keep to the headline launches)
+        if not dist_on and side_legs:   # (the PMC / kernel-stats child runs keep to the headline launches)
             # end to end through the HOST-pointer entry point (the boundary the N-API addon binds: ncg_msm): inputs in pinned host
             # memory (ncg_host_register once), scalars first, the points in parts accumulated while the next part crosses PCIe
             pts_h, sc_h = pts.cpu().numpy(), sc.cpu().numpy()
@@ -1040,7 +1052,7 @@ def main():
             wres.free()
             entry["window_share"] = dict(shares, note="per-rank share of ONE %d-point MSM cut by windows over G ranks (resident set, stored form), emulated on one GPU; speedup_* = "
                                                       "this run's single-GPU ms_per_msm / share; the xGMI all-gather (~30 us) is not included" % nn)
-        if not dist_on:
+        if not dist_on and args.full:
             # the same MSM on a resident set verified to lie in the prime-order subgroup (ncg_points_verify_subgroup,
             # once per set): the scalars are split along the curve endomorphism (csrc/endo.hpp) - same group
             # element, half (G1) / a quarter (G2) of the windows.  pippenger itself accepts arbitrary curve
@@ -1194,7 +1206,7 @@ def main():
                                                  "first 4096 points of the same MSM through the reference's pippenger (abstract/curve.ts:863-905), one call; "
                                                  "result compared bit-exactly with the GPU MSM on the same subset")
         extra["msm_g1"] = msm
-        if dist_on:
+        if dist_on and args.full:
             # strong scaling (configs[3] as written): ONE 2^log2n-point MSM whose points are split
             # across the ranks (n/world each), combined inside the C ABI
             ns = n // world
@@ -1257,7 +1269,7 @@ def main():
                                                   "first 1024 points of the same MSM through the reference's pippenger over Fp2, one call; result compared "
                                                   "bit-exactly with the GPU MSM on the same subset")
         extra["msm_g2"] = msm2
-        if dist_on:
+        if dist_on and args.full:
             ns = n2 // world
             sub_expect = sum(k * p for k, p in zip(sub2["ks"][:ns], sub2["pks"][:ns])) % BLS_R
             hs2 = {}
@@ -1318,7 +1330,7 @@ def main():
         wall, ev_ms = st_ed
         if dump:
             dump.add_rows("ed25519_valid", d_ok)
-        pstate_e = power_state(step_ed, dev_index, 0.9) if (rank == 0 and world == 1 and not args.quick_verify) else None
+        pstate_e = power_state(step_ed, dev_index, 0.9) if (rank == 0 and world == 1 and side_legs) else None
         wall = max_over_ranks(wall, dist_on, device)
         got = d_ok.cpu().numpy().astype(bool)
         assert np.array_equal(got, expect), "ed25519 verdict mismatch vs construction / zip215.json"
@@ -1327,7 +1339,7 @@ def main():
         torch.cuda.synchronize()
         got_strict = d_ok.cpu().numpy().astype(bool)
         assert np.array_equal(got_strict[:tail], expect[:tail]), "ed25519 strict-mode verdict mismatch"
-        if not args.quick_verify:
+        if side_legs:
             for j in range(nz):
                 assert got_strict[tail + j] == eddsa_verify(Ed25519, sig_np[tail + j].tobytes(), b"Zcash", pk_np[tail + j].tobytes(), zip215=False), \
                     "strict-mode verdict differs from the oracle on zip215.json case %d" % j
@@ -1458,7 +1470,8 @@ def main():
     if extra:
         result["extra"] = extra
     if rank == 0:
-        result["host"] = host
+        if host:
+            result["host"] = host
         result["prewarm"] = (("%d untimed steps" % PREWARM_DIST_STEPS if dist_on else "%.0f ms of untimed steps" % (PREWARM_S * 1e3)) +
                              " before the W warm-up steps of every timed loop (boost-clock settling; the K timed steps are unchanged)")
         result["pmc"] = "live rocprofv3 passes in this run" if live else "committed profile (see roofline.traffic_source)"

@@ -32,8 +32,8 @@ def test_bench_gpus3_self_launched_as_three_gloo_ranks_prints_one_line(tmp_path)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--quick-verify",
-                        "--no-cpu-baseline", "--no-live-pmc", "--out", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1400)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1", "--full",
+                        "--quick-verify", "--no-cpu-baseline", "--no-live-pmc", "--out", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-3000:]                       # rank 0's line and nothing else on stdout

@@ -1,4 +1,4 @@
-"""Key figures of a bench.py --out file, one line per workload (A/B tooling)."""
+"""Key figures of a `bench.py --full` --out file, one line per workload (A/B tooling)."""
 import json, sys
 for f in sys.argv[1:]:
     d = json.load(open(f))

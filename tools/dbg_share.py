@@ -14,7 +14,7 @@ def patched(submit, collect, depth, steps, warmup, dist_on, check=None):
             print("[dbg]   again ms/job", round(pw2 / steps * 1e3, 4), file=sys.stderr, flush=True)
     return pw, iv
 bench.time_pipelined = patched
-sys.argv = ["bench.py", "--workload", "msm_g1", "--no-cpu-baseline", "--no-live-pmc", "--steps", "20", "--warmup", "5", "--out", "/tmp/x.json"]
+sys.argv = ["bench.py", "--workload", "msm_g1", "--full", "--no-cpu-baseline", "--no-live-pmc", "--steps", "20", "--warmup", "5", "--out", "/tmp/x.json"]
 bench.main()
 
 # ---- after bench.main(): the stand-alone share sequence of tools/share_stream_test.py in THIS process
