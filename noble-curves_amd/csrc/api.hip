@@ -114,15 +114,153 @@ struct PagedParts {
   }
 };
 
+int ncg_grow_buf(ncg_ctx* ctx, void** p, size_t* have, size_t need, size_t alloc, GrowWait wait, hipStream_t st, bool zero) {
+  if (*have >= need) return NCG_OK;
+  if (wait == GrowWait::stream) NCG_HIP(ctx, hipStreamSynchronize(st));
+  if (wait == GrowWait::device && *p) NCG_HIP(ctx, hipDeviceSynchronize());
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  *have = 0;
+  hipError_t e = hipMalloc(p, alloc);
+  if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", alloc, hipGetErrorString(e));
+  *have = alloc;
+  if (zero) NCG_HIP(ctx, hipMemsetAsync(*p, 0, alloc, st));
+  return NCG_OK;
+}
+
 static int ensure_scratch(ncg_ctx* ctx, size_t bytes) {
-  if (ctx->scratch_bytes >= bytes) return NCG_OK;
-  if (ctx->scratch) (void)hipFree(ctx->scratch);
-  ctx->scratch = nullptr;
-  ctx->scratch_bytes = 0;
-  size_t want = bytes + (bytes >> 2) + 4096;
-  hipError_t e = hipMalloc(&ctx->scratch, want);
-  if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-  ctx->scratch_bytes = want;
+  return ncg_grow_buf(ctx, &ctx->scratch, &ctx->scratch_bytes, bytes, bytes + (bytes >> 2) + 4096);
+}
+
+// One host-pointer call staged through ctx->scratch.  The caller declares its slots - in(): uploaded; out(): copied back
+// unless its host pointer is NULL, optionally zero-filled first; inout(): both, in place; dev_only(): device memory only -
+// then stage() grows the scratch once, lays the slots out at 256-byte boundaries and enqueues the uploads on ctx->stream,
+// and finish() takes the status of the _dev call, copies the outputs back and synchronises.  Once stage() has enqueued
+// anything, every exit waits for ctx->stream (the destructor), so the host memory handed to in() - temporaries included -
+// must be declared BEFORE the HostCall.
+// The slots live in ctx->scratch: a _dev form called from a host wrapper must never use ctx->scratch itself.
+// (The chunked pipelines of ncg_mul_var_batch / ncg_msm lay out the scratch on their own.)
+struct HostCall {
+  struct Slot {
+    const void* in;
+    void* out;
+    size_t bytes, off;
+    bool zero;
+  };
+  ncg_ctx* ctx;
+  PinSet pins;
+  std::vector<Slot> slots;
+  bool enqueued = false;
+  explicit HostCall(ncg_ctx* c) : ctx(c), pins(c) {}
+  ~HostCall() {
+    if (enqueued) (void)hipStreamSynchronize(ctx->stream);
+  }
+  int in(const void* host, size_t bytes) { return add(host, nullptr, bytes, false); }
+  int out(void* host, size_t bytes, bool zero = false) { return add(nullptr, host, bytes, zero); }
+  int inout(const void* in_host, void* out_host, size_t bytes) { return add(in_host, out_host, bytes, false); }
+  int dev_only(size_t bytes) { return add(nullptr, nullptr, bytes, false); }
+  template <class T = void>
+  T* dev(int i) const { return (T*)((char*)ctx->scratch + slots[i].off); }
+  int stage() {
+    size_t total = 0;
+    for (Slot& s : slots) {
+      s.off = total;
+      total += align256(s.bytes);
+    }
+    if (int rc = ensure_scratch(ctx, total)) return rc;
+    enqueued = true;
+    for (const Slot& s : slots) {
+      if (s.in && s.bytes) NCG_HIP(ctx, pins.h2d((char*)ctx->scratch + s.off, s.in, s.bytes));
+      if (s.zero) NCG_HIP(ctx, hipMemsetAsync((char*)ctx->scratch + s.off, 0, s.bytes, ctx->stream));
+    }
+    return NCG_OK;
+  }
+  int finish(int rc) {
+    if (rc) return rc;
+    for (const Slot& s : slots)
+      if (s.out && s.bytes) NCG_HIP(ctx, pins.d2h(s.out, (char*)ctx->scratch + s.off, s.bytes));
+    NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    enqueued = false;
+    return NCG_OK;
+  }
+
+ private:
+  int add(const void* in, void* out, size_t bytes, bool zero) {
+    slots.push_back(Slot{in, out, bytes, 0, zero});
+    return (int)slots.size() - 1;
+  }
+};
+
+// ---- What each operation accepts - its curves or field and its own argument rules - written once and checked by its host
+// and _dev forms alike through NCG_BEGIN.  `rc` is NCG_OK or the status already recorded; `op` names the operation in the
+// messages of the prologue.
+struct Rule {
+  const char* op;
+  int rc;
+};
+static Rule curve_rule(ncg_ctx* ctx, const char* op, int curve, bool ok) {
+  return {op, ok ? NCG_OK : set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: %s: unsupported curve %d", op, curve)};
+}
+static Rule mul_var_rule(ncg_ctx* ctx, int curve) { return curve_rule(ctx, "mul_var_batch", curve, ncg_point_bytes(curve) != 0); }
+static Rule add_pairs_rule(ncg_ctx* ctx, int curve) { return curve_rule(ctx, "add_pairs_batch", curve, ncg_point_bytes(curve) != 0); }
+static Rule mul_base_rule(ncg_ctx* ctx, int curve) {  // no fixed-base table for bn254 G1
+  return curve_rule(ctx, "mul_base_batch", curve, ncg_point_bytes(curve) != 0 && curve != NCG_BN254_G1);
+}
+static Rule normalize_rule(ncg_ctx* ctx, int curve) { return curve_rule(ctx, "normalize_batch", curve, ncg_point_bytes(curve) != 0); }
+static Rule msm_rule(ncg_ctx* ctx, int curve) { return curve_rule(ctx, "msm", curve, ncg_point_bytes(curve) != 0); }
+// the curves with a wire encoding (decode, encode and everything that takes encoded points)
+static Rule encoded_rule(ncg_ctx* ctx, const char* op, int curve) { return curve_rule(ctx, op, curve, ncg::decode_in_bytes(curve) != 0); }
+static Rule map_rule(ncg_ctx* ctx, int curve, int count) {
+  Rule r = curve_rule(ctx, "map_to_curve_batch", curve, curve == NCG_BLS12_381_G1 || curve == NCG_BLS12_381_G2);
+  if (r.rc == NCG_OK && count != 1 && count != 2)
+    r.rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: map_to_curve_batch: count must be 1 or 2");
+  return r;
+}
+static Rule secp_rule(ncg_ctx* ctx, const char* op, int curve) {
+  return {op, curve == NCG_SECP256K1 ? NCG_OK : set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: %s: secp256k1 only", op)};
+}
+static Rule ntt_rule(ncg_ctx* ctx, int field, int log2n, size_t batch) {
+  int rc = NCG_OK;
+  if (field != NCG_FIELD_BLS12_381_FR) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ntt: unsupported field %d", field);
+  else if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N)
+    rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: log2n %d out of range 0..%d", log2n, NCG_NTT_MAX_LOG2N);
+  else if (batch > 65535) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: batch %zu too large (max 65535)", batch);
+  return {"ntt", rc};
+}
+static Rule no_rule(const char* op) { return {op, NCG_OK}; }  // nothing to check beyond the prologue
+static Rule handle_rule(ncg_ctx* ctx, const char* op, const ncg_points* pts) {
+  return {op, pts && pts->ctx == ctx ? NCG_OK
+                                     : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: handle does not belong to this context", op)};
+}
+
+// the batch limit and the buffers the calling form requires, then the device
+static int batch_args(ncg_ctx* ctx, const char* op, size_t n, std::initializer_list<const void*> bufs) {
+  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: batch too large", op);
+  for (const void* p : bufs)
+    if (!p) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer", op);
+  NCG_HIP(ctx, hipSetDevice(ctx->device));
+  return NCG_OK;
+}
+// The prologue of every batch entry point, in this order: the context, the operation's rule, the empty batch (`if_empty`,
+// before any buffer is looked at), the batch limit, the buffers this form requires (`...`), hipSetDevice.
+#define NCG_BEGIN_OR(ctx, rule, n, if_empty, ...)                                     \
+  do {                                                                                \
+    if (!(ctx)) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL"); \
+    const Rule r_ = (rule);                                                           \
+    if (r_.rc) return r_.rc;                                                          \
+    if ((n) == 0) return (if_empty);                                                  \
+    if (const int rc_ = batch_args(ctx, r_.op, n, {__VA_ARGS__})) return rc_;         \
+  } while (0)
+#define NCG_BEGIN(ctx, rule, n, ...) NCG_BEGIN_OR(ctx, rule, n, NCG_OK, __VA_ARGS__)
+
+static hipStream_t stream_of(ncg_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// An empty MSM is the identity (reference curve.ts:878): written, not refused, so the output is required even then.
+static int msm_identity(ncg_ctx* ctx, int curve, void* out_affine, uint8_t* out_is_inf) {
+  if (!out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: NULL output");
+  memset(out_affine, 0, ncg_point_bytes(curve));
+  if (curve == NCG_ED25519) ((uint8_t*)out_affine)[32] = 1;  // Edwards identity is (0, 1)
+  if (out_is_inf) *out_is_inf = 1;
   return NCG_OK;
 }
 
@@ -142,21 +280,12 @@ static void msm_apply_ctx(ncg_ctx* ctx, ncg::MsmPlan& pl) {
 }
 int ncg_msm_ensure_buf(ncg_ctx* ctx, int curve, ncg::MsmPlan& pl, void** ws, size_t* ws_bytes) {
   msm_apply_ctx(ctx, pl);
-  size_t need = ncg::msm_workspace_bytes(curve, pl);
-  if (*ws_bytes < need) {
-    // ncg_msm_last_plan reads the long-run counter of the last MSM out of ITS workspace: forget the pointer when that
-    // workspace is the one being replaced (the trace then reports 0 runs instead of reading freed memory)
-    const char* lr = (const char*)ctx->msm_trace.d_long_runs;
-    if (*ws && lr && lr >= (const char*)*ws && lr < (const char*)*ws + *ws_bytes) ctx->msm_trace.d_long_runs = nullptr;
-    if (*ws) (void)hipFree(*ws);
-    *ws = nullptr;
-    *ws_bytes = 0;
-    hipError_t e = hipMalloc(ws, need);
-    if (e != hipSuccess)
-      return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: msm workspace hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-    *ws_bytes = need;
-  }
-  return NCG_OK;
+  const size_t need = ncg::msm_workspace_bytes(curve, pl);
+  // ncg_msm_last_plan reads the long-run counter of the last MSM out of ITS workspace: forget the pointer when that
+  // workspace is the one being replaced (the trace then reports 0 runs instead of reading freed memory)
+  const char* lr = (const char*)ctx->msm_trace.d_long_runs;
+  if (*ws_bytes < need && *ws && lr && lr >= (const char*)*ws && lr < (const char*)*ws + *ws_bytes) ctx->msm_trace.d_long_runs = nullptr;
+  return ncg_grow_buf(ctx, ws, ws_bytes, need, need);
 }
 static int msm_ensure_ws(ncg_ctx* ctx, int curve, ncg::MsmPlan& pl) { return ncg_msm_ensure_buf(ctx, curve, pl, &ctx->msm_ws, &ctx->msm_ws_bytes); }
 int ncg_msm_plan_ws_windows(ncg_ctx* ctx, int curve, size_t n, int w0, int cnt, ncg::MsmPlan* pl, void** ws, size_t* ws_bytes) {
@@ -166,8 +295,6 @@ int ncg_msm_plan_ws_windows(ncg_ctx* ctx, int curve, size_t n, int w0, int cnt, 
   ncg::msm_plan_take_windows(*pl, w0, cnt);
   return ncg_msm_ensure_buf(ctx, curve, *pl, ws ? ws : &ctx->msm_ws, ws_bytes ? ws_bytes : &ctx->msm_ws_bytes);
 }
-// device buffers are read with 16-byte accesses (ncg.h "Conventions"): refuse a misaligned pointer instead of faulting
-static inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
 // only the C ABI of include/ncg.h is exported (the objects are built with -fvisibility=hidden)
 #pragma GCC visibility push(default)
@@ -275,37 +402,18 @@ int ncg_sync(ncg_ctx* ctx) {
   return NCG_OK;
 }
 
+// (the fresh allocation is cleared here, so the first kernel that uses it is not the one paying for the page mappings of a
+// GB-sized buffer)
 static int ensure_mul_ws(ncg_ctx* ctx, int curve, size_t n, hipStream_t st) {
-  size_t need = ncg::mul_var_tmp_bytes(curve, (int)n);
-  if (ctx->mul_ws_bytes >= need) return NCG_OK;
-  NCG_HIP(ctx, hipStreamSynchronize(st));
-  if (ctx->mul_ws) (void)hipFree(ctx->mul_ws);
-  ctx->mul_ws = nullptr;
-  ctx->mul_ws_bytes = 0;
-  hipError_t e = hipMalloc(&ctx->mul_ws, need);
-  if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-  ctx->mul_ws_bytes = need;
-  // touch the fresh allocation once here, so the first kernel that uses it is not the one paying for
-  // the page mappings of a GB-sized buffer
-  NCG_HIP(ctx, hipMemsetAsync(ctx->mul_ws, 0, need, st));
-  return NCG_OK;
+  const size_t need = ncg::mul_var_tmp_bytes(curve, (int)n);
+  return ncg_grow_buf(ctx, &ctx->mul_ws, &ctx->mul_ws_bytes, need, need, GrowWait::stream, st, true);
 }
 
 int ncg_mul_var_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* points_affine_dev, const void* scalars_dev,
                           void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if ((curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2) && curve != NCG_BN254_G1)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_var_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!points_affine_dev || !scalars_dev || !out_affine_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch: NULL buffer");
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  {
-    int rc = ensure_mul_ws(ctx, curve, n, st);
-    if (rc) return rc;
-  }
+  NCG_BEGIN(ctx, mul_var_rule(ctx, curve), n, points_affine_dev, scalars_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_mul_ws(ctx, curve, n, st)) return rc;
   NCG_HIP(ctx, ncg::mul_var_batch(curve, (const uint32_t*)points_affine_dev, (const uint32_t*)scalars_dev,
                                   (uint32_t*)out_affine_dev, out_is_inf_dev, (int)n, (uint32_t*)ctx->mul_ws, st));
   return NCG_OK;
@@ -360,15 +468,10 @@ static hipError_t drain_copy_streams(ncg_ctx* ctx) {
 
 int ncg_mul_var_batch(ncg_ctx* ctx, int curve, size_t n, const void* points_affine, const void* scalars,
                       void* out_affine, uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_var_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!points_affine || !scalars || !out_affine)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
+  NCG_BEGIN(ctx, mul_var_rule(ctx, curve), n, points_affine, scalars, out_affine);
+  const int pb = ncg_point_bytes(curve);
   PinSet pins(ctx);
-  size_t pts_b = n * pb, sc_b = n * 32, inf_b = (n + 255) & ~(size_t)255;
+  size_t pts_b = n * pb, sc_b = n * 32, inf_b = align256(n);
   int rc = ensure_scratch(ctx, 2 * pts_b + sc_b + inf_b + 1024);
   if (rc) return rc;
   char* base = (char*)ctx->scratch;
@@ -442,17 +545,9 @@ int ncg_mul_var_batch(ncg_ctx* ctx, int curve, size_t n, const void* points_affi
 
 int ncg_add_pairs_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* a_dev, const void* b_dev, int subtract,
                             void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if ((curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2) && curve != NCG_BN254_G1)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: add_pairs_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!a_dev || !b_dev || !out_affine_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: add_pairs_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  int rc = ensure_mul_ws(ctx, curve, n, st);
-  if (rc) return rc;
+  NCG_BEGIN(ctx, add_pairs_rule(ctx, curve), n, a_dev, b_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_mul_ws(ctx, curve, n, st)) return rc;
   NCG_HIP(ctx, ncg::pair_add_batch(curve, (const uint32_t*)a_dev, (const uint32_t*)b_dev, subtract, (uint32_t*)out_affine_dev,
                                    out_is_inf_dev, (int)n, (uint32_t*)ctx->mul_ws, st));
   return NCG_OK;
@@ -460,43 +555,20 @@ int ncg_add_pairs_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* a_dev
 
 int ncg_add_pairs_batch(ncg_ctx* ctx, int curve, size_t n, const void* a, const void* b, int subtract, void* out_affine,
                         uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: add_pairs_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!a || !b || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: add_pairs_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t pts_b = n * (size_t)pb, inf_b = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, 3 * pts_b + inf_b + 1024);
-  if (rc) return rc;
-  char* d_a = (char*)ctx->scratch;
-  char* d_b = d_a + pts_b;
-  char* d_out = d_b + pts_b;
-  char* d_inf = d_out + pts_b;
-  NCG_HIP(ctx, pins.h2d(d_a, a, pts_b));
-  NCG_HIP(ctx, pins.h2d(d_b, b, pts_b));
-  rc = ncg_add_pairs_batch_dev(ctx, curve, n, d_a, d_b, subtract, d_out, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, pts_b));
-  if (out_is_inf) NCG_HIP(ctx, pins.d2h(out_is_inf, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, add_pairs_rule(ctx, curve), n, a, b, out_affine);
+  const size_t pts_b = n * (size_t)ncg_point_bytes(curve);
+  HostCall hc(ctx);
+  const int da = hc.in(a, pts_b), db = hc.in(b, pts_b);
+  const int o = hc.out(out_affine, pts_b), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_add_pairs_batch_dev(ctx, curve, n, hc.dev(da), hc.dev(db), subtract, hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
 int ncg_mul_base_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* scalars_dev, void* out_affine_dev,
                            uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve < NCG_SECP256K1 || curve > NCG_BLS12_381_G2)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_base_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!scalars_dev || !out_affine_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_base_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  int rc = ensure_mul_ws(ctx, curve, n > 8192 ? n : 8192, st);
-  if (rc) return rc;
+  NCG_BEGIN(ctx, mul_base_rule(ctx, curve), n, scalars_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_mul_ws(ctx, curve, n > 8192 ? n : 8192, st)) return rc;
   if (curve == NCG_ED25519) {  // table computed on the host (33 x 128 affine Niels points), cached per context
     if (!ctx->base_tab[curve]) {
       std::vector<uint32_t> host(ncg::ed25519_fixed_table_words());
@@ -533,27 +605,12 @@ int ncg_mul_base_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* scalar
 }
 
 int ncg_mul_base_batch(ncg_ctx* ctx, int curve, size_t n, const void* scalars, void* out_affine, uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0 || curve == NCG_BN254_G1)  // no fixed-base table for bn254 G1
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: mul_base_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!scalars || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_base_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t pts_b = n * pb, sc_b = n * 32, inf_b = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, pts_b + sc_b + inf_b + 1024);
-  if (rc) return rc;
-  char* d_out = (char*)ctx->scratch;
-  char* d_sc = d_out + pts_b;
-  char* d_inf = d_sc + sc_b;
-  NCG_HIP(ctx, pins.h2d(d_sc, scalars, sc_b));
-  rc = ncg_mul_base_batch_dev(ctx, curve, n, d_sc, d_out, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, pts_b));
-  if (out_is_inf) NCG_HIP(ctx, pins.d2h(out_is_inf, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, mul_base_rule(ctx, curve), n, scalars, out_affine);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, n * 32);
+  const int o = hc.out(out_affine, n * (size_t)ncg_point_bytes(curve)), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_mul_base_batch_dev(ctx, curve, n, hc.dev(sc), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
 // window plan the MSM entry points use for n points: out = {c, nwin, buckets per window, grouped sums per window}
@@ -594,29 +651,16 @@ int ncg_msm_last_plan(ncg_ctx* ctx, int* out8) {
 
 int ncg_msm_dev(ncg_ctx* ctx, int curve, size_t n, const void* points_affine_dev, const void* scalars_dev,
                 void* out_affine, uint8_t* out_is_inf, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: msm: unsupported curve %d", curve);
-  if (!out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: NULL output");
-  uint8_t inf_local = 0;
-  if (n == 0) {  // empty MSM is the identity (reference curve.ts:878)
-    memset(out_affine, 0, pb);
-    if (curve == NCG_ED25519) ((uint8_t*)out_affine)[32] = 1;  // Edwards identity is (0, 1)
-    if (out_is_inf) *out_is_inf = 1;
-    return NCG_OK;
-  }
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: too many points");
-  if (!points_affine_dev || !scalars_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: NULL buffer");
+  NCG_BEGIN_OR(ctx, msm_rule(ctx, curve), n, msm_identity(ctx, curve, out_affine, out_is_inf), points_affine_dev, scalars_dev,
+               out_affine);
   if (misaligned16(points_affine_dev) || misaligned16(scalars_dev))
     return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: device buffers must be 16-byte aligned");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
   ncg::MsmPlan pl;
-  int prc = ncg_msm_plan_ws(ctx, curve, n, 0, &pl);
-  if (prc) return prc;
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = ncg_msm_plan_ws(ctx, curve, n, 0, &pl)) return rc;
   uint32_t bad = 0xFFFFFFFFu;
+  uint8_t inf_local = 0;
   NCG_HIP(ctx, ncg::msm_run(curve, pl, (const uint32_t*)points_affine_dev, (const uint32_t*)scalars_dev, ctx->msm_ws,
-                            (uint32_t*)out_affine, &inf_local, st, &bad, &ctx->msm_side));
+                            (uint32_t*)out_affine, &inf_local, stream_of(ctx, stream), &bad, &ctx->msm_side));
   if (bad != 0xFFFFFFFFu)  // validateMSMScalars (curve.ts:398-404): scalars must be below the group order
     return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: invalid scalar at index %u (not below the group order)", bad);
   if (out_is_inf) *out_is_inf = inf_local;
@@ -625,16 +669,11 @@ int ncg_msm_dev(ncg_ctx* ctx, int curve, size_t n, const void* points_affine_dev
 
 int ncg_msm(ncg_ctx* ctx, int curve, size_t n, const void* points_affine, const void* scalars, void* out_affine,
             uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: msm: unsupported curve %d", curve);
-  if (n == 0) return ncg_msm_dev(ctx, curve, 0, nullptr, nullptr, out_affine, out_is_inf, nullptr);
-  if (!points_affine || !scalars || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm: too many points");
+  NCG_BEGIN_OR(ctx, msm_rule(ctx, curve), n, msm_identity(ctx, curve, out_affine, out_is_inf), points_affine, scalars, out_affine);
+  const int pb = ncg_point_bytes(curve);
   PinSet pins(ctx);
   size_t pts_b = n * pb, sc_b = n * 32;
-  const size_t pts_al = (pts_b + 255) & ~(size_t)255, sc_al = (sc_b + 255) & ~(size_t)255;
+  const size_t pts_al = align256(pts_b), sc_al = align256(sc_b);
   const size_t stored_b = n * ncg::msm_stored_words_per_point(curve) * 4;
   int rc = ensure_scratch(ctx, pts_al + sc_al + stored_b + 2048);
   if (rc) return rc;
@@ -802,32 +841,26 @@ int ncg_points_from_encoded(ncg_ctx* ctx, int curve, size_t n, const void* encod
   if (!ctx || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: points_from_encoded: NULL argument");
   *out = nullptr;
   if (out_bad_index) *out_bad_index = -1;
-  const int ib = ncg::decode_in_bytes(curve), pb = ncg_point_bytes(curve);
-  if (ib == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: points_from_encoded: unsupported curve %d", curve);
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (n && !encoded) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: points_from_encoded: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
+  if (const int rc = encoded_rule(ctx, "points_from_encoded", curve).rc) return rc;
+  if (const int rc = n ? batch_args(ctx, "points_from_encoded", n, {encoded}) : NCG_OK) return rc;
   ncg_points* h = new ncg_points{ctx, curve, n, nullptr};
   if (n) {
-    hipError_t e = hipMalloc(&h->d_pts, n * (size_t)pb);
+    const size_t pts_b = n * (size_t)ncg_point_bytes(curve);
+    hipError_t e = hipMalloc(&h->d_pts, pts_b);
     if (e != hipSuccess) {
       delete h;
-      return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", n * (size_t)pb, hipGetErrorString(e));
+      return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", pts_b, hipGetErrorString(e));
     }
     std::vector<uint8_t> ok(n);
-    const size_t in_b = (n * (size_t)ib + 255) & ~(size_t)255, fl_b = (n + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, in_b + 2 * fl_b + 1024);
-    if (rc == NCG_OK) {
-      PinSet pins(ctx);
-      char* d_in = (char*)ctx->scratch;
-      char* d_ok = d_in + in_b;
-      char* d_inf = d_ok + fl_b;
-      hipError_t e2 = pins.h2d(d_in, encoded, n * (size_t)ib);
-      if (e2 == hipSuccess)
-        rc = ncg_decode_points_batch_dev(ctx, curve, n, d_in, flags, h->d_pts, (uint8_t*)d_ok, (uint8_t*)d_inf, ctx->stream);
-      if (e2 == hipSuccess && rc == NCG_OK) e2 = pins.d2h(ok.data(), d_ok, n);
-      if (e2 == hipSuccess && rc == NCG_OK) e2 = hipStreamSynchronize(ctx->stream);
-      if (e2 != hipSuccess) rc = set_err(ctx, NCG_ERR_HIP, "noble-gpu: points_from_encoded: %s", hipGetErrorString(e2));
+    int rc;
+    {
+      HostCall hc(ctx);
+      const int in = hc.in(encoded, n * (size_t)ncg::decode_in_bytes(curve));
+      const int dok = hc.out(ok.data(), n), inf = hc.dev_only(n);
+      rc = hc.stage();
+      if (rc == NCG_OK)
+        rc = hc.finish(ncg_decode_points_batch_dev(ctx, curve, n, hc.dev(in), flags, h->d_pts, hc.dev<uint8_t>(dok),
+                                                   hc.dev<uint8_t>(inf), ctx->stream));
     }
     if (rc == NCG_OK)
       for (size_t i = 0; i < n; i++)
@@ -861,7 +894,7 @@ int ncg_points_verify_subgroup(ncg_ctx* ctx, ncg_points* h, int64_t* out_bad_ind
   // [z^2] P (G1) / [z] P (G2) by the generic (complete) batch multiply, compared with the first image
   const size_t n = h->n, pb = (size_t)ncg_point_bytes(h->curve);
   char* tmp = nullptr;
-  const size_t sc_b = (n * 32 + 255) & ~(size_t)255, out_b = (n * pb + 255) & ~(size_t)255, inf_b = (n + 255) & ~(size_t)255;
+  const size_t sc_b = align256(n * 32), out_b = align256(n * pb), inf_b = align256(n);
   hipError_t e = hipMalloc((void**)&tmp, sc_b + out_b + inf_b + 256);
   auto drop = [&]() {
     if (tmp) (void)hipFree(tmp);
@@ -978,15 +1011,6 @@ size_t ncg_points_count(const ncg_points* h) { return h ? h->n : 0; }
 int ncg_points_curve(const ncg_points* h) { return h ? h->curve : -1; }
 const void* ncg_points_dev(const ncg_points* h) { return h ? h->d_pts : nullptr; }
 
-// scalars -> the tail of the scratch buffer; returns the device address
-static int upload_scalars(ncg_ctx* ctx, PinSet& pins, size_t n, const void* scalars, char** d_sc) {
-  int rc = ensure_scratch(ctx, n * 32 + 512);
-  if (rc) return rc;
-  *d_sc = (char*)ctx->scratch;
-  NCG_HIP(ctx, pins.h2d(*d_sc, scalars, n * 32));
-  return NCG_OK;
-}
-
 }  // extern "C"
 #pragma GCC visibility pop
 // Which window plan and which device point array an MSM on a resident set uses: the precomputed levels (shared-bucket
@@ -1054,25 +1078,20 @@ static int msm_resident_core(ncg_ctx* ctx, const ncg_points* pts, const void* d_
 }
 
 int ncg_msm_resident(ncg_ctx* ctx, const ncg_points* pts, const void* scalars, void* out_affine, uint8_t* out_is_inf) {
-  if (!ctx || !pts || pts->ctx != ctx) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_resident: handle does not belong to this context");
-  if (pts->n == 0) return ncg_msm_dev(ctx, pts->curve, 0, nullptr, nullptr, out_affine, out_is_inf, nullptr);
-  if (!scalars || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_resident: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  char* d_sc = nullptr;
-  int rc = upload_scalars(ctx, pins, pts->n, scalars, &d_sc);
-  if (rc) return rc;
-  return msm_resident_core(ctx, pts, d_sc, out_affine, out_is_inf, ctx->stream);
+  NCG_BEGIN_OR(ctx, handle_rule(ctx, "msm_resident", pts), pts->n, msm_identity(ctx, pts->curve, out_affine, out_is_inf), scalars,
+               out_affine);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, pts->n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(msm_resident_core(ctx, pts, hc.dev(sc), out_affine, out_is_inf, ctx->stream));
 }
 
 int ncg_msm_resident_dev(ncg_ctx* ctx, const ncg_points* pts, const void* scalars_dev, void* out_affine, uint8_t* out_is_inf,
                          void* stream) {
-  if (!ctx || !pts || pts->ctx != ctx) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_resident: handle does not belong to this context");
-  if (pts->n == 0) return ncg_msm_dev(ctx, pts->curve, 0, nullptr, nullptr, out_affine, out_is_inf, nullptr);
-  if (!scalars_dev || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_resident: NULL buffer");
+  NCG_BEGIN_OR(ctx, handle_rule(ctx, "msm_resident", pts), pts->n, msm_identity(ctx, pts->curve, out_affine, out_is_inf), scalars_dev,
+               out_affine);
   if (misaligned16(scalars_dev)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_resident: device buffers must be 16-byte aligned");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  return msm_resident_core(ctx, pts, scalars_dev, out_affine, out_is_inf, stream ? (hipStream_t)stream : ctx->stream);
+  return msm_resident_core(ctx, pts, scalars_dev, out_affine, out_is_inf, stream_of(ctx, stream));
 }
 
 // batch multiply on a resident set, device buffers: a verified subgroup set takes the endomorphism ladders of
@@ -1097,221 +1116,107 @@ static int mul_var_resident_core(ncg_ctx* ctx, const ncg_points* pts, const void
 
 int ncg_mul_var_batch_resident_dev(ncg_ctx* ctx, const ncg_points* pts, const void* scalars_dev, void* out_affine_dev,
                                    uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx || !pts || pts->ctx != ctx) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch_resident: handle does not belong to this context");
-  if (pts->n == 0) return NCG_OK;
-  if (!scalars_dev || !out_affine_dev || !out_is_inf_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch_resident: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  return mul_var_resident_core(ctx, pts, scalars_dev, out_affine_dev, out_is_inf_dev, stream ? (hipStream_t)stream : ctx->stream);
+  NCG_BEGIN(ctx, handle_rule(ctx, "mul_var_batch_resident", pts), pts->n, scalars_dev, out_affine_dev, out_is_inf_dev);
+  return mul_var_resident_core(ctx, pts, scalars_dev, out_affine_dev, out_is_inf_dev, stream_of(ctx, stream));
 }
 
 int ncg_mul_var_batch_resident(ncg_ctx* ctx, const ncg_points* pts, const void* scalars, void* out_affine,
                                uint8_t* out_is_inf) {
-  if (!ctx || !pts || pts->ctx != ctx) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch_resident: handle does not belong to this context");
+  NCG_BEGIN(ctx, handle_rule(ctx, "mul_var_batch_resident", pts), pts->n, scalars, out_affine);
   const size_t n = pts->n;
-  if (n == 0) return NCG_OK;
-  if (!scalars || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: mul_var_batch_resident: NULL buffer");
-  const int pb = ncg_point_bytes(pts->curve);
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  const size_t sc_b = (n * 32 + 255) & ~(size_t)255, out_b = (n * (size_t)pb + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, sc_b + out_b + n + 1024);
-  if (rc) return rc;
-  char* d_sc = (char*)ctx->scratch;
-  char* d_out = d_sc + sc_b;
-  char* d_inf = d_out + out_b;
-  NCG_HIP(ctx, pins.h2d(d_sc, scalars, n * 32));
-  rc = mul_var_resident_core(ctx, pts, d_sc, d_out, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, n * (size_t)pb));
-  std::vector<uint8_t> inf_tmp;
-  uint8_t* inf_dst = out_is_inf;
-  if (!inf_dst) {
-    inf_tmp.resize(n);
-    inf_dst = inf_tmp.data();
-  }
-  NCG_HIP(ctx, pins.d2h(inf_dst, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, n * 32);
+  const int o = hc.out(out_affine, n * (size_t)ncg_point_bytes(pts->curve)), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(mul_var_resident_core(ctx, pts, hc.dev(sc), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
 // decode on the device, then sum through the MSM path with unit scalars; nothing but the encodings
 // goes up and one point (plus the verdicts) comes back
 int ncg_aggregate_encoded(ncg_ctx* ctx, int curve, size_t n, const void* encoded, int flags, void* out_affine,
                           uint8_t* out_is_inf, int64_t* out_bad_index) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  const int ib = ncg::decode_in_bytes(curve), pb = ncg_point_bytes(curve);
-  if (ib == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: aggregate_encoded: unsupported curve %d", curve);
   if (out_bad_index) *out_bad_index = -1;
-  if (n == 0) return ncg_msm_dev(ctx, curve, 0, nullptr, nullptr, out_affine, out_is_inf, nullptr);
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!encoded || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: aggregate_encoded: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
+  NCG_BEGIN_OR(ctx, encoded_rule(ctx, "aggregate_encoded", curve), n, msm_identity(ctx, curve, out_affine, out_is_inf), encoded,
+               out_affine);
   std::vector<uint8_t> ok(n);
-  const size_t in_b = (n * (size_t)ib + 255) & ~(size_t)255, pts_b = (n * (size_t)pb + 255) & ~(size_t)255,
-               sc_b = n * 32, fl_b = (n + 255) & ~(size_t)255;
-  {
-    PinSet pins(ctx);
-    int rc = ensure_scratch(ctx, in_b + pts_b + sc_b + 2 * fl_b + 2048);
-    if (rc) return rc;
-    char* d_in = (char*)ctx->scratch;
-    char* d_pts = d_in + in_b;
-    char* d_sc = d_pts + pts_b;
-    char* d_ok = d_sc + sc_b;
-    char* d_inf = d_ok + fl_b;
-    NCG_HIP(ctx, pins.h2d(d_in, encoded, n * (size_t)ib));
-    rc = ncg_decode_points_batch_dev(ctx, curve, n, d_in, flags, d_pts, (uint8_t*)d_ok, (uint8_t*)d_inf, ctx->stream);
-    if (rc) return rc;
-    NCG_HIP(ctx, hipMemsetAsync(d_sc, 0, sc_b, ctx->stream));
-    NCG_HIP(ctx, hipMemset2DAsync(d_sc, 32, 1, 1, n, ctx->stream));  // scalar 1 in every 32-byte row
-    NCG_HIP(ctx, pins.d2h(ok.data(), d_ok, n));
-    NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
+  HostCall hc(ctx);
+  const int in = hc.in(encoded, n * (size_t)ncg::decode_in_bytes(curve)), dok = hc.out(ok.data(), n);
+  const int pts = hc.dev_only(n * (size_t)ncg_point_bytes(curve)), sc = hc.dev_only(n * 32), inf = hc.dev_only(n);
+  if (int rc = hc.stage()) return rc;
+  if (int rc = ncg_decode_points_batch_dev(ctx, curve, n, hc.dev(in), flags, hc.dev(pts), hc.dev<uint8_t>(dok), hc.dev<uint8_t>(inf),
+                                           ctx->stream))
+    return rc;
+  NCG_HIP(ctx, hipMemsetAsync(hc.dev(sc), 0, n * 32, ctx->stream));
+  NCG_HIP(ctx, hipMemset2DAsync(hc.dev(sc), 32, 1, 1, n, ctx->stream));  // scalar 1 in every 32-byte row
+  if (int rc = hc.finish(NCG_OK)) return rc;
   for (size_t i = 0; i < n; i++)
     if (!ok[i]) {  // the reference throws while decoding (Point.fromBytes / assertValidity)
       if (out_bad_index) *out_bad_index = (int64_t)i;
       return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: aggregate_encoded: invalid point encoding at index %zu", i);
     }
-  char* d_pts = (char*)ctx->scratch + in_b;
-  char* d_sc = d_pts + pts_b;
-  return ncg_msm_dev(ctx, curve, n, d_pts, d_sc, out_affine, out_is_inf, ctx->stream);
+  return ncg_msm_dev(ctx, curve, n, hc.dev(pts), hc.dev(sc), out_affine, out_is_inf, ctx->stream);
 }
 
 int ncg_normalize_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* points_proj_dev, void* out_affine_dev,
                             uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (ncg_point_bytes(curve) == 0)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: normalize_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!points_proj_dev || !out_affine_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: normalize_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, normalize_rule(ctx, curve), n, points_proj_dev, out_affine_dev, out_is_inf_dev);
   NCG_HIP(ctx, ncg::normalize_batch(curve, (const uint32_t*)points_proj_dev, (uint32_t*)out_affine_dev, out_is_inf_dev,
-                                    (int)n, st));
+                                    (int)n, stream_of(ctx, stream)));
   return NCG_OK;
 }
 
 int ncg_normalize_batch(ncg_ctx* ctx, int curve, size_t n, const void* points_proj, void* out_affine,
                         uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int pb = ncg_point_bytes(curve);
-  if (pb == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: normalize_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!points_proj || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: normalize_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t in_b = n * (size_t)(pb / 2) * 3, out_b = n * (size_t)pb, inf_b = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, in_b + out_b + inf_b + 2048);
-  if (rc) return rc;
-  char* d_in = (char*)ctx->scratch;
-  char* d_out = d_in + ((in_b + 255) & ~(size_t)255);
-  char* d_inf = d_out + out_b;
-  NCG_HIP(ctx, pins.h2d(d_in, points_proj, in_b));
-  rc = ncg_normalize_batch_dev(ctx, curve, n, d_in, d_out, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, out_b));
-  if (out_is_inf) NCG_HIP(ctx, pins.d2h(out_is_inf, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, normalize_rule(ctx, curve), n, points_proj, out_affine);
+  const size_t pb = (size_t)ncg_point_bytes(curve);
+  HostCall hc(ctx);
+  const int in = hc.in(points_proj, n * (pb / 2) * 3);
+  const int o = hc.out(out_affine, n * pb), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_normalize_batch_dev(ctx, curve, n, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
 int ncg_decode_points_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* encoded_dev, int flags,
                                 void* out_affine_dev, uint8_t* out_ok_dev, uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (ncg::decode_in_bytes(curve) == 0)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: decode_points_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!encoded_dev || !out_affine_dev || !out_ok_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: decode_points_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, encoded_rule(ctx, "decode_points_batch", curve), n, encoded_dev, out_affine_dev, out_ok_dev, out_is_inf_dev);
   NCG_HIP(ctx, ncg::decode_points_batch(curve, (const uint8_t*)encoded_dev, flags, (uint32_t*)out_affine_dev, out_ok_dev,
-                                        out_is_inf_dev, (int)n, st));
+                                        out_is_inf_dev, (int)n, stream_of(ctx, stream)));
   return NCG_OK;
 }
 
 int ncg_decode_points_batch(ncg_ctx* ctx, int curve, size_t n, const void* encoded, int flags, void* out_affine,
                             uint8_t* out_ok, uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int ib = ncg::decode_in_bytes(curve), pb = ncg_point_bytes(curve);
-  if (ib == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: decode_points_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!encoded || !out_affine || !out_ok)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: decode_points_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t in_b = (n * ib + 255) & ~(size_t)255, out_b = n * (size_t)pb, fl_b = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, in_b + out_b + 2 * fl_b + 1024);
-  if (rc) return rc;
-  char* d_in = (char*)ctx->scratch;
-  char* d_out = d_in + in_b;
-  char* d_ok = d_out + out_b;
-  char* d_inf = d_ok + fl_b;
-  NCG_HIP(ctx, pins.h2d(d_in, encoded, n * ib));
-  rc = ncg_decode_points_batch_dev(ctx, curve, n, d_in, flags, d_out, (uint8_t*)d_ok, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, out_b));
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  if (out_is_inf) NCG_HIP(ctx, pins.d2h(out_is_inf, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, encoded_rule(ctx, "decode_points_batch", curve), n, encoded, out_affine, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(encoded, n * (size_t)ncg::decode_in_bytes(curve));
+  const int o = hc.out(out_affine, n * (size_t)ncg_point_bytes(curve)), ok = hc.out(out_ok, n), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decode_points_batch_dev(ctx, curve, n, hc.dev(in), flags, hc.dev(o), hc.dev<uint8_t>(ok), hc.dev<uint8_t>(f),
+                                               ctx->stream));
 }
 
 int ncg_encode_points_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* affine_dev, void* out_encoded_dev,
                                 uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (ncg::decode_in_bytes(curve) == 0)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: encode_points_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!affine_dev || !out_encoded_dev || !out_ok_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: encode_points_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  NCG_HIP(ctx, ncg::encode_points_batch(curve, (const uint32_t*)affine_dev, (uint8_t*)out_encoded_dev, out_ok_dev, (int)n, st));
+  NCG_BEGIN(ctx, encoded_rule(ctx, "encode_points_batch", curve), n, affine_dev, out_encoded_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::encode_points_batch(curve, (const uint32_t*)affine_dev, (uint8_t*)out_encoded_dev, out_ok_dev, (int)n,
+                                        stream_of(ctx, stream)));
   return NCG_OK;
 }
 
 int ncg_encode_points_batch(ncg_ctx* ctx, int curve, size_t n, const void* affine, void* out_encoded, uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  int ob = ncg::decode_in_bytes(curve), pb = ncg_point_bytes(curve);
-  if (ob == 0) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: encode_points_batch: unsupported curve %d", curve);
-  if (n == 0) return NCG_OK;
-  if (!affine || !out_encoded || !out_ok)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: encode_points_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t in_b = (n * (size_t)pb + 255) & ~(size_t)255, out_b = (n * (size_t)ob + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, in_b + out_b + n + 1024);
-  if (rc) return rc;
-  char* d_in = (char*)ctx->scratch;
-  char* d_out = d_in + in_b;
-  char* d_ok = d_out + out_b;
-  NCG_HIP(ctx, pins.h2d(d_in, affine, n * (size_t)pb));
-  rc = ncg_encode_points_batch_dev(ctx, curve, n, d_in, d_out, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_encoded, d_out, n * (size_t)ob));
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, encoded_rule(ctx, "encode_points_batch", curve), n, affine, out_encoded, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(affine, n * (size_t)ncg_point_bytes(curve));
+  const int o = hc.out(out_encoded, n * (size_t)ncg::decode_in_bytes(curve)), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_encode_points_batch_dev(ctx, curve, n, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
 int ncg_map_to_curve_batch_dev(ncg_ctx* ctx, int curve, size_t n, int count, const void* u_dev, void* out_affine_dev,
                                uint8_t* out_is_inf_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_BLS12_381_G1 && curve != NCG_BLS12_381_G2)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: map_to_curve_batch: unsupported curve %d", curve);
-  if (count != 1 && count != 2) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: map_to_curve_batch: count must be 1 or 2");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!u_dev || !out_affine_dev || !out_is_inf_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: map_to_curve_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  int rc = ensure_mul_ws(ctx, curve, n, st);  // Jacobian scratch for the batched affine conversion
-  if (rc) return rc;
+  NCG_BEGIN(ctx, map_rule(ctx, curve, count), n, u_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_mul_ws(ctx, curve, n, st)) return rc;  // Jacobian scratch for the batched affine conversion
   NCG_HIP(ctx, ncg::map_to_curve_batch(curve, (const uint32_t*)u_dev, count, (uint32_t*)out_affine_dev, out_is_inf_dev,
                                        (int)n, (uint32_t*)ctx->mul_ws, st));
   return NCG_OK;
@@ -1319,28 +1224,13 @@ int ncg_map_to_curve_batch_dev(ncg_ctx* ctx, int curve, size_t n, int count, con
 
 int ncg_map_to_curve_batch(ncg_ctx* ctx, int curve, size_t n, int count, const void* u, void* out_affine,
                            uint8_t* out_is_inf) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_BLS12_381_G1 && curve != NCG_BLS12_381_G2)
-    return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: map_to_curve_batch: unsupported curve %d", curve);
-  if (count != 1 && count != 2) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: map_to_curve_batch: count must be 1 or 2");
-  if (n == 0) return NCG_OK;
-  if (!u || !out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: map_to_curve_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  const int pb = ncg_point_bytes(curve);
-  const size_t in_b = (n * (size_t)count * (pb / 2) + 255) & ~(size_t)255, out_b = n * (size_t)pb;
-  int rc = ensure_scratch(ctx, in_b + out_b + n + 1024);
-  if (rc) return rc;
-  char* d_in = (char*)ctx->scratch;
-  char* d_out = d_in + in_b;
-  char* d_inf = d_out + out_b;
-  NCG_HIP(ctx, pins.h2d(d_in, u, n * (size_t)count * (pb / 2)));
-  rc = ncg_map_to_curve_batch_dev(ctx, curve, n, count, d_in, d_out, (uint8_t*)d_inf, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, out_b));
-  if (out_is_inf) NCG_HIP(ctx, pins.d2h(out_is_inf, d_inf, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, map_rule(ctx, curve, count), n, u, out_affine);
+  const size_t pb = (size_t)ncg_point_bytes(curve);
+  HostCall hc(ctx);
+  const int in = hc.in(u, n * (size_t)count * (pb / 2));
+  const int o = hc.out(out_affine, n * pb), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_map_to_curve_batch_dev(ctx, curve, n, count, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
 // twiddle table for (log2n, omega): built on first use, rebuilt if a different root is passed
@@ -1398,55 +1288,25 @@ static int ensure_ntt_table(ncg_ctx* ctx, int log2n, const uint32_t* omega) {
 
 int ncg_ntt_dev(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* omega, const void* in_dev, void* out_dev,
                 int flags, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (field != NCG_FIELD_BLS12_381_FR) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ntt: unsupported field %d", field);
-  if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: log2n %d out of range 0..%d", log2n, NCG_NTT_MAX_LOG2N);
-  if (batch == 0) return NCG_OK;
-  if (batch > 65535) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: batch too large");
-  if (!omega || !in_dev || !out_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: NULL buffer");
+  NCG_BEGIN(ctx, ntt_rule(ctx, field, log2n, batch), batch, omega, in_dev, out_dev);
   if (misaligned16(in_dev) || misaligned16(out_dev)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: device buffers must be 16-byte aligned");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_ntt_table(ctx, log2n, (const uint32_t*)omega);
-  if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  if (int rc = ensure_ntt_table(ctx, log2n, (const uint32_t*)omega)) return rc;
   const bool fold = ((flags >> 1) & 1) == ((flags >> 2) & 1);
   const size_t bytes = (batch << log2n) * 32;
-  if (fold && log2n > 10 && ctx->ntt_ws_bytes < bytes) {
-    if (ctx->ntt_ws) {
-      NCG_HIP(ctx, hipDeviceSynchronize());
-      (void)hipFree(ctx->ntt_ws);
-      ctx->ntt_ws = nullptr;
-      ctx->ntt_ws_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&ctx->ntt_ws, bytes);
-    if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: ntt workspace hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    ctx->ntt_ws_bytes = bytes;
+  if (fold && log2n > 10) {
+    if (int rc = ncg_grow_buf(ctx, &ctx->ntt_ws, &ctx->ntt_ws_bytes, bytes, bytes, GrowWait::device)) return rc;
   }
   NCG_HIP(ctx, ncg::ntt_run(log2n, batch, (const uint32_t*)in_dev, (uint32_t*)out_dev, (uint32_t*)ctx->ntt_ws,
-                            ctx->ntt_tab[log2n], log2n, flags, st));
+                            ctx->ntt_tab[log2n], log2n, flags, stream_of(ctx, stream)));
   return NCG_OK;
 }
 
 int ncg_ntt(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* omega, const void* in, void* out, int flags) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: log2n %d out of range 0..%d", log2n, NCG_NTT_MAX_LOG2N);
-  if (field != NCG_FIELD_BLS12_381_FR) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ntt: unsupported field %d", field);
-  if (batch == 0) return NCG_OK;
-  if (batch > 65535) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: batch %zu too large (max 65535)", batch);
-  if (!omega || !in || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  const size_t bytes = (batch << log2n) * 32;  // batch <= 2^16, log2n <= 28: below 2^49
-  int rc = ensure_scratch(ctx, bytes + 1024);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.h2d(ctx->scratch, in, bytes));
-  rc = ncg_ntt_dev(ctx, field, log2n, batch, omega, ctx->scratch, ctx->scratch, flags, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out, ctx->scratch, bytes));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, ntt_rule(ctx, field, log2n, batch), batch, omega, in, out);
+  HostCall hc(ctx);
+  const int io = hc.inout(in, out, (batch << log2n) * 32);  // batch <= 2^16, log2n <= 28: below 2^49
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ntt_dev(ctx, field, log2n, batch, omega, hc.dev(io), hc.dev(io), flags, ctx->stream));
 }
 
 static int ensure_ed_table(ncg_ctx* ctx) {
@@ -1460,17 +1320,10 @@ static int ensure_ed_table(ncg_ctx* ctx) {
 
 int ncg_ed25519_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, const void* pk32_dev,
                                  const void* k32_dev, int zip215, uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !pk32_dev || !k32_dev || !out_ok_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_ed_table(ctx);
-  if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  rc = ensure_mul_ws(ctx, NCG_ED25519, n, st);  // per-item window tables live in the multiply scratch
-  if (rc) return rc;
+  NCG_BEGIN(ctx, no_rule("ed25519_verify_batch"), n, sig64_dev, pk32_dev, k32_dev, out_ok_dev);
+  if (int rc = ensure_ed_table(ctx)) return rc;
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_mul_ws(ctx, NCG_ED25519, n, st)) return rc;  // per-item window tables live in the multiply scratch
   NCG_HIP(ctx, ncg::ed25519_verify_batch((const uint32_t*)sig64_dev, (const uint32_t*)pk32_dev,
                                          (const uint32_t*)k32_dev, ctx->ed_btab, zip215, out_ok_dev, (int)n,
                                          (uint32_t*)ctx->mul_ws, st));
@@ -1479,106 +1332,60 @@ int ncg_ed25519_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, 
 
 int ncg_ed25519_verify_batch(ncg_ctx* ctx, size_t n, const void* sig64, const void* pk32, const void* k32,
                              int zip215, uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (!sig64 || !pk32 || !k32 || !out_ok)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_batch: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  size_t okb = (n + 255) & ~(size_t)255;
-  int rc = ensure_scratch(ctx, n * 128 + okb + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_pk = d_sig + n * 64;
-  char* d_k = d_pk + n * 32;
-  char* d_ok = d_k + n * 32;
-  NCG_HIP(ctx, pins.h2d(d_sig, sig64, n * 64));
-  NCG_HIP(ctx, pins.h2d(d_pk, pk32, n * 32));
-  NCG_HIP(ctx, pins.h2d(d_k, k32, n * 32));
-  rc = ncg_ed25519_verify_batch_dev(ctx, n, d_sig, d_pk, d_k, zip215, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, no_rule("ed25519_verify_batch"), n, sig64, pk32, k32, out_ok);
+  HostCall hc(ctx);
+  const int sig = hc.in(sig64, n * 64), pk = hc.in(pk32, n * 32), k = hc.in(k32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed25519_verify_batch_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(k), zip215, hc.dev<uint8_t>(ok), ctx->stream));
 }
 
 // ---- ed25519 verify from messages: the challenge hash runs on the device too
-static int ensure_ed_ks(ncg_ctx* ctx, size_t n, hipStream_t st) {
-  const size_t need = n * 32;
-  if (ctx->ed_ks_bytes >= need) return NCG_OK;
-  NCG_HIP(ctx, hipStreamSynchronize(st));
-  if (ctx->ed_ks) (void)hipFree(ctx->ed_ks);
-  ctx->ed_ks = nullptr;
-  ctx->ed_ks_bytes = 0;
-  hipError_t e = hipMalloc(&ctx->ed_ks, need + (need >> 2));
-  if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-  ctx->ed_ks_bytes = need + (need >> 2);
-  return NCG_OK;
-}
-
 int ncg_ed25519_challenge_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, const void* pk32_dev, const void* msgs_dev,
                                     const uint64_t* msg_off_dev, void* out_k32_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !pk32_dev || !msg_off_dev || !out_k32_dev)
-    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_challenge: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, no_rule("ed25519_challenge"), n, sig64_dev, pk32_dev, msg_off_dev, out_k32_dev);
   NCG_HIP(ctx, ncg::ed25519_challenge_batch((const uint8_t*)sig64_dev, (const uint8_t*)pk32_dev, (const uint8_t*)msgs_dev,
-                                            msg_off_dev, (uint32_t*)out_k32_dev, (int)n, st));
+                                            msg_off_dev, (uint32_t*)out_k32_dev, (int)n, stream_of(ctx, stream)));
   return NCG_OK;
 }
 
 int ncg_ed25519_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, const void* pk32_dev,
                                       const void* msgs_dev, const uint64_t* msg_off_dev, int zip215, uint8_t* out_ok_dev,
                                       void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_msgs: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-  int rc = ensure_ed_ks(ctx, n, st);
-  if (rc) return rc;
-  rc = ncg_ed25519_challenge_batch_dev(ctx, n, sig64_dev, pk32_dev, msgs_dev, msg_off_dev, ctx->ed_ks, st);
-  if (rc) return rc;
+  NCG_BEGIN(ctx, no_rule("ed25519_verify_msgs"), n, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ncg_grow_buf(ctx, &ctx->ed_ks, &ctx->ed_ks_bytes, n * 32, n * 40, GrowWait::stream, st)) return rc;
+  if (int rc = ncg_ed25519_challenge_batch_dev(ctx, n, sig64_dev, pk32_dev, msgs_dev, msg_off_dev, ctx->ed_ks, st)) return rc;
   return ncg_ed25519_verify_batch_dev(ctx, n, sig64_dev, pk32_dev, ctx->ed_ks, zip215, out_ok_dev, st);
+}
+
+// The message blob of the message-taking host forms: the offsets must not decrease and a non-empty blob needs its buffer;
+// the blob goes up from its first message, with the offsets made relative to it in `rel` (declared before `hc`).
+static int stage_msgs(HostCall& hc, const char* op, size_t n, const void* msgs, const uint64_t* msg_off, std::vector<uint64_t>& rel,
+                      int* d_msg, int* d_off) {
+  for (size_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i])
+      return set_err(hc.ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: offsets must not decrease (index %zu)", op, i);
+  const size_t mbytes = (size_t)(msg_off[n] - msg_off[0]);
+  if (mbytes && !msgs) return set_err(hc.ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL message buffer", op);
+  rel.resize(n + 1);
+  for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
+  *d_off = hc.in(rel.data(), (n + 1) * 8);
+  *d_msg = hc.in(mbytes ? (const char*)msgs + msg_off[0] : nullptr, mbytes);
+  return NCG_OK;
 }
 
 int ncg_ed25519_verify_batch_msgs(ncg_ctx* ctx, size_t n, const void* sig64, const void* pk32, const void* msgs,
                                   const uint64_t* msg_off, int zip215, uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64 || !pk32 || !msg_off || !out_ok) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_msgs: NULL buffer");
-  for (size_t i = 0; i < n; i++)
-    if (msg_off[i + 1] < msg_off[i]) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_msgs: offsets must not decrease (index %zu)", i);
-  const size_t mbytes = (size_t)(msg_off[n] - msg_off[0]);
-  if (mbytes && !msgs) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed25519_verify_msgs: NULL message buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  const size_t sig_b = n * 64, pk_b = n * 32, off_b = (n + 1) * 8;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  int rc = ensure_scratch(ctx, al(sig_b) + al(pk_b) + al(off_b) + al(mbytes + 8) + al(n) + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_pk = d_sig + al(sig_b);
-  char* d_off = d_pk + al(pk_b);
-  char* d_msg = d_off + al(off_b);
-  char* d_ok = d_msg + al(mbytes + 8);
-  NCG_HIP(ctx, pins.h2d(d_sig, sig64, sig_b));
-  NCG_HIP(ctx, pins.h2d(d_pk, pk32, pk_b));
-  std::vector<uint64_t> rel(n + 1);  // offsets relative to the first message
-  for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
-  NCG_HIP(ctx, hipMemcpyAsync(d_off, rel.data(), off_b, hipMemcpyHostToDevice, ctx->stream));
-  if (mbytes) NCG_HIP(ctx, pins.h2d(d_msg, (const char*)msgs + msg_off[0], mbytes));
-  rc = ncg_ed25519_verify_batch_msgs_dev(ctx, n, d_sig, d_pk, d_msg, (const uint64_t*)d_off, zip215, (uint8_t*)d_ok,
-                                         ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, no_rule("ed25519_verify_msgs"), n, sig64, pk32, msg_off, out_ok);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int sig = hc.in(sig64, n * 64), pk = hc.in(pk32, n * 32);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed25519_verify_msgs", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed25519_verify_batch_msgs_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(msg), hc.dev<const uint64_t>(off), zip215,
+                                                     hc.dev<uint8_t>(ok), ctx->stream));
 }
 
 // ---- secp256k1 ECDSA batch verify (weierstrass.ts:1571-1620): SEC1 decode of the keys, the scalar side
@@ -1588,18 +1395,9 @@ struct SigWs {  // device buffers of the signature pipelines (ECDSA, Schnorr)
   uint8_t *pub_ok, *pub_inf, *pre_ok, *A_inf, *B_inf, *R_inf;
 };
 static int sig_ws(ncg_ctx* ctx, size_t n, hipStream_t st, SigWs* w) {
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t pt_b = al(n * 64), sc_b = al(n * 32), fl_b = al(n), pk_b = al(n * 33);
+  const size_t pt_b = align256(n * 64), sc_b = align256(n * 32), fl_b = align256(n), pk_b = align256(n * 33);
   const size_t need = 4 * pt_b + 3 * sc_b + 6 * fl_b + pk_b;
-  if (ctx->ecdsa_ws_bytes < need) {
-    NCG_HIP(ctx, hipStreamSynchronize(st));
-    if (ctx->ecdsa_ws) (void)hipFree(ctx->ecdsa_ws);
-    ctx->ecdsa_ws = nullptr;
-    ctx->ecdsa_ws_bytes = 0;
-    hipError_t e = hipMalloc(&ctx->ecdsa_ws, need + (need >> 2));
-    if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
-    ctx->ecdsa_ws_bytes = need + (need >> 2);
-  }
+  if (int rc = ncg_grow_buf(ctx, &ctx->ecdsa_ws, &ctx->ecdsa_ws_bytes, need, need + (need >> 2), GrowWait::stream, st)) return rc;
   char* p = (char*)ctx->ecdsa_ws;
   w->pub = p;    p += pt_b;
   w->A = p;      p += pt_b;
@@ -1628,26 +1426,18 @@ static int sig_mul_add(ncg_ctx* ctx, int curve, size_t n, const SigWs& w, hipStr
 
 int ncg_ecdsa_verify_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* sig64_dev, const void* hash32_dev,
                                const void* pub33_dev, int flags, uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_verify: secp256k1 only");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !hash32_dev || !pub33_dev || !out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_verify: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, secp_rule(ctx, "ecdsa_verify", curve), n, sig64_dev, hash32_dev, pub33_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
   SigWs w;
-  int rc = sig_ws(ctx, n, st, &w);
-  if (rc) return rc;
+  if (int rc = sig_ws(ctx, n, st, &w)) return rc;
   if (flags & NCG_ECDSA_PUB_UNCOMPRESSED) {  // 65-byte keys: range + curve-equation check, no square root
     NCG_HIP(ctx, ncg::secp_load_uncompressed((const uint8_t*)pub33_dev, (uint32_t*)w.pub, w.pub_ok, w.pub_inf, (int)n, st));
   } else {
-    rc = ncg_decode_points_batch_dev(ctx, curve, n, pub33_dev, 0, w.pub, w.pub_ok, w.pub_inf, st);
-    if (rc) return rc;
+    if (int rc = ncg_decode_points_batch_dev(ctx, curve, n, pub33_dev, 0, w.pub, w.pub_ok, w.pub_inf, st)) return rc;
   }
   NCG_HIP(ctx, ncg::ecdsa_prepare((const uint8_t*)sig64_dev, (const uint8_t*)hash32_dev, (int)n, (flags & NCG_ECDSA_LOW_S) != 0,
                                   (uint32_t*)w.u1, (uint32_t*)w.u2, w.pre_ok, st));
-  rc = sig_mul_add(ctx, curve, n, w, st);
-  if (rc) return rc;
+  if (int rc = sig_mul_add(ctx, curve, n, w, st)) return rc;
   NCG_HIP(ctx, ncg::ecdsa_finish((const uint8_t*)sig64_dev, (const uint32_t*)w.R, w.R_inf, w.pre_ok, w.pub_ok, w.pub_inf, (int)n,
                                  out_ok_dev, st));
   return NCG_OK;
@@ -1656,19 +1446,13 @@ int ncg_ecdsa_verify_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* si
 // Q[i] = recoverPublicKey(sig65[i], hash[i]) as an affine wire point, out_ok[i] = 0 where the reference throws
 int ncg_ecdsa_recover_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* sig65_dev, const void* hash32_dev,
                                 void* out_affine_dev, uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_recover: secp256k1 only");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig65_dev || !hash32_dev || !out_affine_dev || !out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_recover: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, secp_rule(ctx, "ecdsa_recover", curve), n, sig65_dev, hash32_dev, out_affine_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
   SigWs w;
-  int rc = sig_ws(ctx, n, st, &w);
-  if (rc) return rc;
+  if (int rc = sig_ws(ctx, n, st, &w)) return rc;
   NCG_HIP(ctx, ncg::ecdsa_recover_prepare((const uint8_t*)sig65_dev, (const uint8_t*)hash32_dev, (int)n, (uint32_t*)w.u1, (uint32_t*)w.u2,
                                           (uint8_t*)w.pub33, w.pre_ok, st));
-  rc = ncg_decode_points_batch_dev(ctx, curve, n, w.pub33, 0, w.pub, w.pub_ok, w.pub_inf, st);  // R from (x, parity)
+  int rc = ncg_decode_points_batch_dev(ctx, curve, n, w.pub33, 0, w.pub, w.pub_ok, w.pub_inf, st);  // R from (x, parity)
   if (rc) return rc;
   rc = ncg_mul_base_batch_dev(ctx, curve, n, w.u1, w.A, w.A_inf, st);
   if (rc) return rc;
@@ -1682,44 +1466,22 @@ int ncg_ecdsa_recover_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* s
 
 int ncg_ecdsa_recover_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig65, const void* hash32, void* out_affine,
                             uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_recover: secp256k1 only");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig65 || !hash32 || !out_affine || !out_ok) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_recover: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  int rc = ensure_scratch(ctx, al(n * 65) + al(n * 32) + al(n * 64) + al(n) + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_hash = d_sig + al(n * 65);
-  char* d_out = d_hash + al(n * 32);
-  char* d_ok = d_out + al(n * 64);
-  NCG_HIP(ctx, pins.h2d(d_sig, sig65, n * 65));
-  NCG_HIP(ctx, pins.h2d(d_hash, hash32, n * 32));
-  rc = ncg_ecdsa_recover_batch_dev(ctx, curve, n, d_sig, d_hash, d_out, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_affine, d_out, n * 64));
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, secp_rule(ctx, "ecdsa_recover", curve), n, sig65, hash32, out_affine, out_ok);
+  HostCall hc(ctx);
+  const int sig = hc.in(sig65, n * 65), hash = hc.in(hash32, n * 32), o = hc.out(out_affine, n * 64), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ecdsa_recover_batch_dev(ctx, curve, n, hc.dev(sig), hc.dev(hash), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
 int ncg_schnorr_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, const void* e32_dev, const void* pkx32_dev,
                                  uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !e32_dev || !pkx32_dev || !out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: schnorr_verify: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, no_rule("schnorr_verify"), n, sig64_dev, e32_dev, pkx32_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
   SigWs w;
-  int rc = sig_ws(ctx, n, st, &w);
-  if (rc) return rc;
+  if (int rc = sig_ws(ctx, n, st, &w)) return rc;
   NCG_HIP(ctx, ncg::schnorr_prepare((const uint8_t*)sig64_dev, (const uint8_t*)e32_dev, (const uint8_t*)pkx32_dev, (int)n,
                                     (uint32_t*)w.u1, (uint32_t*)w.u2, (uint8_t*)w.pub33, w.pre_ok, st));
-  rc = ncg_decode_points_batch_dev(ctx, NCG_SECP256K1, n, w.pub33, 0, w.pub, w.pub_ok, w.pub_inf, st);  // lift_x: the even root
+  int rc = ncg_decode_points_batch_dev(ctx, NCG_SECP256K1, n, w.pub33, 0, w.pub, w.pub_ok, w.pub_inf, st);  // lift_x: the even root
   if (rc) return rc;
   rc = sig_mul_add(ctx, NCG_SECP256K1, n, w, st);
   if (rc) return rc;
@@ -1732,159 +1494,90 @@ int ncg_schnorr_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, 
 // tagged challenge - then the entry points above
 int ncg_ecdsa_verify_batch_msgs_dev(ncg_ctx* ctx, int curve, size_t n, const void* sig64_dev, const void* msgs_dev,
                                     const uint64_t* msg_off_dev, const void* pub_dev, int flags, uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_verify: secp256k1 only");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !msg_off_dev || !pub_dev || !out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_verify_msgs: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, secp_rule(ctx, "ecdsa_verify_msgs", curve), n, sig64_dev, msg_off_dev, pub_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
   SigWs w;
-  int rc = sig_ws(ctx, n, st, &w);
-  if (rc) return rc;
+  if (int rc = sig_ws(ctx, n, st, &w)) return rc;
   NCG_HIP(ctx, ncg::sha256_msgs((const uint8_t*)msgs_dev, msg_off_dev, nullptr, nullptr, 0, (int)n, (uint8_t*)w.hash, st));
   return ncg_ecdsa_verify_batch_dev(ctx, curve, n, sig64_dev, w.hash, pub_dev, flags, out_ok_dev, st);
 }
 
 int ncg_schnorr_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig64_dev, const void* msgs_dev,
                                       const uint64_t* msg_off_dev, const void* pkx32_dev, uint8_t* out_ok_dev, void* stream) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64_dev || !msg_off_dev || !pkx32_dev || !out_ok_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: schnorr_verify_msgs: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+  NCG_BEGIN(ctx, no_rule("schnorr_verify_msgs"), n, sig64_dev, msg_off_dev, pkx32_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
   SigWs w;
-  int rc = sig_ws(ctx, n, st, &w);
-  if (rc) return rc;
+  if (int rc = sig_ws(ctx, n, st, &w)) return rc;
   NCG_HIP(ctx, ncg::sha256_msgs((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)sig64_dev, (const uint8_t*)pkx32_dev, 1, (int)n,
                                 (uint8_t*)w.hash, st));
   return ncg_schnorr_verify_batch_dev(ctx, n, sig64_dev, w.hash, pkx32_dev, out_ok_dev, st);
 }
 
 // host-pointer variants: mode 0 = ECDSA (keys: kb bytes per row), mode 1 = Schnorr (32-byte x-only keys)
-static int sig_verify_msgs_host(ncg_ctx* ctx, int mode, size_t n, const void* sig64, const void* msgs, const uint64_t* msg_off,
-                                const void* keys, size_t kb, int flags, uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64 || !msg_off || !keys || !out_ok) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: verify_msgs: NULL buffer");
-  for (size_t i = 0; i < n; i++)
-    if (msg_off[i + 1] < msg_off[i]) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: verify_msgs: offsets must not decrease (index %zu)", i);
-  const size_t mbytes = (size_t)(msg_off[n] - msg_off[0]);
-  if (mbytes && !msgs) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: verify_msgs: NULL message buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t off_b = (n + 1) * 8;
-  int rc = ensure_scratch(ctx, al(n * 64) + al(n * kb) + al(off_b) + al(mbytes + 8) + al(n) + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_key = d_sig + al(n * 64);
-  char* d_off = d_key + al(n * kb);
-  char* d_msg = d_off + al(off_b);
-  char* d_ok = d_msg + al(mbytes + 8);
-  NCG_HIP(ctx, pins.h2d(d_sig, sig64, n * 64));
-  NCG_HIP(ctx, pins.h2d(d_key, keys, n * kb));
-  std::vector<uint64_t> rel(n + 1);
-  for (size_t i = 0; i <= n; i++) rel[i] = msg_off[i] - msg_off[0];
-  NCG_HIP(ctx, hipMemcpyAsync(d_off, rel.data(), off_b, hipMemcpyHostToDevice, ctx->stream));
-  if (mbytes) NCG_HIP(ctx, pins.h2d(d_msg, (const char*)msgs + msg_off[0], mbytes));
-  if (mode == 0)
-    rc = ncg_ecdsa_verify_batch_msgs_dev(ctx, NCG_SECP256K1, n, d_sig, d_msg, (const uint64_t*)d_off, d_key, flags, (uint8_t*)d_ok, ctx->stream);
-  else
-    rc = ncg_schnorr_verify_batch_msgs_dev(ctx, n, d_sig, d_msg, (const uint64_t*)d_off, d_key, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));  // also keeps `rel` alive until its copy is done
-  return NCG_OK;
+static int sig_verify_msgs_host(ncg_ctx* ctx, Rule rule, int mode, size_t n, const void* sig64, const void* msgs,
+                                const uint64_t* msg_off, const void* keys, size_t kb, int flags, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, rule, n, sig64, msg_off, keys, out_ok);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int sig = hc.in(sig64, n * 64), key = hc.in(keys, n * kb);
+  int msg, off;
+  if (int rc = stage_msgs(hc, rule.op, n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  const uint64_t* d_off = hc.dev<const uint64_t>(off);
+  return hc.finish(mode == 0 ? ncg_ecdsa_verify_batch_msgs_dev(ctx, NCG_SECP256K1, n, hc.dev(sig), hc.dev(msg), d_off, hc.dev(key), flags,
+                                                               hc.dev<uint8_t>(ok), ctx->stream)
+                             : ncg_schnorr_verify_batch_msgs_dev(ctx, n, hc.dev(sig), hc.dev(msg), d_off, hc.dev(key), hc.dev<uint8_t>(ok),
+                                                                 ctx->stream));
 }
 int ncg_ecdsa_verify_batch_msgs(ncg_ctx* ctx, int curve, size_t n, const void* sig64, const void* msgs, const uint64_t* msg_off,
                                 const void* pub, int flags, uint8_t* out_ok) {
-  if (ctx && curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_verify: secp256k1 only");
-  return sig_verify_msgs_host(ctx, 0, n, sig64, msgs, msg_off, pub, (flags & NCG_ECDSA_PUB_UNCOMPRESSED) ? 65 : 33, flags, out_ok);
+  return sig_verify_msgs_host(ctx, secp_rule(ctx, "ecdsa_verify_msgs", curve), 0, n, sig64, msgs, msg_off, pub,
+                              (flags & NCG_ECDSA_PUB_UNCOMPRESSED) ? 65 : 33, flags, out_ok);
 }
 int ncg_schnorr_verify_batch_msgs(ncg_ctx* ctx, size_t n, const void* sig64, const void* msgs, const uint64_t* msg_off,
                                   const void* pkx32, uint8_t* out_ok) {
-  return sig_verify_msgs_host(ctx, 1, n, sig64, msgs, msg_off, pkx32, 32, 0, out_ok);
+  return sig_verify_msgs_host(ctx, no_rule("schnorr_verify_msgs"), 1, n, sig64, msgs, msg_off, pkx32, 32, 0, out_ok);
 }
 
 int ncg_schnorr_verify_batch(ncg_ctx* ctx, size_t n, const void* sig64, const void* e32, const void* pkx32, uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64 || !e32 || !pkx32 || !out_ok) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: schnorr_verify: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  int rc = ensure_scratch(ctx, al(n * 64) + 2 * al(n * 32) + al(n) + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_e = d_sig + al(n * 64);
-  char* d_pk = d_e + al(n * 32);
-  char* d_ok = d_pk + al(n * 32);
-  NCG_HIP(ctx, pins.h2d(d_sig, sig64, n * 64));
-  NCG_HIP(ctx, pins.h2d(d_e, e32, n * 32));
-  NCG_HIP(ctx, pins.h2d(d_pk, pkx32, n * 32));
-  rc = ncg_schnorr_verify_batch_dev(ctx, n, d_sig, d_e, d_pk, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, no_rule("schnorr_verify"), n, sig64, e32, pkx32, out_ok);
+  HostCall hc(ctx);
+  const int sig = hc.in(sig64, n * 64), e = hc.in(e32, n * 32), pk = hc.in(pkx32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_schnorr_verify_batch_dev(ctx, n, hc.dev(sig), hc.dev(e), hc.dev(pk), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
 int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64, const void* hash32, const void* pub33, int flags,
                            uint8_t* out_ok) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (curve != NCG_SECP256K1) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ecdsa_verify: secp256k1 only");
-  if (n == 0) return NCG_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: batch too large");
-  if (!sig64 || !hash32 || !pub33 || !out_ok) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_verify: NULL buffer");
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  PinSet pins(ctx);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  NCG_BEGIN(ctx, secp_rule(ctx, "ecdsa_verify", curve), n, sig64, hash32, pub33, out_ok);
   const size_t kb = (flags & NCG_ECDSA_PUB_UNCOMPRESSED) ? 65 : 33;  // bytes per key row
-  int rc = ensure_scratch(ctx, al(n * 64) + al(n * 32) + al(n * kb) + al(n) + 1024);
-  if (rc) return rc;
-  char* d_sig = (char*)ctx->scratch;
-  char* d_hash = d_sig + al(n * 64);
-  char* d_pub = d_hash + al(n * 32);
-  char* d_ok = d_pub + al(n * kb);
-  NCG_HIP(ctx, pins.h2d(d_sig, sig64, n * 64));
-  NCG_HIP(ctx, pins.h2d(d_hash, hash32, n * 32));
-  NCG_HIP(ctx, pins.h2d(d_pub, pub33, n * kb));
-  rc = ncg_ecdsa_verify_batch_dev(ctx, curve, n, d_sig, d_hash, d_pub, flags, (uint8_t*)d_ok, ctx->stream);
-  if (rc) return rc;
-  NCG_HIP(ctx, pins.d2h(out_ok, d_ok, n));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  HostCall hc(ctx);
+  const int sig = hc.in(sig64, n * 64), hash = hc.in(hash32, n * 32), pub = hc.in(pub33, n * kb), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ecdsa_verify_batch_dev(ctx, curve, n, hc.dev(sig), hc.dev(hash), hc.dev(pub), flags, hc.dev<uint8_t>(ok), ctx->stream));
 }
 
+// words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
+// Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
+// bn254 Fe9 Montgomery raw limbs 9 / 9 / 9
+static const size_t k_field_wa[10] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9}, k_field_wb[10] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9},
+                    k_field_wo[10] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9};
+static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {
+  int rc = NCG_OK;
+  if (field < 0 || field > 9) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  else if (n > (1u << 24)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: batch too large (max 2^24)");
+  return {"field_check", rc};
+}
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out) {
-  if (!ctx) return set_err(nullptr, NCG_ERR_INVALID_ARG, "noble-gpu: ctx is NULL");
-  if (field < 0 || field > 9) return set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
-  if (n == 0) return NCG_OK;
-  if (n > (1u << 24) || !a || !b || !out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: bad arguments");
-  // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
-  // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
-  // bn254 Fe9 Montgomery raw limbs 9 / 9 / 9
-  static const size_t wa[10] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9}, wb[10] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9},
-                      wo[10] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9};
-  const size_t in_wa = wa[field], in_wb = wb[field], out_w = wo[field];
-  NCG_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t in_ba = (n * in_wa * 4 + 255) & ~(size_t)255, in_bb = (n * in_wb * 4 + 255) & ~(size_t)255, out_b = n * out_w * 4;
-  int rc = ensure_scratch(ctx, in_ba + in_bb + out_b + 1024);
-  if (rc) return rc;
-  char* d_a = (char*)ctx->scratch;
-  char* d_b = d_a + in_ba;
-  char* d_o = d_b + in_bb;
-  NCG_HIP(ctx, hipMemcpyAsync(d_a, a, n * in_wa * 4, hipMemcpyHostToDevice, ctx->stream));
-  NCG_HIP(ctx, hipMemcpyAsync(d_b, b, n * in_wb * 4, hipMemcpyHostToDevice, ctx->stream));
-  NCG_HIP(ctx, hipMemsetAsync(d_o, 0, out_b, ctx->stream));
-  NCG_HIP(ctx, ncg::field_check_run(field, op, variant, (const uint32_t*)d_a, (const uint32_t*)d_b, (uint32_t*)d_o, (int)n, ctx->stream));
-  NCG_HIP(ctx, hipMemcpyAsync(out, d_o, out_b, hipMemcpyDeviceToHost, ctx->stream));
-  NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return NCG_OK;
+  NCG_BEGIN(ctx, field_rule(ctx, field, n), n, a, b, out);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * k_field_wa[field] * 4), db = hc.in(b, n * k_field_wb[field] * 4);
+  const int o = hc.out(out, n * k_field_wo[field] * 4, true);
+  if (int rc = hc.stage()) return rc;
+  NCG_HIP(ctx, ncg::field_check_run(field, op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n,
+                                    ctx->stream));
+  return hc.finish(NCG_OK);
 }
 
 int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float* out_ms) {
@@ -1904,13 +1597,8 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
     }
     NCG_HIP(ctx, hipMemcpy(ctx->ub_in, h, sizeof h, hipMemcpyHostToDevice));
   }
-  size_t words = (size_t)blocks * threads;
-  if (ctx->ub_out_words < words) {
-    if (ctx->ub_out) (void)hipFree(ctx->ub_out);
-    ctx->ub_out = nullptr;
-    NCG_HIP(ctx, hipMalloc((void**)&ctx->ub_out, words * 4));
-    ctx->ub_out_words = words;
-  }
+  const size_t bytes = (size_t)blocks * threads * 4;
+  if (int rc = ncg_grow_buf(ctx, (void**)&ctx->ub_out, &ctx->ub_out_bytes, bytes, bytes)) return rc;
   NCG_HIP(ctx, ncg::ubench_run(kind, blocks, threads, iters, ctx->ub_out, ctx->ub_in, ctx->stream, out_ms));
   return NCG_OK;
 }

@@ -136,16 +136,6 @@ struct ShardJob {
   int part = 0, nparts = 1;            // this rank's place in the exchange
 };
 
-int ensure_dev_buf(ncg_ctx* ctx, void** p, size_t* have, size_t bytes) {
-  if (*have >= bytes) return NCG_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) return set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-  *have = bytes;
-  return NCG_OK;
-}
 int ensure_land(ncg_ctx* ctx, uint32_t** p, size_t* have_words, size_t words) {
   if (*have_words >= words) return NCG_OK;
   if (*p) (void)hipHostFree(*p);
@@ -193,7 +183,8 @@ int job_local_phase(ncg_ctx* ctx, const JobRes& R, const ShardJob& J, int slot_i
   const size_t ng = (size_t)ncg::msm_ngroups(whole.c);
   const size_t fin_words = ng * (mode == ncg::SHARD_WINDOWS_SHARED ? 1 : (size_t)cnt) * xw;
   const size_t stride = ncg::msm_shard_slot_bytes(curve);  // the same on every rank, whatever its plan
-  rc = ensure_dev_buf(ctx, R.comm_buf, R.comm_buf_bytes, comm_buf_need(stride, ncg::msm_shard_max_fin_words(curve), nslots));
+  const size_t buf_b = comm_buf_need(stride, ncg::msm_shard_max_fin_words(curve), nslots);
+  rc = ncg_grow_buf(ctx, R.comm_buf, R.comm_buf_bytes, buf_b, buf_b);
   if (rc) return rc;
   const bool work = J.n_local > 0 && cnt > 0;
   if (work) {
@@ -388,8 +379,6 @@ int check_common(ncg_ctx* ctx, int curve, const void* out_affine, const char* wh
   if (!out_affine) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL output", who);
   return NCG_OK;
 }
-inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-
 }  // namespace
 
 struct ncg_multi {
@@ -610,7 +599,8 @@ int ncg_msm_shard_combine(ncg_ctx* ctx, int curve, size_t n_max, int nparts, con
   } else {
     return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: msm_shard_combine: malformed slot header (mode %u)", h0.mode);
   }
-  rc = ensure_dev_buf(ctx, R.comm_buf, R.comm_buf_bytes, comm_buf_need(stride, ncg::msm_shard_max_fin_words(curve), nparts));
+  const size_t buf_b = comm_buf_need(stride, ncg::msm_shard_max_fin_words(curve), nparts);
+  rc = ncg_grow_buf(ctx, R.comm_buf, R.comm_buf_bytes, buf_b, buf_b);
   if (rc) return rc;
   rc = ensure_land(ctx, R.land, R.land_words, (stride * (size_t)nparts + ncg::msm_shard_max_fin_words(curve) * 4) / 4 + 64);
   if (rc) return rc;
@@ -904,15 +894,8 @@ int ncg_msm_multi(ncg_multi* m, int curve, size_t n, const void* points_affine, 
     const size_t lo = std::min(n, per * (size_t)g), cnt = std::min(n, lo + per) - lo;
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(set_err(ctx, NCG_ERR_HIP, "noble-gpu: hipSetDevice failed"));
     const size_t pts_b = cnt * (size_t)pb, sc_b = cnt * 32;
-    const size_t pts_al = (pts_b + 255) & ~(size_t)255;
-    if (ctx->scratch_bytes < pts_al + sc_b + 512) {
-      if (ctx->scratch) (void)hipFree(ctx->scratch);
-      ctx->scratch = nullptr;
-      ctx->scratch_bytes = 0;
-      const size_t want = pts_al + sc_b + 4096;
-      if (hipMalloc(&ctx->scratch, want) != hipSuccess) return fail(set_err(ctx, NCG_ERR_NOMEM, "noble-gpu: hipMalloc(%zu) failed", want));
-      ctx->scratch_bytes = want;
-    }
+    const size_t pts_al = align256(pts_b);
+    if (int rc = ncg_grow_buf(ctx, &ctx->scratch, &ctx->scratch_bytes, pts_al + sc_b + 512, pts_al + sc_b + 4096)) return fail(rc);
     char* d_pts = (char*)ctx->scratch;
     char* d_sc = d_pts + pts_al;
     if (cnt) {

@@ -51,7 +51,7 @@ struct ncg_ctx {
   uint32_t* base_tab[4] = {nullptr, nullptr, nullptr, nullptr};  // fixed-base tables per curve (device)
   uint32_t* ub_in = nullptr;
   uint32_t* ub_out = nullptr;
-  size_t ub_out_words = 0;
+  size_t ub_out_bytes = 0;
   // NTT: one twiddle table per transform size (device), keyed by the root it was built from
   uint32_t* ntt_tab[NCG_NTT_MAX_LOG2N + 1] = {};
   uint32_t ntt_omega[NCG_NTT_MAX_LOG2N + 1][8] = {};
@@ -102,6 +102,18 @@ int ncg_set_err(ncg_ctx* ctx, int code, const char* fmt, ...);
 #define set_err ncg_set_err
 
 int ncg_msm_plan_ws(ncg_ctx* ctx, int curve, size_t n, int c_override, ncg::MsmPlan* pl);
+
+// Grows a device buffer of the context to hold `need` bytes, allocating `alloc` >= need (its headroom); what it held is
+// lost.  Each buffer keeps the policy it has always had: what is waited for before the old buffer is freed (`st`, or the
+// whole device for a buffer that any stream may still be reading - only when there is an old buffer), and whether the
+// fresh memory is cleared on `st`.  A failed allocation leaves the buffer empty and returns NCG_ERR_NOMEM.
+enum class GrowWait { none, stream, device };
+int ncg_grow_buf(ncg_ctx* ctx, void** p, size_t* have, size_t need, size_t alloc, GrowWait wait = GrowWait::none,
+                 hipStream_t st = nullptr, bool zero = false);
+
+// device buffers are read with 16-byte accesses (ncg.h "Conventions"): refuse a misaligned pointer instead of faulting
+inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 #define NCG_HIP(ctx, expr)                                                                   \
   do {                                                                                       \
