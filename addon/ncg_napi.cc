@@ -10,7 +10,7 @@
 //   decodePoints(curveId, encoded, zip215: bool)     -> Uint8Array n * (PB + 2)  (points, ok flags, inf flags)
 //   encodePoints(curveId, points)                    -> Uint8Array n * (EB + 1)  (encodings, ok flags)
 //   aggregateEncoded(curveId, encoded, zip215)       -> Uint8Array PB + 1 (flag); throws naming a bad index
-//   ntt(log2n, omega: Uint8Array 32, data, flags)    -> Uint8Array (same length)
+//   ntt(log2n, omega: Uint8Array 32, data, flags, field = 0) -> Uint8Array (same length); field: NCG_FIELD_* of ncg.h
 //   mapToCurve(curveId, count, u)                    -> Uint8Array n * (PB + 1)
 //   pointBytes(curveId) / version()
 // Buffers use the wire format of include/ncg.h.  Build: make -C addon  (g++ + /usr/include/node).
@@ -687,19 +687,20 @@ static napi_value EncodePoints(napi_env env, napi_callback_info info) {
 }
 
 static napi_value Ntt(napi_env env, napi_callback_info info) {
-  size_t argc = 4;
-  napi_value argv[4];
+  size_t argc = 5;
+  napi_value argv[5];
   NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   if (!need_ctx(env)) return nullptr;
-  int32_t log2n, flags = 0;
+  int32_t log2n, flags = 0, field = NCG_FIELD_BLS12_381_FR;
   uint8_t *om, *data, *out;
   size_t ol, dl;
   if (argc < 3 || napi_get_value_int32(env, argv[0], &log2n) != napi_ok || !get_u8(env, argv[1], &om, &ol) || ol != 32 ||
       !get_u8(env, argv[2], &data, &dl)) {
-    napi_throw_type_error(env, nullptr, "noble-gpu: ntt(log2n, omega32, data, flags)");
+    napi_throw_type_error(env, nullptr, "noble-gpu: ntt(log2n, omega32, data, flags, field)");
     return nullptr;
   }
   if (argc >= 4) napi_get_value_int32(env, argv[3], &flags);
+  if (argc >= 5) napi_get_value_int32(env, argv[4], &field);
   if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N || dl % ((size_t)32 << log2n)) {
     napi_throw_error(env, nullptr, "FFT: Polynomial size should be power of two");
     return nullptr;
@@ -707,7 +708,7 @@ static napi_value Ntt(napi_env env, napi_callback_info info) {
   napi_value res = make_u8(env, dl, &out);
   if (!res) return nullptr;
   size_t batch = dl / ((size_t)32 << log2n);
-  if (batch && ncg_ntt(g_ctx, NCG_FIELD_BLS12_381_FR, log2n, batch, om, data, out, flags) != 0) return throw_native(env);
+  if (batch && ncg_ntt(g_ctx, field, log2n, batch, om, data, out, flags) != 0) return throw_native(env);
   return res;
 }
 

@@ -525,14 +525,23 @@ function aggregateFromBytes(c, encodings, zip215) {
   return unmarshalPoint(c, id, out, 0, out[pb] === 1);
 }
 
-// ---- FFT over the bls12-381 scalar field: FFT(roots, Fr).direct / .inverse (fft.ts:518-577) --------
+// ---- FFT over the bls12-381 scalar field (the default) or, with opts.field = 'bn254', the bn254 scalar field:
+// FFT(roots, Fr).direct / .inverse (fft.ts:518-577) ----------------------------------------------------
 const FR = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001n;
+const FFT_FIELDS = {                            // ORDER, NCG_FIELD_* id (include/ncg.h), 2-adicity
+  bls12_381: { order: FR, id: 0, twoAdicity: 32 },
+  bn254: { order: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001n, id: 5, twoAdicity: 28 },
+};
 function powMod(b, e, m) { let r = 1n; b %= m; while (e > 0n) { if (e & 1n) r = r * b % m; b = b * b % m; e >>= 1n; } return r; }
-function fftFr(values, opts) {                  // opts: { inverse, brpInput, brpOutput, generator = 7n }
+function fftFr(values, opts) {                  // opts: { inverse, brpInput, brpOutput, generator = 7n, field = 'bls12_381' }
   opts = opts || {};
+  const fld = FFT_FIELDS[opts.field || 'bls12_381'];
+  if (!fld) throw new Error('noble-gpu: fftFr: unknown field ' + opts.field + ' (bls12_381, bn254)');
+  const FR = fld.order;
   const N = values.length;
   if (N === 0 || (N & (N - 1)) !== 0) throw new Error('FFT: Polynomial size should be power of two');
   const bits = 31 - Math.clz32(N);
+  if (bits > fld.twoAdicity) throw new Error('rootsOfUnity: wrong bits ' + bits + ' powerOfTwo=' + fld.twoAdicity);   // fft.ts:262-266
   const omega = powMod(opts.generator || 7n, (FR - 1n) >> BigInt(bits), FR);   // rootsOfUnity.omega(bits), fft.ts:238-241
   const data = new Uint8Array(N * 32), om = new Uint8Array(32);
   values.forEach((v, i) => {
@@ -541,7 +550,7 @@ function fftFr(values, opts) {                  // opts: { inverse, brpInput, br
   });
   leBytes(omega, 32, om, 0);
   init();
-  const out = native.ntt(bits, om, data, (opts.inverse ? 1 : 0) | (opts.brpInput ? 2 : 0) | (opts.brpOutput ? 4 : 0));
+  const out = native.ntt(bits, om, data, (opts.inverse ? 1 : 0) | (opts.brpInput ? 2 : 0) | (opts.brpOutput ? 4 : 0), fld.id);
   return values.map((_, i) => leNumber(out, 32 * i, 32));
 }
 

@@ -173,8 +173,14 @@ int ncg_map_to_curve_batch_dev(ncg_ctx* ctx, int curve, size_t n, int count, con
  * residues, 32 bytes little-endian.  `omega` (HOST pointer, 32 bytes, canonical) is the primitive
  * N-th root roots.omega(log2n) = G^((r-1)/N); the table roots(log2n) is built on the device at
  * first use and cached per size.  The inverse transform walks the reversed table
- * (roots.inverse, :296-304) and scales by 1/N (:568-570).  in and out may alias. */
+ * (roots.inverse, :296-304) and scales by 1/N (:568-570).  in and out may alias.
+ * field: NCG_FIELD_BLS12_381_FR (bls12_381.fields.Fr) or NCG_FIELD_BN254_FR (bn254.fields.Fr, r =
+ * 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001; the number is that of NCG_BN254_G1, whose
+ * scalars it holds).  bn254 Fr has 2-adicity 28 = NCG_NTT_MAX_LOG2N; the reference's generator for it is 5
+ * (findGenerator) or the 7 its tests pass.  The twiddle tables are cached per (field, log2n); a root of the other
+ * field is refused as not primitive.  Every other field id returns NCG_ERR_UNSUPPORTED. */
 #define NCG_FIELD_BLS12_381_FR 0
+#define NCG_FIELD_BN254_FR 5
 #define NCG_NTT_INVERSE 1
 #define NCG_NTT_BRP_INPUT 2
 #define NCG_NTT_BRP_OUTPUT 4
@@ -467,7 +473,8 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg.
  * field 8 = fr29.hpp, the bls12-381 Fr form of the NTT butterflies, RAW limbs in and out: a, b, out = 9 words each.
  * ops 0 mont(a, b), 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)),
- * 7 to_words(a) (8 words, then 0).
+ * 7 to_words(a) (8 words, then 0), 8 one fold (fr29_fold255).  `variant` 0 = bls12-381 Fr, 1 = bn254 Fr (the same
+ * ops with that field's constants; its fold is at 2^254); any other variant leaves out zero.
  * field 9 = the bn254 base field (fe9m.hpp: radix 2^29, Montgomery R = 2^261), RAW limbs in and out: a, b, out = 9 words
  * each, `variant` = 10 A + B names the operand bound types (11 12 22 23 32 17 71 33 77; a bound-B element has limbs below
  * B 2^29 and a value below 2 B p).  ops 0 a*b, 1 a^2, 2 a + b, 3 a - b, 4 -a, 5 1/a, 6 weak normalisation, 7 to wire

@@ -16,6 +16,7 @@ SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1 = 0, 1, 2, 3, 5
 POINT_BYTES = {SECP256K1: 64, ED25519: 64, BLS12_381_G1: 96, BLS12_381_G2: 192, BN254_G1: 64}
 FIELD_BYTES = {SECP256K1: 32, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 48, BN254_G1: 32}
 FIELD_BLS12_381_FR = 0
+FIELD_BN254_FR = 5
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -690,9 +691,9 @@ class Engine:
     def _ntt_flags(inverse, brp_input, brp_output):
         return (1 if inverse else 0) | (2 if brp_input else 0) | (4 if brp_output else 0)
 
-    def ntt(self, log2n, data, omega, inverse=False, brp_input=False, brp_output=False):
-        """data uint8 [batch * 2^log2n, 32] (canonical LE residues of bls12-381 Fr) -> transformed
-        copy; omega: int, the primitive 2^log2n-th root of unity (roots.omega(log2n))."""
+    def ntt(self, log2n, data, omega, inverse=False, brp_input=False, brp_output=False, field=FIELD_BLS12_381_FR):
+        """data uint8 [batch * 2^log2n, 32] (canonical LE residues of the scalar field `field`: FIELD_BLS12_381_FR or
+        FIELD_BN254_FR) -> transformed copy; omega: int, the primitive 2^log2n-th root of unity (roots.omega(log2n))."""
         data = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, 32)
         n = 1 << log2n
         if data.shape[0] % n:
@@ -700,21 +701,22 @@ class Engine:
         out = np.empty_like(data)
         om = np.frombuffer(int(omega).to_bytes(32, "little"), dtype=np.uint8).copy()
         if data.shape[0]:
-            self._check(self.lib.ncg_ntt(self.h, FIELD_BLS12_381_FR, log2n, data.shape[0] // n, om.ctypes.data,
+            self._check(self.lib.ncg_ntt(self.h, field, log2n, data.shape[0] // n, om.ctypes.data,
                                          data.ctypes.data, out.ctypes.data,
                                          self._ntt_flags(inverse, brp_input, brp_output)))
         return out
 
-    def ntt_dev(self, log2n, batch, omega, d_in, d_out, stream, inverse=False, brp_input=False, brp_output=False):
+    def ntt_dev(self, log2n, batch, omega, d_in, d_out, stream, inverse=False, brp_input=False, brp_output=False,
+                field=FIELD_BLS12_381_FR):
         om = np.frombuffer(int(omega).to_bytes(32, "little"), dtype=np.uint8).copy()
-        self._check(self.lib.ncg_ntt_dev(self.h, FIELD_BLS12_381_FR, log2n, batch, om.ctypes.data, d_in, d_out,
+        self._check(self.lib.ncg_ntt_dev(self.h, field, log2n, batch, om.ctypes.data, d_in, d_out,
                                          self._ntt_flags(inverse, brp_input, brp_output), stream))
 
     def field_check(self, field, op, variant, a_words, b_words):
         """Device field code on raw operands (ncg_field_check): a_words, b_words uint32 [n, 9] (fields 0/1),
         [n, 12] (field 2), [n, 28] (field 3: raw Fe29 limbs [a, c]), [n, 56] (field 4: lane-paired Fp2 raw limbs),
         [n, 18] (fields 5/6: fused Fe9 expressions, raw limbs [a, c] and [b, d]), a [n, 27] and b [n, 18] (field 7:
-        secp256k1 ladder pieces) or [n, 9] (field 8: fr29 raw limbs; field 9: bn254 Montgomery raw limbs) -> uint32
+        secp256k1 ladder pieces) or [n, 9] (field 8: fr29 raw limbs, variant 0 bls12-381 Fr, 1 bn254 Fr; field 9: bn254 Montgomery raw limbs) -> uint32
         [n, 8 | 8 | 12 | 12 | 24 | 9 | 9 | 27 | 9 | 9]."""
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)

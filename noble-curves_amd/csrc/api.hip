@@ -221,7 +221,7 @@ static Rule secp_rule(ncg_ctx* ctx, const char* op, int curve) {
 }
 static Rule ntt_rule(ncg_ctx* ctx, int field, int log2n, size_t batch) {
   int rc = NCG_OK;
-  if (field != NCG_FIELD_BLS12_381_FR) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ntt: unsupported field %d", field);
+  if (field != NCG_FIELD_BLS12_381_FR && field != NCG_FIELD_BN254_FR) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: ntt: unsupported field %d", field);
   else if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N)
     rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: log2n %d out of range 0..%d", log2n, NCG_NTT_MAX_LOG2N);
   else if (batch > 65535) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: batch %zu too large (max 65535)", batch);
@@ -352,8 +352,9 @@ void ncg_destroy(ncg_ctx* ctx) {
     if (ctx->base_tab[i]) (void)hipFree(ctx->base_tab[i]);
   if (ctx->ub_in) (void)hipFree(ctx->ub_in);
   if (ctx->ub_out) (void)hipFree(ctx->ub_out);
-  for (int i = 0; i <= NCG_NTT_MAX_LOG2N; i++)
-    if (ctx->ntt_tab[i]) (void)hipFree(ctx->ntt_tab[i]);
+  for (int f = 0; f < 2; f++)
+    for (int i = 0; i <= NCG_NTT_MAX_LOG2N; i++)
+      if (ctx->ntt_tab[f][i]) (void)hipFree(ctx->ntt_tab[f][i]);
   if (ctx->ntt_ws) (void)hipFree(ctx->ntt_ws);
   (void)ncg_comm_destroy(ctx);
   if (ctx->comm_buf) (void)hipFree(ctx->comm_buf);
@@ -1233,13 +1234,17 @@ int ncg_map_to_curve_batch(ncg_ctx* ctx, int curve, size_t n, int count, const v
   return hc.finish(ncg_map_to_curve_batch_dev(ctx, curve, n, count, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
-// twiddle table for (log2n, omega): built on first use, rebuilt if a different root is passed
-static int ensure_ntt_table(ncg_ctx* ctx, int log2n, const uint32_t* omega) {
-  if (ctx->ntt_tab[log2n] && memcmp(ctx->ntt_omega[log2n], omega, 32) == 0) return NCG_OK;
-  if (ctx->ntt_tab[log2n]) {
+// twiddle table for (field, log2n, omega): built on first use, rebuilt if a different root is passed; the two fields
+// keep their tables side by side
+static int ntt_field_slot(int field) { return field == NCG_FIELD_BN254_FR ? 1 : 0; }
+static int ensure_ntt_table(ncg_ctx* ctx, int field, int log2n, const uint32_t* omega) {
+  uint32_t*& slot = ctx->ntt_tab[ntt_field_slot(field)][log2n];
+  uint32_t(&slot_omega)[8] = ctx->ntt_omega[ntt_field_slot(field)][log2n];
+  if (slot && memcmp(slot_omega, omega, 32) == 0) return NCG_OK;
+  if (slot) {
     NCG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->ntt_tab[log2n]);
-    ctx->ntt_tab[log2n] = nullptr;
+    (void)hipFree(slot);
+    slot = nullptr;
   }
   uint32_t* tab = nullptr;
   void* tmp = nullptr;
@@ -1255,7 +1260,7 @@ static int ensure_ntt_table(ncg_ctx* ctx, int log2n, const uint32_t* omega) {
   alignas(16) uint32_t probe[16] = {0}, expect_tw[16] = {0};
   const int tww = ncg::ntt_tw_words();
   e = hipMemcpyAsync(d_omega, omega, 32, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = ncg::ntt_build_table(log2n, d_omega, d_small, tab, ctx->stream);
+  if (e == hipSuccess) e = ncg::ntt_build_table(field, log2n, d_omega, d_small, tab, ctx->stream);
   // primitive-root check: omega^(N/2) == -1 (N = 1: omega == 1); table entries are x 2^261 mod r
   const size_t probe_idx = log2n ? ((size_t)1 << (log2n - 1)) : 0;
   if (e == hipSuccess) e = hipMemcpyAsync(probe, tab + probe_idx * tww, (size_t)tww * 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -1265,13 +1270,15 @@ static int ensure_ntt_table(ncg_ctx* ctx, int log2n, const uint32_t* omega) {
     (void)hipFree(tab);
     return set_err(ctx, NCG_ERR_HIP, "noble-gpu: ntt table build failed: %s", hipGetErrorString(e));
   }
-  uint32_t expect[8];  // entries are x 2^261 mod r (ntt.hip): K261 for +1, r - K261 for -1
+  uint32_t expect[8];  // entries are x 2^261 mod r (ntt.hip): K261 for +1, r - K261 for -1, r and K261 of this field
+  const uint32_t *fp, *fk;
+  ncg::ntt_field_consts(field, &fp, &fk);
   if (log2n == 0) {
-    for (int i = 0; i < 8; i++) expect[i] = ncg::Fr29PR::K261[i];
+    for (int i = 0; i < 8; i++) expect[i] = fk[i];
   } else {
     uint64_t bw = 0;
     for (int i = 0; i < 8; i++) {
-      uint64_t d = (uint64_t)ncg::ParamsBlsR::P[i] - ncg::Fr29PR::K261[i] - bw;
+      uint64_t d = (uint64_t)fp[i] - fk[i] - bw;
       expect[i] = (uint32_t)d;
       bw = (d >> 32) & 1;
     }
@@ -1281,8 +1288,8 @@ static int ensure_ntt_table(ncg_ctx* ctx, int log2n, const uint32_t* omega) {
     (void)hipFree(tab);
     return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: omega is not a primitive 2^%d-th root of unity", log2n);
   }
-  ctx->ntt_tab[log2n] = tab;
-  memcpy(ctx->ntt_omega[log2n], omega, 32);
+  slot = tab;
+  memcpy(slot_omega, omega, 32);
   return NCG_OK;
 }
 
@@ -1290,14 +1297,14 @@ int ncg_ntt_dev(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* om
                 int flags, void* stream) {
   NCG_BEGIN(ctx, ntt_rule(ctx, field, log2n, batch), batch, omega, in_dev, out_dev);
   if (misaligned16(in_dev) || misaligned16(out_dev)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: device buffers must be 16-byte aligned");
-  if (int rc = ensure_ntt_table(ctx, log2n, (const uint32_t*)omega)) return rc;
+  if (int rc = ensure_ntt_table(ctx, field, log2n, (const uint32_t*)omega)) return rc;
   const bool fold = ((flags >> 1) & 1) == ((flags >> 2) & 1);
   const size_t bytes = (batch << log2n) * 32;
   if (fold && log2n > 10) {
     if (int rc = ncg_grow_buf(ctx, &ctx->ntt_ws, &ctx->ntt_ws_bytes, bytes, bytes, GrowWait::device)) return rc;
   }
-  NCG_HIP(ctx, ncg::ntt_run(log2n, batch, (const uint32_t*)in_dev, (uint32_t*)out_dev, (uint32_t*)ctx->ntt_ws,
-                            ctx->ntt_tab[log2n], log2n, flags, stream_of(ctx, stream)));
+  NCG_HIP(ctx, ncg::ntt_run(field, log2n, batch, (const uint32_t*)in_dev, (uint32_t*)out_dev, (uint32_t*)ctx->ntt_ws,
+                            ctx->ntt_tab[ntt_field_slot(field)][log2n], log2n, flags, stream_of(ctx, stream)));
   return NCG_OK;
 }
 

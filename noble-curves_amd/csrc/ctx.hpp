@@ -52,9 +52,10 @@ struct ncg_ctx {
   uint32_t* ub_in = nullptr;
   uint32_t* ub_out = nullptr;
   size_t ub_out_bytes = 0;
-  // NTT: one twiddle table per transform size (device), keyed by the root it was built from
-  uint32_t* ntt_tab[NCG_NTT_MAX_LOG2N + 1] = {};
-  uint32_t ntt_omega[NCG_NTT_MAX_LOG2N + 1][8] = {};
+  // NTT: one twiddle table per (field, transform size) (device), keyed by the root it was built from;
+  // field slot 0 = bls12-381 Fr, 1 = bn254 Fr
+  uint32_t* ntt_tab[2][NCG_NTT_MAX_LOG2N + 1] = {};
+  uint32_t ntt_omega[2][NCG_NTT_MAX_LOG2N + 1][8] = {};
   void* ntt_ws = nullptr;
   size_t ntt_ws_bytes = 0;
   // multi-GPU (comm.hip): RCCL communicator of this rank and the gather buffer of the sharded MSM

@@ -42,15 +42,16 @@ hipError_t map_to_curve_batch(int curve, const uint32_t* u, int count, uint32_t*
                               uint32_t* jac_tmp, hipStream_t st);
 void map_to_curve_host(int curve, const uint32_t* u, int count, uint32_t* out, uint8_t* inf, int n);
 
-// radix-2 NTT over bls12-381 Fr (ntt.hip)
+// radix-2 NTT over bls12-381 Fr or bn254 Fr (ntt.hip); field = NCG_FIELD_BLS12_381_FR | NCG_FIELD_BN254_FR
 size_t ntt_table_bytes(int n);
 int ntt_tw_words();
 void ntt_tw_from_canonical(const uint32_t (&w)[8], uint32_t* out);
 size_t ntt_small_bytes(int n);
-hipError_t ntt_build_table(int n, const uint32_t* d_omega, uint32_t* d_small, uint32_t* d_tab, hipStream_t st);
-hipError_t ntt_run(int n, size_t batch, const uint32_t* src, uint32_t* dst, uint32_t* ws, const uint32_t* tab,
+void ntt_field_consts(int field, const uint32_t** p, const uint32_t** k261);  // r and 2^261 mod r, 8 LE words each
+hipError_t ntt_build_table(int field, int n, const uint32_t* d_omega, uint32_t* d_small, uint32_t* d_tab, hipStream_t st);
+hipError_t ntt_run(int field, int n, size_t batch, const uint32_t* src, uint32_t* dst, uint32_t* ws, const uint32_t* tab,
                    int tab_log, int flags, hipStream_t st);
-int ntt_host(int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max = 10, int tmax = 8);
+int ntt_host(int field, int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max = 10, int tmax = 8);
 
 struct MsmPlan;
 // Optional second stream of a context: the wire -> storage conversion of the points has no consumer before

@@ -261,6 +261,43 @@ static int ht_fe9_fused_t(int op, int variant, const uint32_t* a, const uint32_t
   }
 }
 
+// fr29.hpp on RAW limbs for one field (ht_fr29_op, ht_fr29_field_op below)
+template <class F>
+static int fr29_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  Fr29 x, y, z;
+  for (int i = 0; i < 9; i++) {
+    x.v[i] = a[i];
+    y.v[i] = b ? b[i] : 0;
+    z.v[i] = 0;
+  }
+  fr29_overflows() = 0;
+  switch (op) {
+    case 0: z = fr29_mont<F>(x, y); break;
+    case 1: z = fr29_add(x, y); break;
+    case 2: z = fr29_sub<F>(x, y); break;
+    case 3: z = fr29_weak(x); break;
+    case 4: z = fr29_reduce256<F>(x); break;
+    case 5: z = fr29_cond_sub<F>(x); break;
+    case 8: z = fr29_fold255<F>(x); break;  // one fold (only through ht_fr29_field_op)
+    case 6: {
+      uint32_t w[8];
+      for (int i = 0; i < 8; i++) w[i] = a[i];
+      z = fr29_from_words(w);
+      break;
+    }
+    case 7: {
+      uint32_t w[8];
+      fr29_to_words(w, x);
+      for (int i = 0; i < 8; i++) z.v[i] = w[i];
+      z.v[8] = 0;
+      break;
+    }
+    default: return -1;
+  }
+  for (int i = 0; i < 9; i++) r[i] = z.v[i];
+  return fr29_overflows();
+}
+
 extern "C" {
 
 // field: 0 secp256k1 p, 1 ed25519 p (radix-2^29 lazy form, fe9.hpp); a, b: 9 raw limbs; r: 8 wire words
@@ -400,48 +437,32 @@ int ht_map_to_curve(int curve, const uint32_t* u, int count, uint32_t* out, uint
 
 // NTT over Fr on the CPU through the device field code (butterflies + table walk of ntt.hip)
 int ht_ntt(int n, const uint32_t* omega, const uint32_t* in, uint32_t* out, int flags) {
-  return ntt_host(n, omega, in, out, flags);  // number of column / limb overflows seen by the host checks
+  return ntt_host(NCG_FIELD_BLS12_381_FR, n, omega, in, out, flags);  // number of column / limb overflows seen by the host checks
 }
 // the same with smaller passes (first pass of at most t0max stages, the others of at most tmax)
 int ht_ntt_small_passes(int n, const uint32_t* omega, const uint32_t* in, uint32_t* out, int flags, int t0max, int tmax) {
   if (t0max < 1 || tmax < 1 || 1 + (n - (n < t0max ? n : t0max) + tmax - 1) / tmax > 8) return -1;
-  return ntt_host(n, omega, in, out, flags, t0max, tmax);
+  return ntt_host(NCG_FIELD_BLS12_381_FR, n, omega, in, out, flags, t0max, tmax);
+}
+// the two above for either field of ncg_ntt (NCG_FIELD_BLS12_381_FR, NCG_FIELD_BN254_FR); t0max = tmax = 0: the device's pass limits
+int ht_ntt_field(int field, int n, const uint32_t* omega, const uint32_t* in, uint32_t* out, int flags, int t0max, int tmax) {
+  if (field != NCG_FIELD_BLS12_381_FR && field != NCG_FIELD_BN254_FR) return -1;
+  if (t0max == 0 && tmax == 0) return ntt_host(field, n, omega, in, out, flags);
+  if (t0max < 1 || tmax < 1 || 1 + (n - (n < t0max ? n : t0max) + tmax - 1) / tmax > 8) return -1;
+  return ntt_host(field, n, omega, in, out, flags, t0max, tmax);
 }
 // fr29.hpp on RAW limbs (9 words each).  op 0: mont(a, b) -> 9 limbs; 1: a + b; 2: a + 3r - b; 3: weak(a);
 // 4: reduce256(a); 5: cond_sub(a); 6: from_words(a[0..7]); 7: to_words(a) -> 8 words.
 // Returns the overflow count of the call.
 int ht_fr29_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  Fr29 x, y, z;
-  for (int i = 0; i < 9; i++) {
-    x.v[i] = a[i];
-    y.v[i] = b ? b[i] : 0;
-    z.v[i] = 0;
-  }
-  fr29_overflows() = 0;
-  switch (op) {
-    case 0: z = fr29_mont(x, y); break;
-    case 1: z = fr29_add(x, y); break;
-    case 2: z = fr29_sub(x, y); break;
-    case 3: z = fr29_weak(x); break;
-    case 4: z = fr29_reduce256(x); break;
-    case 5: z = fr29_cond_sub(x); break;
-    case 6: {
-      uint32_t w[8];
-      for (int i = 0; i < 8; i++) w[i] = a[i];
-      z = fr29_from_words(w);
-      break;
-    }
-    case 7: {
-      uint32_t w[8];
-      fr29_to_words(w, x);
-      for (int i = 0; i < 8; i++) z.v[i] = w[i];
-      z.v[8] = 0;
-      break;
-    }
-    default: return -1;
-  }
-  for (int i = 0; i < 9; i++) r[i] = z.v[i];
-  return fr29_overflows();
+  if (op < 0 || op > 7) return -1;
+  return fr29_op_host<Fr29Bls>(op, a, b, r);
+}
+// the same for either field, numbered as ncg_field_check field 8's variant: 0 bls12-381 Fr, 1 bn254 Fr; ops 0..7 and 8 = one fold
+int ht_fr29_field_op(int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  if (variant == 0) return fr29_op_host<Fr29Bls>(op, a, b, r);
+  if (variant == 1) return fr29_op_host<Fr29Bn>(op, a, b, r);
+  return -1;
 }
 // fe9m.hpp (bn254 base field, Montgomery radix 2^29) on RAW limbs: fe9m_check (fe9m_check.hpp), the same code as
 // ncg_field_check field 9.  Returns the overflow count of the call, or -1 for an unknown op / variant.

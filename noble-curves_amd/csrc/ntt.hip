@@ -1,4 +1,7 @@
-// Radix-2 number-theoretic transform over the bls12-381 scalar field Fr.
+// Radix-2 number-theoretic transform over the bls12-381 scalar field Fr and, with the same
+// passes and index arithmetic, over the bn254 scalar field (NCG_FIELD_BN254_FR; fr29.hpp Fr29Bn): everything below that
+// touches a field element is a template over the field F (Fr29Bls / Fr29Bn), the planner, the schedule, the tiles and the
+// twiddle positions are shared.
 //
 // Reference: FFT(roots, Fr).direct / .inverse (src/abstract/fft.ts:518-577) over FFTCore
 // (:422-480) with the tables of rootsOfUnity (:230-312).  The four input/output orderings of the
@@ -30,10 +33,13 @@
 #include "fp.hpp"
 #include "fr29.hpp"
 #include "host_api.hpp"
+#include "../../include/ncg.h"
 
 namespace ncg {
 
-using Fr = Fp<ParamsBlsR>;
+using Fr = Fp<ParamsBlsR>;  // also the 8-word container of the pass code (loads, stores, word <-> limb conversion) for either field
+template <class F>
+using FrOf = Fp<typename F::M8>;  // the field the twiddle table is computed in
 
 struct NttPass {
   int n;          // log2 N
@@ -50,15 +56,17 @@ struct NttPass {
   int tshift;     // log2(table size) - n
 };
 
-NCG_DI Fr fr_load_g(const uint32_t* __restrict__ p) {
+template <class T = Fr>
+NCG_DI T fr_load_g(const uint32_t* __restrict__ p) {
   const uint4* q = reinterpret_cast<const uint4*>(p);
   uint4 a = q[0], b = q[1];
-  Fr r;
+  T r;
   r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
   r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
   return r;
 }
-NCG_DI void fr_store_g(uint32_t* __restrict__ p, const Fr& r) {
+template <class T>
+NCG_DI void fr_store_g(uint32_t* __restrict__ p, const T& r) {
   uint4* q = reinterpret_cast<uint4*>(p);
   q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
   q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
@@ -120,7 +128,8 @@ NCG_DI Fr29 ntt_load_tw(const uint32_t* __restrict__ p) {
   for (int i = 0; i < 9; i++) r.v[i] = t.v[i];
   return r;
 }
-NCG_DI void ntt_store_tw(uint32_t* __restrict__ p, const Fr& canonical) {
+template <class T>
+NCG_DI void ntt_store_tw(uint32_t* __restrict__ p, const T& canonical) {
   const Fr29 l = fr29_from_words(canonical.v);
   NttTw9 t;
 #pragma unroll
@@ -198,12 +207,12 @@ NCG_DI NttBf ntt_bf_index(const NttPass& ps, const NttTile& t, int b, int st) {
 }
 // `weak`: bring the limbs back below 2^29 + 8 on the way out (the caller tracks the limb bound: +2 per
 // stage, at most 5 going in)
-template <int E, class LDS>
+template <class F, int E, class LDS>
 NCG_DI void ntt_bf_run(LDS lds, const NttBf& bf, bool trivial, const Fr29& tw, bool weak) {
   const Fr29 a = fr29_load_l<E>(lds, bf.e0);
   Fr29 tt = fr29_load_l<E>(lds, bf.e1);
-  if (!trivial) tt = fr29_mont(tt, tw);
-  Fr29 o0 = fr29_add(a, tt), o1 = fr29_sub(a, tt);  // fft.ts:470-473
+  if (!trivial) tt = fr29_mont<F>(tt, tw);
+  Fr29 o0 = fr29_add(a, tt), o1 = fr29_sub<F>(a, tt);  // fft.ts:470-473
   if (weak) {
     o0 = fr29_weak(o0);
     o1 = fr29_weak(o1);
@@ -211,7 +220,7 @@ NCG_DI void ntt_bf_run(LDS lds, const NttBf& bf, bool trivial, const Fr29& tw, b
   fr29_store_l<E>(lds, bf.e0, o0);
   fr29_store_l<E>(lds, bf.e1, o1);
 }
-template <int E, class LDS>
+template <class F, int E, class LDS>
 NCG_DI void ntt_pass_store(LDS lds, int tid, uint32_t* __restrict__ dst, const uint32_t* __restrict__ tab,
                            const NttPass& ps, const NttTile& t) {
   Fr29 ninv;
@@ -222,9 +231,12 @@ NCG_DI void ntt_pass_store(LDS lds, int tid, uint32_t* __restrict__ dst, const u
     if (e < E) {
       size_t g = ntt_tile_index(ps, t, e);
       Fr29 v = fr29_load_l<E>(lds, e);
-      if (ps.scale) v = fr29_mont(v, ninv);  // fft.ts:568-570; below 1.5 r
-      else v = fr29_reduce256(v);            // below 1.29 * 2^255 = 1.42 r
-      if (ps.canon) v = fr29_cond_sub(v);
+      if (ps.scale) v = fr29_mont<F>(v, ninv);  // fft.ts:568-570; below 1.5 r
+      else v = fr29_reduce256<F>(v);            // below 1.29 * 2^255 = 1.42 r; bn254: below 2.71 * 2^254 = 3.58 r
+      if constexpr (F::FOLDS_2R > 2) {          // bn254: a third fold brings the canonical store below 2 r (fr29.hpp)
+        if (ps.canon && !ps.scale) v = fr29_fold255<F>(v);
+      }
+      if (ps.canon) v = fr29_cond_sub<F>(v);
       Fr o;
       fr29_to_words(o.v, v);
       if (ps.brp_store) g = ps.n ? (size_t)(ntt_brev32((uint32_t)g) >> (32 - ps.n)) : 0;
@@ -258,7 +270,7 @@ __device__ __forceinline__ void ntt_sync(bool block) {
   }
 }
 #endif
-template <int LOGE>
+template <class F, int LOGE>
 __global__ void __launch_bounds__(ntt_threads(LOGE), 8) k_ntt_pass(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                                                                   const uint32_t* __restrict__ tab, NttPass ps) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -277,11 +289,11 @@ __global__ void __launch_bounds__(ntt_threads(LOGE), 8) k_ntt_pass(const uint32_
       const NttBf bf = ntt_bf_index(ps, t, tid, st);
       Fr29 tw;
       if (!trivial) tw = ntt_load_tw(tab + (size_t)bf.pos * NTT_TW);
-      ntt_bf_run<E>(lds, bf, trivial, tw, weak);
+      ntt_bf_run<F, E>(lds, bf, trivial, tw, weak);
     }
     ntt_sync(ntt_stage_cross(ps, st) || (st + 1 < ps.T && ntt_stage_cross(ps, st + 1)));
   }
-  ntt_pass_store<E>(lds, tid, dst, tab, ps, t);
+  ntt_pass_store<F, E>(lds, tid, dst, tab, ps, t);
 #endif
 }
 
@@ -290,35 +302,41 @@ __global__ void __launch_bounds__(ntt_threads(LOGE), 8) k_ntt_pass(const uint32_
 // times the plain integer K261 = 2^261 mod r is x 2^261.
 constexpr int NTT_SPLIT = 12;
 // small[0 .. 2^lo) = omega^j ; small[2^lo .. 2^lo + 2^hi) = omega^(j 2^lo)
+template <class F>
 __global__ void k_ntt_small_tables(const uint32_t* __restrict__ omega_wire, uint32_t* __restrict__ small, int lo, int hi) {
+  using M8 = typename F::M8;
+  using Fr = FrOf<F>;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int nlo = 1 << lo, nhi = 1 << hi;
   if (t >= nlo + nhi) return;
-  Fr w = fp_to_mont<ParamsBlsR>(fr_load_g(omega_wire));
+  Fr w = fp_to_mont<M8>(fr_load_g<Fr>(omega_wire));
   uint32_t ex = t < nlo ? (uint32_t)t : (uint32_t)(t - nlo);
-  if (t >= nlo) w = fp_sqr_n<ParamsBlsR>(w, lo);
+  if (t >= nlo) w = fp_sqr_n<M8>(w, lo);
   Fr r = Fr::one();
   while (ex) {
     if (ex & 1u) r = r * w;
-    w = fp_sqr<ParamsBlsR>(w);
+    w = fp_sqr<M8>(w);
     ex >>= 1;
   }
   fr_store_g(small + (size_t)t * 8, r);
 }
+template <class F>
 __global__ void __launch_bounds__(256) k_ntt_fill_table(const uint32_t* __restrict__ small, uint32_t* __restrict__ tab,
                                                         int n, int lo) {
+  using Fr = FrOf<F>;
+  using K = typename F::K;
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t N = (size_t)1 << n;
   if (k > N) return;
   if (k == N) {  // 1/N = (1/2)^n
-    Fr h = Fr::from_const(ParamsBlsR::INV2), r = Fr::one();
+    Fr h = Fr::from_const(F::M8::INV2), r = Fr::one();
     for (int i = 0; i < n; i++) r = r * h;
-    ntt_store_tw(tab + k * NTT_TW, r * Fr::from_const(Fr29PR::K261));
+    ntt_store_tw(tab + k * NTT_TW, r * Fr::from_const(K::K261));
     return;
   }
-  const Fr a = fr_load_g(small + (k & (((size_t)1 << lo) - 1)) * 8);
-  const Fr b = fr_load_g(small + (((size_t)1 << lo) + (k >> lo)) * 8);
-  ntt_store_tw(tab + k * NTT_TW, a * b * Fr::from_const(Fr29PR::K261));
+  const Fr a = fr_load_g<Fr>(small + (k & (((size_t)1 << lo) - 1)) * 8);
+  const Fr b = fr_load_g<Fr>(small + (((size_t)1 << lo) + (k >> lo)) * 8);
+  ntt_store_tw(tab + k * NTT_TW, a * b * Fr::from_const(K::K261));
 }
 
 // host view of one table entry (for the primitive-root probe of the API layer)
@@ -336,13 +354,25 @@ size_t ntt_small_bytes(int n) {
   const int lo = n < NTT_SPLIT ? n : NTT_SPLIT, hi = n - lo;
   return (((size_t)1 << lo) + ((size_t)1 << hi)) * 32;
 }
-hipError_t ntt_build_table(int n, const uint32_t* d_omega, uint32_t* d_small, uint32_t* d_tab, hipStream_t st) {
+template <class F>
+static hipError_t ntt_build_table_t(int n, const uint32_t* d_omega, uint32_t* d_small, uint32_t* d_tab, hipStream_t st) {
   const int lo = n < NTT_SPLIT ? n : NTT_SPLIT, hi = n - lo;
   const int cnt = (1 << lo) + (1 << hi);
-  hipLaunchKernelGGL(k_ntt_small_tables, dim3((cnt + 127) / 128), dim3(128), 0, st, d_omega, d_small, lo, hi);
+  hipLaunchKernelGGL(k_ntt_small_tables<F>, dim3((cnt + 127) / 128), dim3(128), 0, st, d_omega, d_small, lo, hi);
   const size_t N1 = ((size_t)1 << n) + 1;
-  hipLaunchKernelGGL(k_ntt_fill_table, dim3((unsigned)((N1 + 255) / 256)), dim3(256), 0, st, d_small, d_tab, n, lo);
+  hipLaunchKernelGGL(k_ntt_fill_table<F>, dim3((unsigned)((N1 + 255) / 256)), dim3(256), 0, st, d_small, d_tab, n, lo);
   return hipGetLastError();
+}
+// field: NCG_FIELD_BLS12_381_FR or NCG_FIELD_BN254_FR (the API layer has refused every other id)
+hipError_t ntt_build_table(int field, int n, const uint32_t* d_omega, uint32_t* d_small, uint32_t* d_tab, hipStream_t st) {
+  if (field == NCG_FIELD_BN254_FR) return ntt_build_table_t<Fr29Bn>(n, d_omega, d_small, d_tab, st);
+  return ntt_build_table_t<Fr29Bls>(n, d_omega, d_small, d_tab, st);
+}
+// the plain integers of the field that the primitive-root probe of the API layer compares with: r and 2^261 mod r
+void ntt_field_consts(int field, const uint32_t** p, const uint32_t** k261) {
+  const bool bn = field == NCG_FIELD_BN254_FR;
+  *p = bn ? ParamsBn254R::P : ParamsBlsR::P;
+  *k261 = bn ? Fr29Bn254R::K261 : Fr29PR::K261;
 }
 
 // Stage groups, lowest first: the lowest covers up to t0max (10) stages on contiguous 2^T tiles, the others up to tmax (8)
@@ -413,15 +443,16 @@ NttSchedule ntt_schedule(int n, int tab_log, int flags, int t0max = 10, int tmax
   return sc;
 }
 
-template <int LOGE>
+template <class F, int LOGE>
 static void ntt_launch(dim3 grid, hipStream_t st, const uint32_t* in, uint32_t* out, const uint32_t* tab, const NttPass& ps) {
-  hipLaunchKernelGGL((k_ntt_pass<LOGE>), grid, dim3(ntt_threads(LOGE)), std::min((size_t)65536, (size_t)36 << LOGE), st, in, out, tab, ps);
+  hipLaunchKernelGGL((k_ntt_pass<F, LOGE>), grid, dim3(ntt_threads(LOGE)), std::min((size_t)65536, (size_t)36 << LOGE), st, in, out, tab, ps);
 }
 
 // ws: batch * N * 32 bytes (only read when the bit reversal is folded into a multi-pass transform); src may
 // equal dst.
-hipError_t ntt_run(int n, size_t batch, const uint32_t* src, uint32_t* dst, uint32_t* ws, const uint32_t* tab,
-                   int tab_log, int flags, hipStream_t st) {
+template <class F>
+static hipError_t ntt_run_t(int n, size_t batch, const uint32_t* src, uint32_t* dst, uint32_t* ws, const uint32_t* tab,
+                            int tab_log, int flags, hipStream_t st) {
   const size_t N = (size_t)1 << n;
   if (n == 0) {  // N = 1: identity (and 1/N = 1)
     if (src != dst) return hipMemcpyAsync(dst, src, batch * 32, hipMemcpyDeviceToDevice, st);
@@ -435,23 +466,28 @@ hipError_t ntt_run(int n, size_t batch, const uint32_t* src, uint32_t* dst, uint
     const int loge = ps.T + ps.logC;
     const dim3 grid((unsigned)(N >> loge), (unsigned)batch);
     switch (loge) {
-      case 1: ntt_launch<1>(grid, st, in, out, tab, ps); break;
-      case 2: ntt_launch<2>(grid, st, in, out, tab, ps); break;
-      case 3: ntt_launch<3>(grid, st, in, out, tab, ps); break;
-      case 4: ntt_launch<4>(grid, st, in, out, tab, ps); break;
-      case 5: ntt_launch<5>(grid, st, in, out, tab, ps); break;
-      case 6: ntt_launch<6>(grid, st, in, out, tab, ps); break;
-      case 7: ntt_launch<7>(grid, st, in, out, tab, ps); break;
-      case 8: ntt_launch<8>(grid, st, in, out, tab, ps); break;
-      case 9: ntt_launch<9>(grid, st, in, out, tab, ps); break;
-      case 10: ntt_launch<10>(grid, st, in, out, tab, ps); break;
+      case 1: ntt_launch<F, 1>(grid, st, in, out, tab, ps); break;
+      case 2: ntt_launch<F, 2>(grid, st, in, out, tab, ps); break;
+      case 3: ntt_launch<F, 3>(grid, st, in, out, tab, ps); break;
+      case 4: ntt_launch<F, 4>(grid, st, in, out, tab, ps); break;
+      case 5: ntt_launch<F, 5>(grid, st, in, out, tab, ps); break;
+      case 6: ntt_launch<F, 6>(grid, st, in, out, tab, ps); break;
+      case 7: ntt_launch<F, 7>(grid, st, in, out, tab, ps); break;
+      case 8: ntt_launch<F, 8>(grid, st, in, out, tab, ps); break;
+      case 9: ntt_launch<F, 9>(grid, st, in, out, tab, ps); break;
+      case 10: ntt_launch<F, 10>(grid, st, in, out, tab, ps); break;
       default: return hipErrorInvalidValue;  // ntt_plan never asks for more
     }
   }
   return hipGetLastError();
 }
+hipError_t ntt_run(int field, int n, size_t batch, const uint32_t* src, uint32_t* dst, uint32_t* ws, const uint32_t* tab,
+                   int tab_log, int flags, hipStream_t st) {
+  if (field == NCG_FIELD_BN254_FR) return ntt_run_t<Fr29Bn>(n, batch, src, dst, ws, tab, tab_log, flags, st);
+  return ntt_run_t<Fr29Bls>(n, batch, src, dst, ws, tab, tab_log, flags, st);
+}
 
-template <int LOGE>
+template <class F, int LOGE>
 static void ntt_host_pass_t(const uint32_t* in, uint32_t* out, const uint32_t* tab, const NttPass& ps,
                             std::vector<uint32_t>& lds) {
   constexpr int E = 1 << LOGE, nt = ntt_threads(LOGE);
@@ -470,25 +506,26 @@ static void ntt_host_pass_t(const uint32_t* in, uint32_t* out, const uint32_t* t
       for (int tid = 0; tid < E / 2; tid++) {
         const NttBf bf = ntt_bf_index(ps, t, tid, st);
         if (!ntt_stage_cross(ps, st) && ((bf.e0 >> 7) != (tid >> 6) || (bf.e1 >> 7) != (tid >> 6))) fr29_overflows() += 1000;
-        ntt_bf_run<E>(lds.data(), bf, ntt_stage_trivial(ps, st), ntt_load_tw(tab + (size_t)bf.pos * NTT_TW), weak);
+        ntt_bf_run<F, E>(lds.data(), bf, ntt_stage_trivial(ps, st), ntt_load_tw(tab + (size_t)bf.pos * NTT_TW), weak);
       }
     }
-    for (int tid = 0; tid < nt; tid++) ntt_pass_store<E>(lds.data(), tid, out, tab, ps, t);
+    for (int tid = 0; tid < nt; tid++) ntt_pass_store<F, E>(lds.data(), tid, out, tab, ps, t);
   }
 }
+template <class F>
 static bool ntt_host_pass(int loge, const uint32_t* in, uint32_t* out, const uint32_t* tab, const NttPass& ps,
                           std::vector<uint32_t>& lds) {
   switch (loge) {
-    case 1: ntt_host_pass_t<1>(in, out, tab, ps, lds); return true;
-    case 2: ntt_host_pass_t<2>(in, out, tab, ps, lds); return true;
-    case 3: ntt_host_pass_t<3>(in, out, tab, ps, lds); return true;
-    case 4: ntt_host_pass_t<4>(in, out, tab, ps, lds); return true;
-    case 5: ntt_host_pass_t<5>(in, out, tab, ps, lds); return true;
-    case 6: ntt_host_pass_t<6>(in, out, tab, ps, lds); return true;
-    case 7: ntt_host_pass_t<7>(in, out, tab, ps, lds); return true;
-    case 8: ntt_host_pass_t<8>(in, out, tab, ps, lds); return true;
-    case 9: ntt_host_pass_t<9>(in, out, tab, ps, lds); return true;
-    case 10: ntt_host_pass_t<10>(in, out, tab, ps, lds); return true;
+    case 1: ntt_host_pass_t<F, 1>(in, out, tab, ps, lds); return true;
+    case 2: ntt_host_pass_t<F, 2>(in, out, tab, ps, lds); return true;
+    case 3: ntt_host_pass_t<F, 3>(in, out, tab, ps, lds); return true;
+    case 4: ntt_host_pass_t<F, 4>(in, out, tab, ps, lds); return true;
+    case 5: ntt_host_pass_t<F, 5>(in, out, tab, ps, lds); return true;
+    case 6: ntt_host_pass_t<F, 6>(in, out, tab, ps, lds); return true;
+    case 7: ntt_host_pass_t<F, 7>(in, out, tab, ps, lds); return true;
+    case 8: ntt_host_pass_t<F, 8>(in, out, tab, ps, lds); return true;
+    case 9: ntt_host_pass_t<F, 9>(in, out, tab, ps, lds); return true;
+    case 10: ntt_host_pass_t<F, 10>(in, out, tab, ps, lds); return true;
   }
   return false;
 }
@@ -497,7 +534,10 @@ static bool ntt_host_pass(int loge, const uint32_t* in, uint32_t* out, const uin
 // fr29 butterflies and boundary conversions as the kernels, the threads of a block executed one after the
 // other.  t0max / tmax shrink the passes so that small transforms exercise the multi-pass paths.  Returns
 // the number of 64-bit column / 32-bit limb overflows seen by fr29.hpp's host checks (must be 0).
-int ntt_host(int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max, int tmax) {
+template <class F>
+static int ntt_host_t(int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max, int tmax) {
+  using M8 = typename F::M8;
+  using Fr = FrOf<F>;
   const size_t N = (size_t)1 << n;
   if (n == 0) {
     for (int l = 0; l < 8; l++) dst[l] = src[l];
@@ -508,15 +548,15 @@ int ntt_host(int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* d
   {
     Fr w;
     for (int i = 0; i < 8; i++) w.v[i] = omega_wire[i];
-    w = fp_to_mont<ParamsBlsR>(w);
-    const Fr k261 = Fr::from_const(Fr29PR::K261);
+    w = fp_to_mont<M8>(w);
+    const Fr k261 = Fr::from_const(F::K::K261);
     Fr acc = Fr::one();
     for (size_t k = 0; k < N; k++) {
       const Fr e = acc * k261;
       ntt_store_tw(tab.data() + k * NTT_TW, e);
       acc = acc * w;
     }
-    Fr ninv = Fr::one(), h = Fr::from_const(ParamsBlsR::INV2);
+    Fr ninv = Fr::one(), h = Fr::from_const(M8::INV2);
     for (int i = 0; i < n; i++) ninv = ninv * h;
     ninv = ninv * k261;
     ntt_store_tw(tab.data() + N * NTT_TW, ninv);
@@ -528,10 +568,14 @@ int ntt_host(int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* d
     const NttPass& ps = sc.ps[k];
     const uint32_t* in = sc.in[k] == 0 ? src : sc.in[k] == 1 ? dcopy.data() : ws.data();
     uint32_t* out = sc.out[k] == 1 ? dcopy.data() : ws.data();
-    if (!ntt_host_pass(ps.T + ps.logC, in, out, tab.data(), ps, lds)) return -1;
+    if (!ntt_host_pass<F>(ps.T + ps.logC, in, out, tab.data(), ps, lds)) return -1;
   }
   for (size_t i = 0; i < N * 8; i++) dst[i] = dcopy[i];
   return fr29_overflows();
+}
+int ntt_host(int field, int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max, int tmax) {
+  if (field == NCG_FIELD_BN254_FR) return ntt_host_t<Fr29Bn>(n, omega_wire, src, dst, flags, t0max, tmax);
+  return ntt_host_t<Fr29Bls>(n, omega_wire, src, dst, flags, t0max, tmax);
 }
 
 }  // namespace ncg

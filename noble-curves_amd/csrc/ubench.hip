@@ -373,8 +373,9 @@ __global__ void __launch_bounds__(64) k_field_check_secp_ladder(int op, const ui
     r[18 + j] = R.Z.v[j];
   }
 }
-// fr29.hpp (the NTT butterflies' form of bls12-381 Fr) on RAW limbs, ops numbered as hosttest.hip's ht_fr29_op: 0 mont(a, b),
-// 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)), 7 to_words(a) (8 words, then 0).
+// fr29.hpp (the NTT butterflies' form of bls12-381 Fr, variant 0, or bn254 Fr, variant 1) on RAW limbs, ops numbered as
+// hosttest.hip's ht_fr29_op: 0 mont(a, b), 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a),
+// 6 from_words(a[0..8)), 7 to_words(a) (8 words, then 0), 8 one fold.
 // a, b, out: 9 words per item, so that the tests check the output limbs as well as the value.
 // fe9m.hpp (the bn254 base field, Montgomery radix 2^29) on RAW limbs: fe9m_check (fe9m_check.hpp, the host twin's code);
 // a, b, out: 9 words per item.
@@ -390,6 +391,7 @@ __global__ void __launch_bounds__(64) k_field_check_fe9m(int op, int variant, co
   fe9m_check(op, variant, x, y, r);
   for (int j = 0; j < 9; j++) out[(size_t)i * 9 + j] = r[j];
 }
+template <class F>
 __global__ void __launch_bounds__(64) k_field_check_fr29(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                          uint32_t* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -404,12 +406,13 @@ __global__ void __launch_bounds__(64) k_field_check_fr29(int op, const uint32_t*
     z.v[j] = 0;
   }
   switch (op) {
-    case 0: z = fr29_mont(x, y); break;
+    case 0: z = fr29_mont<F>(x, y); break;
     case 1: z = fr29_add(x, y); break;
-    case 2: z = fr29_sub(x, y); break;
+    case 2: z = fr29_sub<F>(x, y); break;
     case 3: z = fr29_weak(x); break;
-    case 4: z = fr29_reduce256(x); break;
-    case 5: z = fr29_cond_sub(x); break;
+    case 4: z = fr29_reduce256<F>(x); break;
+    case 5: z = fr29_cond_sub<F>(x); break;
+    case 8: z = fr29_fold255<F>(x); break;
     case 6: {
       uint32_t w[8];
 #pragma unroll
@@ -441,7 +444,9 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 5) hipLaunchKernelGGL(k_field_check_fused<Fe9SecpPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 6) hipLaunchKernelGGL(k_field_check_fused<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 7) hipLaunchKernelGGL(k_field_check_secp_ladder, grid, block, 0, st, op, d_a, d_b, d_out, n);
-  else if (field == 8) hipLaunchKernelGGL(k_field_check_fr29, grid, block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 8 && variant == 0) hipLaunchKernelGGL(k_field_check_fr29<Fr29Bls>, grid, block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 8 && variant == 1) hipLaunchKernelGGL(k_field_check_fr29<Fr29Bn>, grid, block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 8) return hipSuccess;  // unknown variant: out stays zero
   else if (field == 9) hipLaunchKernelGGL(k_field_check_fe9m, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else return hipErrorInvalidValue;
   return hipGetLastError();

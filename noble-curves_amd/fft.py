@@ -1,7 +1,7 @@
-"""Host mirror of the reference's FFT interface for the bls12-381 scalar field
+"""Host mirror of the reference's FFT interface for the bls12-381 and bn254 scalar fields
 (src/abstract/fft.ts): `rootsOfUnity(Fr, 7)` / `FFT(roots, Fr).direct|inverse(values, brpInput,
 brpOutput)` with the same names, argument meaning and error messages; the transform itself runs in
-`libncg.so` (`ncg_ntt`).  The host side only does what the reference does once per field: the
+`libncg.so` (`ncg_ntt`, field NCG_FIELD_BLS12_381_FR or NCG_FIELD_BN254_FR by the ORDER of the field).  The host side only does what the reference does once per field: the
 2-adic chain of primitive roots (:238-241) - a handful of modular exponentiations.
 """
 import numpy as np
@@ -12,20 +12,27 @@ from ._native import get_engine
 BLS12_381_FR_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
 
+BN254_FR_ORDER = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+
+
 class _Fr:
     """The slice of IField (src/abstract/modular.ts:429-607) the FFT front end touches."""
-    ORDER = BLS12_381_FR_ORDER
-    BITS = 255
     BYTES = 32
     ONE = 1
     ZERO = 0
 
-    @staticmethod
-    def pow(a, e):
-        return pow(a, e, BLS12_381_FR_ORDER)
+    def __init__(self, order):
+        self.ORDER = order
+        self.BITS = order.bit_length()
+
+    def pow(self, a, e):
+        return pow(a, e, self.ORDER)
 
 
-bls12_381_Fr = _Fr()
+bls12_381_Fr = _Fr(BLS12_381_FR_ORDER)
+bn254_Fr = _Fr(BN254_FR_ORDER)
+# ORDER -> field id of ncg_ntt (include/ncg.h)
+_DEVICE_FIELDS = {BLS12_381_FR_ORDER: _native.FIELD_BLS12_381_FR, BN254_FR_ORDER: _native.FIELD_BN254_FR}
 
 
 def isPowerOfTwo(x):                       # fft.ts:56-59
@@ -57,11 +64,11 @@ def bitReversalPermutation(values):        # fft.ts:136-171 (copying form)
 
 
 class RootsOfUnity:
-    """fft.ts:230-312 for a field whose ORDER matches the device field (bls12-381 Fr)."""
+    """fft.ts:230-312 for a field whose ORDER matches a device field (bls12-381 Fr, bn254 Fr)."""
 
     def __init__(self, field, generator=None):
-        if getattr(field, "ORDER", None) != BLS12_381_FR_ORDER:
-            raise ValueError("noble-gpu: the device NTT is built for the bls12-381 scalar field only")
+        if getattr(field, "ORDER", None) not in _DEVICE_FIELDS:
+            raise ValueError("noble-gpu: the device NTT is built for the bls12-381 and bn254 scalar fields only")
         if generator is not None and (not isinstance(generator, int) or isinstance(generator, bool)):
             raise TypeError('"generator" expected bigint, got type=' + type(generator).__name__)
         odd, p2 = field.ORDER - 1, 0
@@ -144,7 +151,8 @@ class FFT:
                     raise ValueError("invalid field element: outside of range 0..ORDER")
             data = _native.ints_to_le(values, 32)
         eng = self._engine or get_engine()
-        out = eng.ntt(bits, data, self.roots.omega(bits), inverse=inverse, brp_input=brpInput, brp_output=brpOutput)
+        out = eng.ntt(bits, data, self.roots.omega(bits), inverse=inverse, brp_input=brpInput, brp_output=brpOutput,
+                      field=_DEVICE_FIELDS[order])
         return out if raw else _native.le_to_ints(out, 32)
 
     def direct(self, values, brpInput=False, brpOutput=False):

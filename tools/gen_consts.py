@@ -241,6 +241,42 @@ def main():
     out += "  static constexpr uint32_t G1[24] = {%s};\n" % wire([g1x, g1y], 12)
     out += "  static constexpr uint32_t G2[48] = {%s};\n" % wire(g2, 12)
     out += "};\n\n"
+    # bn254 scalar field Fr for the NTT (src/bn254.ts bn254_Fr; src/abstract/fft.ts): the 8 x 32-bit Montgomery field of the
+    # table builder, and the radix-2^29 form of the butterflies (fr29.hpp, Fr29Bn).  r = 2^28 + 1 (mod 2^29), so
+    # -r^-1 = 2^28 - 1 (mod 2^29): the Montgomery quotient digit of a column t is ((t & 1) << 28) - t, and q r[0] is a real
+    # term of every column.  C254 = 2^254 - r folds the bits at and above 2^254 (r has 254 bits); BIAS = 3 r with limbs 0..7
+    # in [2^29, 2^30); K261 and ONE as for bls12-381.
+    bn_r = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
+    assert bn_r.bit_length() == 254 and (bn_r - 1) % (1 << 28) == 0 and (bn_r - 1) % (1 << 29) != 0   # 2-adicity 28
+    assert bn_r % (1 << 29) == (1 << 28) + 1 and (-pow(bn_r, -1, 1 << 29)) % (1 << 29) == (1 << 28) - 1
+    for t in (0, 1, 2, 3, m29, m29 - 1, 0x12345678 & m29):                     # the quotient digit cancels the low limb
+        q = (((t & 1) << 28) - t) % (1 << 29)
+        assert (t + q * (bn_r & m29)) % (1 << 29) == 0
+    assert pow(5, (bn_r - 1) // 2, bn_r) == bn_r - 1 and pow(7, (bn_r - 1) // 2, bn_r) == bn_r - 1      # non-residues
+    assert all(pow(g, (bn_r - 1) // 2, bn_r) == 1 for g in (2, 3, 4))           # findGenerator stops at 5
+    # columns of fr29_mont: 9 products of a limb below 6 * 2^29 (limb 8: 2^32) with an exact limb, 9 of q with a limb of r
+    assert (8 * 6 + 8) * (1 << 58) + sum(limbs29(bn_r, 9)) * (1 << 29) + (1 << 36) < (1 << 64)
+    # a pass: values below 2^256 in, + 3 r per stage, 10 stages; two folds at 2^254 come below 2^256, three below 2 r
+    c254 = (1 << 254) - bn_r
+    top = (1 << 256) + 30 * bn_r
+    assert top < (1 << 259)
+    f1 = (1 << 254) + (top >> 254) * c254
+    f2 = (1 << 254) + (f1 >> 254) * c254
+    f3 = (1 << 254) + (f2 >> 254) * c254
+    assert f2 < (1 << 256) and f2 >= 2 * bn_r and f3 < 2 * bn_r
+    assert top * bn_r // (1 << 261) + bn_r < 5 * bn_r // 4                     # a product stays below 1.25 r
+    rest = 3 * bn_r - low
+    assert rest > 0
+    bias = [((rest >> (29 * i)) & m29) + (1 << 29) for i in range(8)] + [rest >> 232]
+    assert sum(b << (29 * i) for i, b in enumerate(bias)) == 3 * bn_r
+    assert all((1 << 29) <= b < (1 << 30) for b in bias[:8]) and bias[8] > (5 * bn_r // 4) >> 232
+    out += field("ParamsBn254R", bn_r, 8, {"INV2": (bn_r + 1) // 2})
+    out += "struct Fr29Bn254R {\n"
+    out += arr29("P", bn_r, 9) + arr29("C254", c254, 9)
+    out += "  static constexpr uint32_t BIAS[9] = {%s};  // 3 r\n" % ", ".join("0x%08xu" % b for b in bias)
+    out += arr("K261", (1 << 261) % bn_r, 8)
+    out += arr29("ONE", (1 << 261) % bn_r, 9)
+    out += "};\n\n"
     out += "}  // namespace ncg\n"
     with open(OUT, "w") as f:
         f.write(out)
