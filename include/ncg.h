@@ -480,6 +480,22 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * B 2^29 and a value below 2 B p).  ops 0 a*b, 1 a^2, 2 a + b, 3 a - b, 4 -a, 5 1/a, 6 weak normalisation, 7 to wire
  * (8 canonical LE words of a / R, then 0), 8 from wire (a[0..8) canonical LE words -> a R).  An op the bounds do not admit
  * leaves out zero.
+ * fields 3 / 4, op 7 = the zero test f_eqz (fe29.hpp) of the element a of the row (the row widths stay; c and b are ignored) taken
+ * as Fe29<A> / the lane-paired Fe29x2P<A>, `variant` = A, one of the bounds the group law instantiates it at: 4 (xyzz_add: the
+ * difference of two products), 66 (xyzz_madd: a product minus a stored coordinate), 128 (CoopXyzz::add: two values read back
+ * as stored coordinates).  out[0] = 1 when the value is j p with j < A (both halves, on field 4), else 0; any other A leaves
+ * out zero.
+ * fields 10-14 = the group law the MSM runs on its buckets, on STORED words (csrc/group_check.hpp): 10 MsmGroup<CurveSecp>
+ * (Fe9, FW = 9 words per coordinate), 11 MsmGroup<CurveEd> (extended accumulators / affine Niels inputs, FW = 9), 12
+ * MsmGroup<CurveG1> (Fe29, FW = 14), 13 MsmGroup<CurveG2P> (lane-paired Fp2, FW = 28: c0 then c1, two lanes per row), 14
+ * MsmGroup<CurveBn254> (Fe9 Montgomery, FW = 9).  Every row of a, b and out is ACC_WORDS = 4 FW raw words in the layout of
+ * acc_load / acc_store - X Y ZZ ZZZ (ed25519: X Y Z T), Montgomery form included, nothing converted; an all-zero row is the
+ * identity.  For ops 0 / 1 the row of b starts with a stored input point in aff_load's layout (x y: 2 FW words; ed25519:
+ * y + x, y - x, 2 d x y: 3 FW words) and the rest of it is ignored.  ops 0 madd(a, b, false), 1 madd(a, b, true) (a - b),
+ * 2 add(a, b), 3 dbl(a).  Fields 12 / 13 also take the four-lane form of msm_coop.hpp (device only; one group of four items per
+ * row, blocks of 64 lanes): 8 CoopXyzz::add(a, b) -> out, 9 the same with out aliasing a (the row is copied to out, then added
+ * in place), 10 with out aliasing b, 11 CoopXyzz::dbl(a) -> out, 12 dbl in place, 13 CoopXyzz::copy; on the other fields ops
+ * 8-13 leave out zero, as does any other op.  `variant` is ignored.
  * bn254 G1 (NCG_BN254_G1) takes the MSM (every entry point, resident / precomputed / async / split / sharded), the batch
  * variable-base multiply, the pairwise add and normalize_batch; the reference has no byte format for it, so decode /
  * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch

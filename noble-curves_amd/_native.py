@@ -717,14 +717,21 @@ class Engine:
         [n, 12] (field 2), [n, 28] (field 3: raw Fe29 limbs [a, c]), [n, 56] (field 4: lane-paired Fp2 raw limbs),
         [n, 18] (fields 5/6: fused Fe9 expressions, raw limbs [a, c] and [b, d]), a [n, 27] and b [n, 18] (field 7:
         secp256k1 ladder pieces) or [n, 9] (field 8: fr29 raw limbs, variant 0 bls12-381 Fr, 1 bn254 Fr; field 9: bn254 Montgomery raw limbs) -> uint32
-        [n, 8 | 8 | 12 | 12 | 24 | 9 | 9 | 27 | 9 | 9]."""
+        [n, 8 | 8 | 12 | 12 | 24 | 9 | 9 | 27 | 9 | 9].  Fields 3 / 4, op 7: out[:, 0] = f_eqz of the element a taken at the value bound
+        `variant` (4, 66 or 128: the bounds under the branches of the group law), the rest zero.
+        Fields 10-14: the group law of the MSM buckets on STORED accumulators (secp256k1, ed25519, bls12-381 G1, lane-paired G2,
+        bn254 G1): a, b and the result [n, 36 | 36 | 56 | 112 | 36] raw words in acc_load's layout (for ops 0 / 1 b starts with a
+        stored input point).  ops 0 madd(a, b), 1 madd(a, -b), 2 add, 3 dbl; fields 12 / 13 also the four-lane form: 8 add, 9 / 10
+        add with out aliasing a / b, 11 dbl, 12 dbl in place, 13 copy (elsewhere those leave out zero)."""
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)
         n = a.shape[0]
-        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18)}.get(field, (9, 9))
+        acc = {10: 36, 11: 36, 12: 56, 13: 112, 14: 36}
+        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18),
+                  **{f: (w, w) for f, w in acc.items()}}.get(field, (9, 9))
         if a.shape != (n, wa) or b.shape != (n, wb):   # the library reads n * wa and n * wb words
             raise ValueError("field_check: field %d takes a [n, %d] and b [n, %d]" % (field, wa, wb))
-        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9}.get(field, 8)), dtype=np.uint32)
+        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, **acc}.get(field, 8)), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_field_check(self.h, field, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out

@@ -1567,12 +1567,14 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
 
 // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
 // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
-// bn254 Fe9 Montgomery raw limbs 9 / 9 / 9
-static const size_t k_field_wa[10] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9}, k_field_wb[10] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9},
-                    k_field_wo[10] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9};
+// bn254 Fe9 Montgomery raw limbs 9 / 9 / 9; the MSM groups (fields 10-14: secp256k1, ed25519, bls12-381 G1, lane-paired G2, bn254 G1):
+// one stored accumulator, 4 FW words, for each of a, b and out
+static const size_t k_field_wa[15] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36},
+                    k_field_wb[15] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36},
+                    k_field_wo[15] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36};
 static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {
   int rc = NCG_OK;
-  if (field < 0 || field > 9) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 14) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   else if (n > (1u << 24)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: batch too large (max 2^24)");
   return {"field_check", rc};
 }

@@ -14,6 +14,7 @@
 #include "ecdsa.hip"
 #include "msm_shard.hpp"
 #include "fe9m_check.hpp"
+#include "group_check.hpp"
 
 using namespace ncg;
 
@@ -470,6 +471,37 @@ int ht_fe9m_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32
   fe9m_overflows() = 0;
   if (fe9m_check(op, variant, a, b, r) != 0) return -1;
   return fe9m_overflows();
+}
+// the group law of the MSM buckets on STORED words (group_check.hpp, the code of ncg_field_check fields 10-14): field 10 secp256k1,
+// 11 ed25519, 12 bls12-381 G1, 13 G2, 14 bn254 G1; ops 0-3; a, b, out: ACC_WORDS raw words.  Field 13 runs the UNPAIRED Fp2 form
+// (CurveG2: the lane-paired products exist on the device only); the stored layout is the same, c0 then c1.
+int ht_group_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (op < 0 || op > 3) return -1;
+  switch (field) {
+    case 10: group_check_op<CurveSecp>(op, a, b, out); return 0;
+    case 11: group_check_op<CurveEd>(op, a, b, out); return 0;
+    case 12: group_check_op<CurveG1>(op, a, b, out); return 0;
+    case 13: group_check_op<CurveG2>(op, a, b, out); return 0;
+    case 14: group_check_op<CurveBn254>(op, a, b, out); return 0;
+  }
+  return -1;
+}
+// f_eqz of raw limbs at the bound A (4, 66 or 128: group_check.hpp): 14 limbs as Fe29<A>, or - paired - 28 limbs c0, c1.  No host
+// case emulates pair_swap (on the host it is the identity), so the paired twin takes the two halves through the unpaired
+// Fe29x2<A>, whose verdict is the and of the halves as well.  Returns 0 / 1, or -1 for an unknown bound.
+int ht_fe29_eqz(int paired, int A, const uint32_t* a) {
+  const int z0 = fe29_eqz_check<Fe29>(A, a);
+  if (!paired || z0 < 0) return z0;
+  auto half = [&](auto x, int h) {
+    for (int i = 0; i < 14; i++) x.v[i] = a[14 * h + i];
+    return x;
+  };
+  switch (A) {
+    case 4: return f_eqz(Fe29x2<4>(half(Fe29<4>(), 0), half(Fe29<4>(), 1))) ? 1 : 0;
+    case 66: return f_eqz(Fe29x2<66>(half(Fe29<66>(), 0), half(Fe29<66>(), 1))) ? 1 : 0;
+    case 128: return f_eqz(Fe29x2<128>(half(Fe29<128>(), 0), half(Fe29<128>(), 1))) ? 1 : 0;
+  }
+  return -1;
 }
 // the pass schedule of ntt_run (the shipped ntt_schedule with the device's pass limits and table): 11 ints per pass,
 // T logC colhi dit inverse brp_store scale canon s_lo in out (buffers 0 src, 1 dst, 2 ws); returns the number of passes

@@ -5,6 +5,8 @@
 #include "fp29.hpp"
 #include "fr29.hpp"
 #include "fe9m_check.hpp"
+#include "group_check.hpp"
+#include "msm_coop.hpp"
 
 namespace ncg {
 
@@ -239,7 +241,7 @@ __device__ __forceinline__ Fe29<B> fe29_raw(const uint32_t* p) {
   for (int i = 0; i < 14; i++) r.v[i] = p[i];
   return r;
 }
-__global__ void __launch_bounds__(64) k_field_check_fe29raw(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+__global__ void __launch_bounds__(64) k_field_check_fe29raw(int op, int variant, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                             uint32_t* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -249,10 +251,15 @@ __global__ void __launch_bounds__(64) k_field_check_fe29raw(int op, const uint32
     case 0: fe29_to_wire(r, fe29_raw<4096>(pa) * fe29_raw<4096>(pb)); break;
     case 1: fe29_to_wire(r, f_sqr(fe29_raw<4096>(pa))); break;
     case 6: fe29_to_wire(r, f_mulsub(fe29_raw<4096>(pa), fe29_raw<2048>(pb), fe29_raw<4096>(pa + 14), fe29_raw<2048>(pb + 14))); break;
+    case 7: {  // the zero test at the bounds the group law instantiates (group_check.hpp): variant = A, out[0] = the verdict
+      const int z = fe29_eqz_check<Fe29>(variant, pa);
+      if (z >= 0) r[0] = (uint32_t)z;
+      break;
+    }
     default: break;
   }
 }
-__global__ void __launch_bounds__(64) k_field_check_fe29x2p(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+__global__ void __launch_bounds__(64) k_field_check_fe29x2p(int op, int variant, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
                                                             uint32_t* __restrict__ out, int n) {
   const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;  // one Fp2 element per lane pair
   if (i >= n) return;
@@ -266,6 +273,11 @@ __global__ void __launch_bounds__(64) k_field_check_fe29x2p(int op, const uint32
       fe29_to_wire(r, f_mulsub(Fe29x2P<4096>(fe29_raw<4096>(pa)), Fe29x2P<1024>(fe29_raw<1024>(pb)),
                                Fe29x2P<4096>(fe29_raw<4096>(pa + 28)), Fe29x2P<1024>(fe29_raw<1024>(pb + 28))).h);
       break;
+    case 7: {  // the pair's verdict on (c0, c1) = a[0..28), written once by the even lane
+      const int z = fe29_eqz_check<Fe29x2P>(variant, pa);
+      if (z >= 0 && !pair_odd()) out[(size_t)i * 24] = (uint32_t)z;
+      break;
+    }
     default: break;
   }
 }
@@ -432,6 +444,75 @@ __global__ void __launch_bounds__(64) k_field_check_fr29(int op, const uint32_t*
 #pragma unroll
   for (int j = 0; j < 9; j++) r[j] = z.v[j];
 }
+// The group law of the MSM buckets on STORED words (group_check.hpp: ops 0-3 through MsmGroup<C>::madd / add / dbl, one item
+// per row: a lane, or a lane pair of the paired Fp2 form), and the four-lane form of msm_coop.hpp, which exists on the device
+// only (ops 8-13, one GROUP of four items per row, the LDS arrangement of k_msm_reduce_level_coop).  a, b, out: ACC_WORDS per
+// row.  A row index beyond n drops a whole item / a whole group: the pair exchange and the group broadcasts read their own lanes.
+template <class C>
+__global__ void __launch_bounds__(64) k_group_check(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                    uint32_t* __restrict__ out, int n) {
+  constexpr int XW = MsmGroup<C>::ACC_WORDS;
+  const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> LaneShift<C>::value);
+  if (i >= n) return;
+  group_check_op<C>(op, a + (size_t)i * XW, b + (size_t)i * XW, out + (size_t)i * XW);
+}
+//   op 8 add(a, b) -> out   9 out = a, then add(out, b) -> out   10 out = b, then add(a, out) -> out
+//   op 11 dbl(a) -> out     12 out = a, then dbl(out) -> out     13 copy(a) -> out
+#ifdef __HIP_DEVICE_COMPILE__
+// between the copy of a row into `out` (global memory here, LDS in the MSM's tail) and the operation that reads it back through
+// the other items of the group: the stores are complete before any lane of the wave loads
+__device__ __forceinline__ void coop_inplace_sync() {
+  __threadfence_block();
+  coop_sync();
+}
+#endif
+template <class C>
+__global__ void __launch_bounds__(64) k_group_check_coop(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b,
+                                                         uint32_t* out, int n) {
+#ifdef __HIP_DEVICE_COMPILE__
+  using K = CoopXyzz<C>;
+  constexpr int XW = MsmGroup<C>::ACC_WORDS;
+  extern __shared__ __attribute__((aligned(16))) uint32_t coop_lds[];
+  uint32_t* lds = coop_lds + (size_t)K::group_in_block() * K::GROUP_WORDS;
+  const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> (K::LS + 2));
+  if (i >= n) return;
+  const uint32_t *pa = a + (size_t)i * XW, *pb = b + (size_t)i * XW;
+  uint32_t* o = out + (size_t)i * XW;
+  switch (op) {
+    case 8: K::add(lds, pa, pb, o); break;
+    case 9:
+      K::copy(pa, o);
+      coop_inplace_sync();
+      K::add(lds, o, pb, o);
+      break;
+    case 10:
+      K::copy(pb, o);
+      coop_inplace_sync();
+      K::add(lds, pa, o, o);
+      break;
+    case 11: K::dbl(lds, pa, o); break;
+    case 12:
+      K::copy(pa, o);
+      coop_inplace_sync();
+      K::dbl(lds, o, o);
+      break;
+    case 13: K::copy(pa, o); break;
+    default: break;
+  }
+#endif
+}
+template <class C>
+static void group_check_launch(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st) {
+  constexpr int LS = LaneShift<C>::value;
+  if (op >= 0 && op <= 3) {
+    hipLaunchKernelGGL(k_group_check<C>, dim3((((size_t)n << LS) + 63) / 64), dim3(64), 0, st, op, d_a, d_b, d_out, n);
+  } else if constexpr (CoopOK<C>::value) {
+    if (op < 8 || op > 13) return;
+    constexpr int GROUPS = 64 >> (LS + 2);   // per block: one wave holds 16 groups (G1) / 8 (G2)
+    const size_t lds_bytes = (size_t)GROUPS * COOP_SLOTS * MsmGroup<C>::FW * 4;
+    hipLaunchKernelGGL(k_group_check_coop<C>, dim3((n + GROUPS - 1) / GROUPS), dim3(64), lds_bytes, st, op, d_a, d_b, d_out, n);
+  }
+}
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
                            hipStream_t st) {
   if (n <= 0) return hipSuccess;
@@ -439,8 +520,8 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   if (field == 0) hipLaunchKernelGGL(k_field_check_fe9<Fe9SecpPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 1) hipLaunchKernelGGL(k_field_check_fe9<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 2) hipLaunchKernelGGL(k_field_check_fe29, grid, block, 0, st, op, d_a, d_b, d_out, n);
-  else if (field == 3) hipLaunchKernelGGL(k_field_check_fe29raw, grid, block, 0, st, op, d_a, d_b, d_out, n);
-  else if (field == 4) hipLaunchKernelGGL(k_field_check_fe29x2p, dim3((2 * n + 63) / 64), block, 0, st, op, d_a, d_b, d_out, n);
+  else if (field == 3) hipLaunchKernelGGL(k_field_check_fe29raw, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
+  else if (field == 4) hipLaunchKernelGGL(k_field_check_fe29x2p, dim3((2 * n + 63) / 64), block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 5) hipLaunchKernelGGL(k_field_check_fused<Fe9SecpPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 6) hipLaunchKernelGGL(k_field_check_fused<Fe9EdPR>, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
   else if (field == 7) hipLaunchKernelGGL(k_field_check_secp_ladder, grid, block, 0, st, op, d_a, d_b, d_out, n);
@@ -448,6 +529,11 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 8 && variant == 1) hipLaunchKernelGGL(k_field_check_fr29<Fr29Bn>, grid, block, 0, st, op, d_a, d_b, d_out, n);
   else if (field == 8) return hipSuccess;  // unknown variant: out stays zero
   else if (field == 9) hipLaunchKernelGGL(k_field_check_fe9m, grid, block, 0, st, op, variant, d_a, d_b, d_out, n);
+  else if (field == 10) group_check_launch<CurveSecp>(op, d_a, d_b, d_out, n, st);
+  else if (field == 11) group_check_launch<CurveEd>(op, d_a, d_b, d_out, n, st);
+  else if (field == 12) group_check_launch<CurveG1>(op, d_a, d_b, d_out, n, st);
+  else if (field == 13) group_check_launch<CurveG2P>(op, d_a, d_b, d_out, n, st);
+  else if (field == 14) group_check_launch<CurveBn254>(op, d_a, d_b, d_out, n, st);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

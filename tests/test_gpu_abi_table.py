@@ -62,7 +62,7 @@ SPECS = [
     ("ncg_schnorr_verify_batch_msgs_dev", "N B M B B B S", None, [], None),
     ("ncg_ntt", "F 3 N h B B 0", 0, [1, 2], "unsupported field %d"),
     ("ncg_ntt_dev", "F 3 N h B B 0 S", 0, [1, 2], "unsupported field %d"),
-    ("ncg_field_check", "F 0 0 N B B B", 0, [-1, 10], "unknown field %d"),
+    ("ncg_field_check", "F 0 0 N B B B", 0, [-1, 15], "unknown field %d"),
     ("ncg_msm_resident", "P B B o", None, [], None),
     ("ncg_msm_resident_dev", "P B h o S", None, [], None),
     ("ncg_mul_var_batch_resident", "P B B b", None, [], None),
