@@ -13,6 +13,8 @@
 #include "endo.hpp"
 #include "ecdsa.hip"
 #include "msm_shard.hpp"
+#include "msm_endo.hip"  // msm_make_plan_endo
+#include "msm_schedule.hpp"
 #include "fe9m_check.hpp"
 #include "group_check.hpp"
 
@@ -610,6 +612,57 @@ int ht_msm_seg(int curve, int n, int c_override, int* out) {
   out[0] = pl.c; out[1] = pl.nwin; out[2] = pl.nb; out[3] = sg.seg; out[4] = sg.nseg; out[5] = sg.nseg << pl.ls; out[6] = pl.accum_waves;
   return 0;
 }
+// the launch schedule of the device phase (msm_schedule.hpp) as integers.  The plan is built as the entry points build it:
+// opt = {endo (msm_make_plan_endo), shared (precomputed set), part_flags, n_layout (> 0: a part of a host-pointer MSM whose
+// layout plan has n_layout points), w0, window count (0 = all; the window-sharded ranks' msm_plan_take_windows), seg override,
+// run_serial override, pts_stored}.  out: the fields named in tests/hosttest.py MSM_SCHEDULE_FIELDS, then (tasks, coop, grid) of
+// the 16 fold-level slots.
+int ht_msm_schedule(int curve, int n, int c_override, const int* opt, long long* out) {
+  MsmPlan pl;
+  if ((opt[0] ? msm_make_plan_endo(curve, n, c_override, &pl) : msm_make_plan_impl(curve, n, c_override, &pl)) != 0) return -1;
+  if (opt[1]) {  // api.hip ncg_resident_plan
+    pl.shared = 1;
+    pl.top_tb = 0;
+    pl.top_submask = 0;
+  }
+  pl.pts_stored = opt[8] || opt[1];
+  pl.part_flags = opt[2];
+  if (opt[3] > 0) {  // api.hip ncg_msm: the layout plan has the same window width
+    MsmPlan layout;
+    if (msm_make_plan_impl(curve, opt[3], pl.c, &layout) != 0) return -1;
+    pl.n_layout = layout.n;
+    pl.Q_layout = layout.Q;
+  }
+  if (opt[5] > 0) msm_plan_take_windows(pl, opt[4], opt[5], opt[5] <= 2 ? 128 : 512);  // comm.hip shard_local
+  pl.seg_override = opt[6];
+  pl.run_serial_override = opt[7];
+  const MsmShape sh = msm_shape(curve);
+  const MsmSchedule S = msm_schedule(pl, sh);
+  const MsmLayout& L = S.layout;
+  // msm_seg prices the placement of the grid it proposes with the rule the launch pins it by
+  const long seg_wgs = (long)S.av.nwin * ((((long)S.sg.nseg << sh.ls) + 255) / 256);
+  const long long v[] = {
+      (long long)L.pts_mont, (long long)L.digits, (long long)L.counts, (long long)L.bucket_start, (long long)L.sorted, (long long)L.sort_tmp,
+      (long long)L.shared_start, (long long)L.buckets, (long long)L.part_pts, (long long)L.part_meta, (long long)L.long_runs, (long long)L.bad,
+      (long long)L.red0, (long long)L.red1, (long long)L.tail0, (long long)L.tail1, (long long)L.fin, (long long)L.total,
+      pl.c, pl.nwin, pl.nb, pl.Q, S.av.n, S.av.nwin, pl.top_tb, sh.ls, sh.coop,
+      S.part_first, S.part_last, S.pts_in_place, S.pts_grid, S.digits_grid,
+      S.sort, S.s2.lgr, S.sort_grid.x, S.sort_grid.y, (long long)S.small_lds, (long long)S.hist_lds, (long long)S.scan_lds, S.split_totals,
+      S.totals_grid.x, S.totals_grid.y, S.shared_grid, S.scatter_n, S.scatter_per,
+      S.sg.seg, S.sg.nseg, S.acc_grid.x, S.acc_grid.y, (long long)S.acc_reserve, S.acc_sparse, msm_acc_pinned(seg_wgs), S.run_serial, S.merge,
+      S.merge_grid.x, S.merge_grid.y, (long long)S.merge_lds, (long long)S.long_lds,
+      S.nfold, (long long)S.fold_coop_lds, S.narr, S.n_in, S.tail_units, (long long)S.tail_lds, S.ngroups, S.top_w,
+      MSM_LONG_BLOCKS, MSM_TAIL_THREADS, (long long)SORT2_STAGE * 4};
+  const int nv = (int)(sizeof(v) / sizeof(v[0]));
+  for (int i = 0; i < nv; i++) out[i] = v[i];
+  for (int l = 0; l < 16; l++) {
+    const bool on = l < S.nfold;
+    out[nv + 3 * l] = on ? S.fold[l].tasks : 0;
+    out[nv + 3 * l + 1] = on ? S.fold[l].coop : 0;
+    out[nv + 3 * l + 2] = on ? S.fold[l].grid : 0;
+  }
+  return nv;
+}
 int ht_msm_shard_combine(int curve, int n_max, int nparts, const uint8_t* slots, uint32_t* out, uint8_t* out_inf, char* err, int errlen) {
 #define CALL(C) ht_shard_combine_t<C>(curve, n_max, nparts, slots, out, out_inf, err, errlen)
   HT_CURVE_DISPATCH(curve, CALL)
@@ -668,7 +721,7 @@ int ht_msm_plan(int curve, int n, int* out) {  // c, nwin, ngroups, acc words
   out[0] = pl.c;
   out[1] = pl.nwin;
   out[2] = msm_ngroups(pl.c);
-  out[3] = (int)msm_acc_words_inl(curve);
+  out[3] = (int)msm_shape(curve).acc_words;
   return 0;
 }
 

@@ -17,7 +17,7 @@
 #include "host_api.hpp"
 #include "msm_coop.hpp"
 #include "msm_finish.hpp"
-#include "msm_plan.hpp"
+#include "msm_schedule.hpp"
 
 namespace ncg {
 
@@ -314,14 +314,7 @@ static __global__ void __launch_bounds__(1024) k_msm_scatter(const int16_t* __re
 // (the order inside a bucket differs, as it already does between runs: LDS atomics).  Entries pack index, sign and the low
 // bucket bits into 32 bits, so the form is used when they fit (n <= 2^22 at c = 16) and for per-window lists only; other
 // plans keep the one-level kernels.
-constexpr int SORT2_MAX_RANGES = 256;   // ranges per window: 64, or 128 / 256 where 64 regions would not fit the staged kernel (Sort2::lgr)
-constexpr int SORT2_SLICES = 8;
 constexpr int SORT2_UNROLL = 8;   // entries a lane of the coarse kernels holds in flight
-struct Sort2 {
-  int lgr;                // log2(ranges per window): 6..8
-  int sh, idxbits;        // log2(buckets per range), bits of an entry index
-  int top_w, top_base, top_sh;   // local index of the plan's top window (-1: not in this plan / full), first bucket its ranges cover, its sh
-};
 __device__ __forceinline__ void sort2_window(const Sort2& s2, int w, uint32_t& base, int& sh) {
   const bool top = w == s2.top_w;
   base = top ? (uint32_t)s2.top_base : 0u;
@@ -495,8 +488,6 @@ static __global__ void __launch_bounds__(1024) k_sort2_scatter(const int16_t* __
 // region in registers and its output staged in LDS: one coalesced read, one coalesced write, no second pass over memory.
 // Larger regions (identical scalars; few distinct values) go through the two slice kernels below, which return at once
 // for every region the staged kernel took.
-constexpr int SORT2_PER_THREAD = 20;
-constexpr int SORT2_STAGE = 1024 * SORT2_PER_THREAD;   // entries: 80 KB of LDS
 // bucket starts of range r from the bucket sizes `v` (thread t = bucket t of the range; at most 512 buckets, blockDim >= 512);
 // returns this bucket's start.  Also writes what no range covers: the buckets past the top window's last range and the end marker.
 __device__ __forceinline__ uint32_t sort2_starts(uint32_t* scan, uint32_t v, uint32_t a, int r, int w, int BL, uint32_t base, int R,
@@ -670,8 +661,6 @@ static __global__ void __launch_bounds__(512) k_sort2_fine_place(const uint32_t*
 // The same workgroup clears its window's bucket accumulators (the accumulate kernel writes non-empty buckets only) and block 0 the
 // fix-up's work-list counter, which saves the two fill launches as well.  Same outputs as the separate kernels (the order inside
 // a bucket is arbitrary there too: LDS atomics).
-constexpr int MSM_SMALL_N = 1 << 15;     // points: 64 KB of LDS digits
-constexpr int MSM_SMALL_NB = 1 << 13;    // buckets per window: 32 KB of LDS counters
 static __global__ void __launch_bounds__(1024) k_msm_sort_small(const uint32_t* __restrict__ scalars, uint32_t* __restrict__ bucket_start,
                                                          uint32_t* __restrict__ sorted, uint32_t* __restrict__ bad_index,
                                                          uint32_t* __restrict__ buckets, int acc_words, uint32_t* __restrict__ long_runs,
@@ -770,56 +759,6 @@ static __global__ void __launch_bounds__(1024) k_msm_sort_small(const uint32_t* 
   }
 #endif
 }
-static bool msm_small_sort_ok(const MsmPlan& pl) {
-  return !pl.endo && !pl.shared && pl.part_flags == 3 && pl.n_layout <= pl.n && pl.n <= MSM_SMALL_N && pl.nb <= MSM_SMALL_NB;
-}
-
-// does the two-level form apply to this plan?  Fills the per-plan constants.
-static bool msm_sort2_ok(const MsmPlan& pl, int n_max, Sort2* s2) {
-  if (pl.shared || pl.nb < 1024 || pl.nb > (1 << 15)) return false;
-  int lg = 0;
-  while ((1 << lg) < pl.nb) lg++;
-  int ib = 1;
-  while (ib < 31 && (1u << ib) < (unsigned)std::max(n_max, 2)) ib++;
-  // 64 ranges per window; 128 / 256 where a region would otherwise hold more than 16 384 entries on average (the staged kernel
-  // takes up to SORT2_STAGE = 20 480): the 2^21 entries of an endomorphism plan over 2^20 G1 points, plans of 2^21 / 2^22 points
-  int lgr = 6;
-  while (lgr < 8 && (n_max >> lgr) > 16384 && lg - lgr > 1) lgr++;
-  if (ib + 1 + (lg - lgr) > 32) return false;
-  s2->lgr = lgr;
-  s2->sh = lg - lgr;
-  s2->idxbits = ib;
-  s2->top_w = -1;
-  s2->top_base = 0;
-  s2->top_sh = lg - lgr;
-  if (!pl.endo && !pl.top_tb) {   // generic plans whose top window is not spread (MsmPlan::top_tb): the top window's field v = (k + H') >> c (nwin - 1) lies in [half, vmax] (H' carries the window's
-                    // own half), so its digits v - half are >= 0 and its buckets are [0, vmax - half) only
-    const int nwt = pl.nwin_total ? pl.nwin_total : pl.nwin;
-    const int wl = nwt - 1 - pl.w0;   // local index of the top window
-    if (wl >= 0 && wl < pl.nwin) {
-      // the ONE computation of the top field's bound (msm_plan.hpp; ADVICE r05: the sort, the spread and the tail must agree on it).
-      // A scalar >= the group order can exceed it: its top digit then wraps through `& (R - 1)` into another region of this window -
-      // memory-safe (every region index stays below R), and harmless only because such a call returns the bad-scalar error and
-      // its sum is discarded by every caller (k_msm_digits records the index; msm_finish_t / job_finish_host check it first)
-      const uint32_t vmax = msm_plan_top_vmax(pl);
-      const uint32_t half = 1u << (pl.c - 1);
-      const uint32_t span = vmax >= half ? vmax - half + 2u : half;   // buckets the window can reach: largest digit vmax - half, + 1, + 1 of slack (msm_plan_top_spread: maxd + 1)
-      int tb = 0;
-      while ((1u << tb) < span) tb++;
-      if ((1u << tb) < half) {
-        s2->top_w = wl;
-        s2->top_base = 0;
-        s2->top_sh = std::max(0, tb - lgr);
-      }
-    }
-  }
-  return true;
-}
-// words of the scratch the two-level sort keeps where the one-level sort keeps its per-chunk bucket counts
-static size_t msm_sort2_words(const MsmPlan& pl) {
-  return (size_t)pl.nwin * ((size_t)pl.Q * SORT2_MAX_RANGES + 2 * (SORT2_MAX_RANGES + 1) + 3) + 8 + (size_t)pl.nwin * pl.nb * SORT2_SLICES;
-}
-
 // ------------------------------------------------------------------ 4. bucket accumulation
 // Balanced, segmented: every lane owns exactly SEG consecutive entries of a window's sorted
 // list (so all lanes of a wave run the same number of mixed adds no matter how the scalars are
@@ -949,9 +888,6 @@ __global__ void __launch_bounds__(256, AccumMinWaves<C>::value) k_msm_accum(cons
 // them; the short top window of most plans) goes to a work list instead, and k_msm_fixup_long (below, after the
 // cooperative operations it uses) gives each such run a whole workgroup: strided partial sums, then an LDS tree -
 // log depth in the run length.
-constexpr int MSM_RUN_SERIAL = 2;
-constexpr int MSM_RUN_SERIAL_SHARED = 8;
-constexpr int MSM_LONG_BLOCKS = 512;
 template <class C>
 __global__ void __launch_bounds__(256, TailMinWaves<C>::value) k_msm_fixup_merge(const uint32_t* __restrict__ part_pts,
                                                         const int* __restrict__ part_meta,
@@ -1048,7 +984,6 @@ __global__ void __launch_bounds__(256) k_msm_reduce_level_coop(const uint32_t* _
 // TailOps<C, COOP>: a "unit" is one item (lane / lane pair) running the complete single-lane routines, or a
 // group of four items sharing each operation (msm_coop.hpp).  Operands and results live in memory; `lds` is the
 // unit's scratch: the exchange slots of the cooperative form, then one accumulator for the grouping chain.
-constexpr int MSM_TAIL_THREADS = 512;
 template <class C, bool COOP> struct TailOps;
 template <class C>
 struct TailOps<C, false> {
@@ -1194,7 +1129,6 @@ __global__ void __launch_bounds__(256, 2) k_msm_fixup_merge_units(const uint32_t
 // kernel of a 2^13 / 2^14-point MSM (62 us, + 35 us of work-list runs above 8 pieces).  Here unit u of the bucket's group sums the
 // pieces u, u + U, .. and a tree over the U accumulators (LDS, all in one wave) finishes: ceil(P / U) - 1 + log2 U dependent
 // additions for P pieces (two units, P = 15: 8 instead of 14).  Runs of more than run_serial heads still go to the work list.
-constexpr int MERGE_TREE_ULOG = 1;
 template <class C, bool COOP>
 __global__ void __launch_bounds__(256, 2) k_msm_fixup_merge_tree(const uint32_t* __restrict__ part_pts, const int* __restrict__ part_meta,
                                                               const uint32_t* __restrict__ bucket_start, uint32_t* __restrict__ buckets,
@@ -1261,7 +1195,6 @@ __global__ void __launch_bounds__(256, 2) k_msm_fixup_merge_tree(const uint32_t*
 // s0 / s1: scratch, MSM_TAIL_REGION accumulators PER WINDOW each - a window's levels ping-pong inside its own
 // regions, laid out [array][n] (workgroups run at different levels, so they must not share a layout);
 // fin: [ngroups][nwin] grouped sums.
-constexpr int MSM_TAIL_REGION = 2 * MSM_TAIL_THREADS + 64;
 template <class C, bool COOP>
 __global__ void __launch_bounds__(MSM_TAIL_THREADS) k_msm_tail(const uint32_t* __restrict__ in, uint32_t* __restrict__ s0,
                                                                uint32_t* __restrict__ s1, uint32_t* __restrict__ fin,
@@ -1377,383 +1310,257 @@ __global__ void __launch_bounds__(256) k_msm_sum_partials(uint32_t* __restrict__
 int msm_make_plan(int curve, int n, int c_override, MsmPlan* pl) { return msm_make_plan_impl(curve, n, c_override, pl); }
 #endif
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct MsmLayout {
-  size_t pts_mont, digits, counts, bucket_start, sorted, sort_tmp, shared_start, buckets, part_pts, part_meta, long_runs, bad, red0, red1, tail0, tail1, fin, total;
-};
-
+// ------------------------------------------------------------------ the driver (schedule: msm_schedule.hpp)
+// the integers the schedule is computed from, tied to the templates the kernels are instantiated with
+template <class C> struct MsmCurveId;
+template <> struct MsmCurveId<CurveSecp> { static constexpr int value = CURVE_SECP256K1; };
+template <> struct MsmCurveId<CurveG1> { static constexpr int value = CURVE_BLS12_381_G1; };
+template <> struct MsmCurveId<CurveG2> { static constexpr int value = CURVE_BLS12_381_G2; };
+template <> struct MsmCurveId<CurveEd> { static constexpr int value = CURVE_ED25519; };
+template <> struct MsmCurveId<CurveBn254> { static constexpr int value = CURVE_BN254_G1; };
 template <class C>
-static MsmLayout msm_layout(const MsmPlan& pl_in) {
-  MsmLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align256(off + bytes);
-    return o;
-  };
-  MsmPlan pl = pl_in;
-  if (pl.n_layout > pl.n) pl.n = pl.n_layout;  // parts of one MSM: every part addresses the layout of the largest
-  if (pl.Q_layout > pl.Q) pl.Q = pl.Q_layout;
-  L.pts_mont = take((pl.endo || pl.pts_stored || pl.shared) ? 0 : (size_t)pl.n * MsmGroup<C>::AFF_WORDS * 4);  // else: the caller's array
-  L.digits = take((size_t)pl.nwin * pl.n * 2);
-  Sort2 s2l;
-  const bool sort2 = msm_sort2_ok(pl, pl.n, &s2l);
-  L.counts = take(sort2 ? msm_sort2_words(pl) * 4 : (size_t)pl.nwin * pl.Q * pl.nb * 4);
-  L.bucket_start = take((size_t)pl.nwin * (pl.nb + 1) * 4);
-  L.sorted = take((size_t)pl.nwin * pl.n * 4);
-  L.sort_tmp = take(sort2 ? (size_t)pl.nwin * pl.n * 4 : 0);   // the regions of the two-level sort
-  L.shared_start = take((size_t)(pl.nb + 1) * 4);
-  const MsmPlan av = msm_acc_view(pl);   // one window of nwin * n entries in shared-bucket mode
-  L.buckets = take((size_t)av.nwin * av.nb * MsmGroup<C>::ACC_WORDS * 4);
-  MsmSeg sg = msm_seg(av);
-  L.part_pts = take((size_t)av.nwin * sg.nseg * 2 * MsmGroup<C>::ACC_WORDS * 4);
-  L.part_meta = take((size_t)av.nwin * sg.nseg * 4 * 4);
-  // work list of the long runs: a counter + (window, bucket, first lane, last lane) per run of more than
-  // MSM_RUN_SERIAL heads - such runs cover disjoint lane ranges, so there are at most nwin * nseg / MSM_RUN_SERIAL
-  // (with a run_serial override below 2 - tests - adjacent runs share a lane: at most one run per lane)
-  L.long_runs = take(16 + ((size_t)av.nwin * (sg.nseg + 1)) * 16);
-  L.bad = take(64);
-  // fold ping-pong: level l output holds (l+1) * nwin * nb/2^l points <= nwin*nb (l = 1, 2)
-  size_t red = (size_t)av.nwin * std::max(av.nb, av.c) * MsmGroup<C>::ACC_WORDS * 4;
-  L.red0 = take(red);
-  L.red1 = take(red);
-  // the tail workgroups' private ping-pong (levels that fit one workgroup per window: at most 2 * 512 additions
-  // per window and level) and the grouped window sums
-  const size_t tail = (size_t)av.nwin * MSM_TAIL_REGION * MsmGroup<C>::ACC_WORDS * 4;
-  L.tail0 = take(tail);
-  L.tail1 = take(tail);
-  L.fin = take((size_t)msm_ngroups(av.c) * av.nwin * MsmGroup<C>::ACC_WORDS * 4);
-  L.total = off;
-  return L;
+constexpr bool msm_shape_matches() {
+  using G = MsmGroup<C>;
+  using D = typename DeviceCurve<C>::type;
+  using K = TailOps<D, CoopOK<D>::value>;
+  constexpr MsmShape s = msm_shape(MsmCurveId<C>::value);
+  return s.aff_words == G::AFF_WORDS && s.acc_words == G::ACC_WORDS && s.wire_words == G::WIRE_AFF && s.ls == LaneShift<D>::value &&
+         s.coop == CoopOK<D>::value && msm_unit_shift(s, s.coop) == K::UNIT_SHIFT && msm_unit_scratch_words(s, s.coop) == K::SCRATCH_WORDS &&
+         msm_unit_lds_words(s, s.coop) == K::LDS_WORDS;
+}
+static_assert(MSM_UNIT_SLOTS == COOP_SLOTS, "msm_schedule.hpp restates msm_coop.hpp");
+static_assert(msm_shape_matches<CurveSecp>() && msm_shape_matches<CurveG1>() && msm_shape_matches<CurveG2>() && msm_shape_matches<CurveEd>() &&
+                  msm_shape_matches<CurveBn254>(),
+              "msm_shape restates MsmGroup / LaneShift / CoopOK / TailOps");
+
+// raise the dynamic-LDS limit of kernel K, once per process and device
+template <auto K>
+static hipError_t msm_lds_limit(int dev, size_t bytes) {
+  static bool attr_done[16] = {};
+  if (dev >= 0 && dev < 16 && attr_done[dev]) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess && dev >= 0 && dev < 16) attr_done[dev] = true;
+  return e;
 }
 
-// Device phase: everything up to the grouped window sums (ng x nwin accumulators, device memory,
-// inside the workspace).  Asynchronous on `st`.
-template <class C>
-static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const uint32_t* d_scalars, void* ws,
-                               const uint32_t** d_fin, hipStream_t st, const uint32_t** d_bad = nullptr,
-                               const MsmSide* side = nullptr) {
-  using G = MsmGroup<C>;
-  using D = typename DeviceCurve<C>::type;  // kernels: lane-paired form for G2
-  constexpr int LS = LaneShift<D>::value;
-  constexpr int XW = G::ACC_WORDS;
-  MsmLayout L = msm_layout<C>(pl);
-  char* base = (char*)ws;
-  uint32_t* pts_mont = (uint32_t*)(base + L.pts_mont);
-  int16_t* digits = (int16_t*)(base + L.digits);
-  uint32_t* counts = (uint32_t*)(base + L.counts);
-  uint32_t* bstart = (uint32_t*)(base + L.bucket_start);
-  uint32_t* sorted = (uint32_t*)(base + L.sorted);
-  uint32_t* buckets = (uint32_t*)(base + L.buckets);
-  uint32_t* red[2] = {(uint32_t*)(base + L.red0), (uint32_t*)(base + L.red1)};
-  const int n = pl.n;
-  hipError_t e;
+// the regions of the workspace (MsmLayout) as pointers
+struct MsmWs {
+  uint32_t* pts_mont;
+  int16_t* digits;
+  uint32_t *counts, *bstart, *sorted, *sort_tmp, *shared_start, *buckets, *part_pts;
+  int* part_meta;
+  uint32_t *long_runs, *bad, *red[2], *tail0, *tail1, *fin;
+  const uint32_t* acc_start;   // the bucket starts the kernels after the sort read (shared-bucket mode: shared_start)
+  int dev;
+};
+// error paths between the fork and the join must not return while the side-stream kernel is still writing into the
+// workspace (the caller may free or re-size it): drain the side stream unless the join has been enqueued on `st`
+struct MsmSideGuard {
+  const MsmSide* side;
+  bool forked = false, armed = false;
+  ~MsmSideGuard() {
+    if (armed && side && side->stream) (void)hipStreamSynchronize(side->stream);
+  }
+};
 
-  const bool part_first = (pl.part_flags & 1) != 0, part_last = (pl.part_flags & 2) != 0;
-  if ((!part_first || !part_last) && (pl.shared || pl.endo)) return hipErrorInvalidValue;  // parts: generic plans only
-  bool forked = false;
-  // error paths between the fork and the join must not return while the side-stream kernel is still writing into the
-  // workspace (the caller may free or re-size it): drain the side stream unless the join has been enqueued on `st`
-  struct SideGuard {
-    const MsmSide* side;
-    bool armed = false;
-    ~SideGuard() {
-      if (armed && side && side->stream) (void)hipStreamSynchronize(side->stream);
-    }
-  } side_guard{side};
-  uint32_t* bad = (uint32_t*)(base + L.bad);
-  if (part_first) {
-    e = hipMemsetAsync(bad, 0xFF, 4, st);
+// stage 1: the scalar verdict's clear, the points into storage format (beside the digits / sort kernels where the caller offers a
+// side stream; joined in front of the accumulate kernel) and the digits
+template <class C>
+static hipError_t msm_stage_points(const MsmPlan& pl, const MsmSchedule& S, MsmWs& W, const uint32_t* d_pts, const uint32_t* d_scalars,
+                                   hipStream_t st, MsmSideGuard& sg) {
+  using D = typename DeviceCurve<C>::type;  // kernels: lane-paired form for G2
+  hipError_t e;
+  if (S.part_first) {
+    e = hipMemsetAsync(W.bad, 0xFF, 4, st);
     if (e != hipSuccess) return e;
   }
-  const bool small_sort = msm_small_sort_ok(pl);   // digits + sort + the two clears in one launch (3c)
-  if (pl.endo) {  // d_pts is the expanded image set, already in storage format (msm_endo_expand)
-    pts_mont = const_cast<uint32_t*>(d_pts);
-    e = msm_endo_digits(pl, d_scalars, digits, bad, st);
-    if (e != hipSuccess) return e;
-  } else {
-    if (pl.pts_stored || pl.shared) {
-      pts_mont = const_cast<uint32_t*>(d_pts);
-    } else if (side && side->stream) {  // beside the digits / sort kernels; joined in front of the accumulate kernel
+  if (S.pts_in_place) W.pts_mont = const_cast<uint32_t*>(d_pts);
+  if (pl.endo) return msm_endo_digits(pl, d_scalars, W.digits, W.bad, st);  // d_pts is the expanded image set, already in storage format (msm_endo_expand)
+  if (!S.pts_in_place) {
+    const MsmSide* side = sg.side;
+    if (side && side->stream) {
       e = hipEventRecord(side->fork, st);
       if (e == hipSuccess) e = hipStreamWaitEvent(side->stream, side->fork, 0);
       if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_points_to_mont<D>, dim3((unsigned)((((size_t)n << LS) + 255) / 256)), dim3(256), 0, side->stream,
-                         d_pts, pts_mont, n);
-      side_guard.armed = true;
+      hipLaunchKernelGGL(k_points_to_mont<D>, dim3(S.pts_grid), dim3(256), 0, side->stream, d_pts, W.pts_mont, pl.n);
+      sg.armed = true;
       e = hipEventRecord(side->join, side->stream);
       if (e != hipSuccess) return e;
-      forked = true;
+      sg.forked = true;
     } else {
-      hipLaunchKernelGGL(k_points_to_mont<D>, dim3((unsigned)((((size_t)n << LS) + 255) / 256)), dim3(256), 0, st, d_pts,
-                         pts_mont, n);
-    }
-    if (!small_sort) hipLaunchKernelGGL(k_msm_digits, dim3((n + 255) / 256), dim3(256), 0, st, d_scalars, digits, pl, bad);
-  }
-  size_t lds = (size_t)pl.nb * 4;
-  {  // opt in to large dynamic LDS once per process and device (c <= 16: at most 128 KB)
-    static bool attr_done[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-      const int max_lds = (1 << 15) * 4;
-      e = hipFuncSetAttribute((const void*)k_msm_hist, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute((const void*)k_msm_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute((const void*)k_msm_scan, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds + max_lds / 32 + 64);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 16) attr_done[dev] = true;
+      hipLaunchKernelGGL(k_points_to_mont<D>, dim3(S.pts_grid), dim3(256), 0, st, d_pts, W.pts_mont, pl.n);
     }
   }
-  const dim3 sort_grid = pl.xcd_map ? dim3((unsigned)(pl.Q * ((pl.nwin + 7) & ~7))) : dim3(pl.Q, pl.nwin);
-  uint32_t* shared_start = (uint32_t*)(base + L.shared_start);
-  Sort2 s2;
-  if (small_sort) {
-    static bool attr_done[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-      e = hipFuncSetAttribute((const void*)k_msm_sort_small, hipFuncAttributeMaxDynamicSharedMemorySize, MSM_SMALL_NB * 4 + MSM_SMALL_N * 2);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 16) attr_done[dev] = true;
-    }
-    hipLaunchKernelGGL(k_msm_sort_small, dim3(pl.nwin), dim3(1024), (size_t)pl.nb * 4 + (size_t)((pl.n + 1) & ~1) * 2, st, d_scalars, bstart, sorted, bad,
-                       buckets, XW, (uint32_t*)(base + L.long_runs), pl);
-  } else if (msm_sort2_ok(pl, std::max(pl.n, pl.n_layout), &s2)) {   // two-level sort (3b): same bucket_start / sorted
-    uint32_t* ccount = counts;
+  if (S.sort != MSM_SORT_SMALL) hipLaunchKernelGGL(k_msm_digits, dim3(S.digits_grid), dim3(256), 0, st, d_scalars, W.digits, pl, W.bad);
+  return hipSuccess;
+}
+
+// stage 2: bucket_start and the per-window lists grouped by bucket
+static hipError_t msm_stage_sort(const MsmPlan& pl, const MsmSchedule& S, const MsmWs& W, const uint32_t* d_scalars, int acc_words,
+                                 hipStream_t st) {
+  hipError_t e;
+  // the one-level kernels opt in to large dynamic LDS whichever sort runs (c <= 16: at most 128 KB)
+  const size_t max_lds = (1 << 15) * 4;
+  e = msm_lds_limit<k_msm_hist>(W.dev, max_lds);
+  if (e == hipSuccess) e = msm_lds_limit<k_msm_scatter>(W.dev, max_lds);
+  if (e == hipSuccess) e = msm_lds_limit<k_msm_scan>(W.dev, max_lds + max_lds / 32 + 64);
+  if (e != hipSuccess) return e;
+  const dim3 sort_grid(S.sort_grid.x, S.sort_grid.y);
+  if (S.sort == MSM_SORT_SMALL) {
+    e = msm_lds_limit<k_msm_sort_small>(W.dev, MSM_SMALL_NB * 4 + MSM_SMALL_N * 2);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_msm_sort_small, dim3(pl.nwin), dim3(1024), S.small_lds, st, d_scalars, W.bstart, W.sorted, W.bad, W.buckets,
+                       acc_words, W.long_runs, pl);
+  } else if (S.sort == MSM_SORT_TWO_LEVEL) {   // (3b): same bucket_start / sorted
+    const Sort2& s2 = S.s2;
+    uint32_t* ccount = W.counts;
     const int R = 1 << s2.lgr;
     uint32_t* region_start = ccount + (size_t)pl.nwin * pl.Q * R;
     uint32_t* oversize = region_start + (((size_t)pl.nwin * (R + 1) + 3) & ~(size_t)3);   // count, then <= nwin * R entries
     uint32_t* fcount = oversize + (((size_t)pl.nwin * R + 1 + 3) & ~(size_t)3);
-    uint32_t* tmp = (uint32_t*)(base + L.sort_tmp);
-    hipLaunchKernelGGL(k_sort2_count, sort_grid, dim3(1024), 0, st, digits, ccount, pl, s2);
+    uint32_t* tmp = W.sort_tmp;
+    hipLaunchKernelGGL(k_sort2_count, sort_grid, dim3(1024), 0, st, W.digits, ccount, pl, s2);
     hipLaunchKernelGGL(k_sort2_scan, dim3(pl.nwin), dim3(R), 0, st, ccount, region_start, oversize, pl, s2);
-    hipLaunchKernelGGL(k_sort2_scatter, sort_grid, dim3(1024), 0, st, digits, ccount, region_start, tmp, pl, s2);
-    {
-      static bool attr_done[16] = {};
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-        e = hipFuncSetAttribute((const void*)k_sort2_fine_staged, hipFuncAttributeMaxDynamicSharedMemorySize, SORT2_STAGE * 4);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 16) attr_done[dev] = true;
-      }
-    }
-    hipLaunchKernelGGL(k_sort2_fine_staged, dim3(R, pl.nwin), dim3(1024), (size_t)SORT2_STAGE * 4, st, tmp, region_start, oversize, bstart,
-                       sorted, pl, s2);
+    hipLaunchKernelGGL(k_sort2_scatter, sort_grid, dim3(1024), 0, st, W.digits, ccount, region_start, tmp, pl, s2);
+    e = msm_lds_limit<k_sort2_fine_staged>(W.dev, SORT2_STAGE * 4);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sort2_fine_staged, dim3(R, pl.nwin), dim3(1024), (size_t)SORT2_STAGE * 4, st, tmp, region_start, oversize, W.bstart,
+                       W.sorted, pl, s2);
     // regions too large for the staged kernel (skewed scalars): a small grid over the work list, empty as a rule
     hipLaunchKernelGGL(k_sort2_fine_count, dim3(SORT2_FALLBACK_BLOCKS), dim3(512), 0, st, tmp, region_start, oversize, fcount, pl, s2);
-    hipLaunchKernelGGL(k_sort2_fine_place, dim3(SORT2_FALLBACK_BLOCKS), dim3(512), 0, st, tmp, region_start, oversize, fcount, bstart, sorted, pl, s2);
+    hipLaunchKernelGGL(k_sort2_fine_place, dim3(SORT2_FALLBACK_BLOCKS), dim3(512), 0, st, tmp, region_start, oversize, fcount, W.bstart, W.sorted, pl, s2);
   } else {
-    hipLaunchKernelGGL(k_msm_hist, sort_grid, dim3(1024), lds, st, digits, counts, pl);
-    if (pl.Q >= 64)
-      hipLaunchKernelGGL(k_msm_bucket_totals_split, dim3((pl.nb + 31) / 32, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
+    hipLaunchKernelGGL(k_msm_hist, sort_grid, dim3(1024), S.hist_lds, st, W.digits, W.counts, pl);
+    const dim3 totals_grid(S.totals_grid.x, S.totals_grid.y);
+    if (S.split_totals)
+      hipLaunchKernelGGL(k_msm_bucket_totals_split, totals_grid, dim3(256), 0, st, W.counts, W.bstart, pl);
     else
-      hipLaunchKernelGGL(k_msm_bucket_totals, dim3((pl.nb + 255) / 256, pl.nwin), dim3(256), 0, st, counts, bstart, pl);
+      hipLaunchKernelGGL(k_msm_bucket_totals, totals_grid, dim3(256), 0, st, W.counts, W.bstart, pl);
     if (pl.shared) {
-      hipLaunchKernelGGL(k_msm_shared_totals, dim3((pl.nb + 255) / 256), dim3(256), 0, st, bstart, shared_start, pl);
-      hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), (size_t)(pl.nb + pl.nb / 32 + 1) * 4, st, shared_start, pl);  // window 0 of a 1-window array
-      hipLaunchKernelGGL(k_msm_shared_starts, dim3((pl.nb + 255) / 256), dim3(256), 0, st, bstart, shared_start, pl);
+      hipLaunchKernelGGL(k_msm_shared_totals, dim3(S.shared_grid), dim3(256), 0, st, W.bstart, W.shared_start, pl);
+      hipLaunchKernelGGL(k_msm_scan, dim3(1), dim3(1024), S.scan_lds, st, W.shared_start, pl);  // window 0 of a 1-window array
+      hipLaunchKernelGGL(k_msm_shared_starts, dim3(S.shared_grid), dim3(256), 0, st, W.bstart, W.shared_start, pl);
     } else {
-      hipLaunchKernelGGL(k_msm_scan, dim3(pl.nwin), dim3(1024), (size_t)(pl.nb + pl.nb / 32 + 1) * 4, st, bstart, pl);
+      hipLaunchKernelGGL(k_msm_scan, dim3(pl.nwin), dim3(1024), S.scan_lds, st, W.bstart, pl);
     }
-    {
-      const int passes = std::max(1, std::min(pl.scatter_passes, pl.nb / 256));
-      const int per = (pl.nb + passes - 1) / passes;
-      for (int p = 0; p < passes; p++) {
-        const int b_lo = p * per, b_hi = std::min(pl.nb, b_lo + per);
-        if (b_lo >= b_hi) break;
-        hipLaunchKernelGGL(k_msm_scatter, sort_grid, dim3(1024), (size_t)(b_hi - b_lo) * 4, st, digits, counts, bstart, sorted, pl, b_lo, b_hi);
-      }
+    for (int p = 0; p < S.scatter_n; p++) {
+      const int b_lo = p * S.scatter_per, b_hi = std::min(pl.nb, b_lo + S.scatter_per);
+      hipLaunchKernelGGL(k_msm_scatter, sort_grid, dim3(1024), (size_t)(b_hi - b_lo) * 4, st, W.digits, W.counts, W.bstart, W.sorted, pl, b_lo, b_hi);
     }
   }
-  // from here on: the accumulate view (shared-bucket mode: ONE window of nwin * n entries whose starts are shared_start)
-  const MsmPlan av = msm_acc_view(pl);
-  const uint32_t* acc_start = pl.shared ? shared_start : bstart;
-  {
-    MsmSeg sg = msm_seg(av);
-    uint32_t* part_pts = (uint32_t*)(base + L.part_pts);
-    int* part_meta = (int*)(base + L.part_meta);
-    if (part_first && !small_sort) {
-      e = hipMemsetAsync(buckets, 0, (size_t)av.nwin * av.nb * XW * 4, st);  // empty buckets = infinity
-      if (e != hipSuccess) return e;
-    }
-    dim3 grid((unsigned)((((size_t)sg.nseg << LS) + 255) / 256), av.nwin);
-    if (forked) {
-      e = hipStreamWaitEvent(st, side->join, 0);
-      if (e != hipSuccess) return e;
-      side_guard.armed = false;
-    }
-    if (side && side->pts_ready) {  // host-pointer path: the points were still crossing PCIe while the sort ran
-      e = hipStreamWaitEvent(st, side->pts_ready, 0);
-      if (e != hipSuccess) return e;
-    }
-    {
-      // A grid of at most two workgroups per CU is latency-bound (every lane's chain of `seg` additions on a wave that has its SIMD
-      // to itself, or shares it with one other), and the dispatcher does not spread workgroups evenly: 238 workgroups on 256 CUs ran
-      // 18.5 us per addition where 104 ran 12.  An LDS reservation the kernel never touches makes the placement explicit: with
-      // 96 KB per workgroup a CU (160 KB) takes one, with 56 KB two.
-      const size_t wgs = (size_t)grid.x * grid.y;
-      size_t reserve = 0;
-      if (wgs <= 256) reserve = 96 * 1024;
-      else if (wgs <= 512) reserve = 56 * 1024;
-      if (reserve) {
-        static bool attr_done[16] = {};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-          e = hipFuncSetAttribute((const void*)k_msm_accum<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_msm_accum<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-          if (e != hipSuccess) return e;
-          if (dev >= 0 && dev < 16) attr_done[dev] = true;
-        }
-      }
-      const int top_local = (pl.nwin_total ? pl.nwin_total : pl.nwin) - 1 - pl.w0;
-      if (pl.top_tb && top_local >= 0 && top_local < pl.nwin)   // this launch holds a spread top window: it may be sparse
-        hipLaunchKernelGGL((k_msm_accum<D, true>), grid, dim3(256), reserve, st, pts_mont, sorted, acc_start, buckets, part_pts, part_meta, av, sg);
-      else
-        hipLaunchKernelGGL((k_msm_accum<D, false>), grid, dim3(256), reserve, st, pts_mont, sorted, acc_start, buckets, part_pts, part_meta, av, sg);
-    }
-    uint32_t* long_runs = (uint32_t*)(base + L.long_runs);
-    if (!small_sort) {
-      e = hipMemsetAsync(long_runs, 0, 16, st);
-      if (e != hipSuccess) return e;
-    }
-    // How many heads the owner of a run adds itself.  A bucket of m entries cut by lanes of `seg` entries has up to
-    // ceil(m / seg) heads; m is n / nb on average and rarely above m + 4 sqrt(m).  The seg that fills the chip in one
-    // round can be a third of that (verified G1 set of 2^17 points: 64 entries per bucket, seg 20), and with a fixed
-    // limit of 2 EVERY bucket went to the work list - 40 000 runs through 512 workgroups, 2.9 ms against 1.0 ms for the
-    // generic path.  A serial head costs one dependent addition (3 us); the work list is for real outliers (equal
-    // scalars, a short top window).
-    const double m_avg = (double)av.n / (double)av.nb;
-    const int heads_typ = (int)std::ceil((m_avg + 4.0 * std::sqrt(m_avg) + 1.0) / (double)sg.seg);
-    const int run_serial_auto = std::max(MSM_RUN_SERIAL, std::min(8, heads_typ));
-    const bool rs_forced = pl.run_serial_override >= 0;  // ncg_msm_set_tuning: exactly this many (tests force the work list)
-    const int run_serial = rs_forced ? pl.run_serial_override : run_serial_auto;
-    // the threshold the fix-up kernel actually runs with, decided ONCE (the trace reported another value than the launch
-    // used for per-window plans on the cooperative-units kernel)
-    const bool merge_units = (pl.shared || run_serial_auto >= 3) && CoopOK<D>::value;
-    // short segments (plans that do not fill the chip): a tree of MERGE_TREE_U units per bucket, up to 16 pieces
-    const bool merge_tree = merge_units && sg.seg < 16;
-    const int run_serial_eff = rs_forced ? run_serial : std::max(run_serial, merge_tree ? 15 : (merge_units || pl.shared) ? MSM_RUN_SERIAL_SHARED : MSM_RUN_SERIAL);
-    if (pl.trace) {
-      MsmTrace& tr = *pl.trace;
-      tr.c = pl.c; tr.nwin = pl.nwin; tr.nb = pl.nb; tr.seg = sg.seg; tr.nseg = sg.nseg; tr.w0 = pl.w0;
-      tr.nwin_total = pl.nwin_total ? pl.nwin_total : pl.nwin;
-      tr.run_serial = run_serial_eff;
-      tr.d_long_runs = (const uint32_t*)(base + L.long_runs);
-    }
-    // shared-bucket mode: every bucket holds nwin * n / nb entries, i.e. a handful of pieces - all of them, so their
-    // owners add them serially (fully parallel over the buckets), as cooperative groups where the curve has them;
-    // the work list is for the outliers only
-    // ... and the same kernel for per-window plans whose buckets are cut into three or more pieces as a rule (lanes of `seg`
-    // entries against buckets of n / nb: the two-window ranks of a window-sharded MSM run seg = 16 against 32-entry buckets):
-    // the owner's serial chain of 3-4 single-lane additions (~30 us each on a lone wave) was the longest kernel of such a share
-    // after the accumulate itself (138 us of 0.88 ms); four lanes per addition shorten every link of it
-    if (merge_tree) {
-      constexpr bool MCOOP = CoopOK<D>::value;
-      using K = TailOps<D, MCOOP>;
-      const dim3 mgrid((unsigned)((((size_t)av.nb << (K::UNIT_SHIFT + MERGE_TREE_ULOG)) + 255) / 256), av.nwin);
-      hipLaunchKernelGGL((k_msm_fixup_merge_tree<D, MCOOP>), mgrid, dim3(256), (size_t)(256 >> K::UNIT_SHIFT) * K::LDS_WORDS * 4, st, part_pts,
-                         part_meta, acc_start, buckets, av, sg, long_runs, run_serial_eff);
-    } else if (merge_units) {
-      constexpr bool MCOOP = CoopOK<D>::value;
-      using K = TailOps<D, MCOOP>;
-      const dim3 mgrid((unsigned)((((size_t)av.nb << K::UNIT_SHIFT) + 255) / 256), av.nwin);
-      hipLaunchKernelGGL((k_msm_fixup_merge_units<D, MCOOP>), mgrid, dim3(256), (size_t)(256 >> K::UNIT_SHIFT) * K::LDS_WORDS * 4, st, part_pts,
-                         part_meta, acc_start, buckets, av, sg, long_runs,
-                         // up to 8 pieces per bucket stay with the bucket's own unit (a cooperative addition is ~8 us; the work list costs
-                         // a launch-wide 120 us as soon as many buckets overflow - the top window of 254-bit scalars holds 64-entry buckets)
-                         run_serial_eff);
-    } else {
-      hipLaunchKernelGGL(k_msm_fixup_merge<D>, grid, dim3(256), 0, st, part_pts, part_meta, acc_start, buckets, av, sg, long_runs, run_serial_eff);
-    }
-    {
-      constexpr bool LCOOP = CoopOK<D>::value;
-      using K = TailOps<D, LCOOP>;
-      const size_t lds_b = (size_t)(MSM_TAIL_THREADS >> K::UNIT_SHIFT) * K::LDS_WORDS * 4;
-      static bool attr_done[16] = {};
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-        e = hipFuncSetAttribute((const void*)k_msm_fixup_long<D, LCOOP>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 16) attr_done[dev] = true;
-      }
-      hipLaunchKernelGGL((k_msm_fixup_long<D, LCOOP>), dim3(MSM_LONG_BLOCKS), dim3(MSM_TAIL_THREADS), lds_b, st, part_pts, buckets, av, sg,
-                         long_runs);
-    }
+  return hipSuccess;
+}
+
+// stage 3: bucket sums (lanes of sg.seg entries), then the pieces of every bucket that a lane boundary cut
+template <class C>
+static hipError_t msm_stage_accumulate(const MsmPlan& pl, const MsmSchedule& S, const MsmWs& W, hipStream_t st, MsmSideGuard& side) {
+  using D = typename DeviceCurve<C>::type;
+  constexpr bool COOP = CoopOK<D>::value;
+  const MsmPlan& av = S.av;
+  const MsmSeg sg = S.sg;
+  hipError_t e;
+  if (S.part_first && S.sort != MSM_SORT_SMALL) {
+    e = hipMemsetAsync(W.buckets, 0, (size_t)av.nwin * av.nb * MsmGroup<C>::ACC_WORDS * 4, st);  // empty buckets = infinity
+    if (e != hipSuccess) return e;
   }
-  if (!part_last) {  // more parts follow: the buckets stay as they are
-    *d_fin = nullptr;
-    if (d_bad) *d_bad = bad;
-    return hipGetLastError();
+  if (side.forked) {
+    e = hipStreamWaitEvent(st, side.side->join, 0);
+    if (e != hipSuccess) return e;
+    side.armed = false;
   }
-  // fold: nb -> 1 per window in c-1 levels.  Wide levels: one item per addition (throughput); levels that no longer
-  // fill the chip: four items per addition (latency, msm_coop.hpp); the last levels + the grouping: k_msm_tail.
-  // cooperative form wherever the group offers it (compile-time) and the level fits the resident lanes
-  constexpr bool CAN_COOP = CoopOK<D>::value;
-  constexpr bool coop = CAN_COOP;
-  const int tail_units = MSM_TAIL_THREADS >> (LS + (coop ? 2 : 0));
-  // lanes the chip keeps resident for these kernels (2 waves/SIMD): beyond that the cooperative form costs throughput
-  const long coop_max_tasks = (65536L * 2) >> (LS + 2);
-  const uint32_t* cur = buckets;
-  int narr = 1, n_in = av.nb, flip = 0;
-  {
-    static bool attr_done[16] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 16 || !attr_done[dev]) {
-      const int max_lds = 128 * 1024;
-      e = hipFuncSetAttribute((const void*)k_msm_tail<D, CAN_COOP>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 16) attr_done[dev] = true;
-    }
+  if (side.side && side.side->pts_ready) {  // host-pointer path: the points were still crossing PCIe while the sort ran
+    e = hipStreamWaitEvent(st, side.side->pts_ready, 0);
+    if (e != hipSuccess) return e;
   }
-  // a level that needs more than `tail_rounds` rounds of the tail workgroup's units is a launch of its own: chip-wide it costs
-  // 9-13 us, inside the tail 8-12 us PER ROUND (one workgroup per window)
-  constexpr int tail_rounds = 1;
-  while (n_in > 1 && (long)(narr + 1) * (n_in >> 1) > (long)tail_rounds * tail_units) {
-    const long total = (long)(narr + 1) * av.nwin * (n_in >> 1);
+  const dim3 grid(S.acc_grid.x, S.acc_grid.y);
+  if (S.acc_reserve) {   // a pinned grid (msm_plan.hpp MSM_ACC_PIN)
+    e = msm_lds_limit<k_msm_accum<D, true>>(W.dev, MSM_ACC_PIN[0].lds);
+    if (e == hipSuccess) e = msm_lds_limit<k_msm_accum<D, false>>(W.dev, MSM_ACC_PIN[0].lds);
+    if (e != hipSuccess) return e;
+  }
+  if (S.acc_sparse)   // this launch holds a spread top window: it may be sparse
+    hipLaunchKernelGGL((k_msm_accum<D, true>), grid, dim3(256), S.acc_reserve, st, W.pts_mont, W.sorted, W.acc_start, W.buckets, W.part_pts, W.part_meta, av, sg);
+  else
+    hipLaunchKernelGGL((k_msm_accum<D, false>), grid, dim3(256), S.acc_reserve, st, W.pts_mont, W.sorted, W.acc_start, W.buckets, W.part_pts, W.part_meta, av, sg);
+  if (S.sort != MSM_SORT_SMALL) {
+    e = hipMemsetAsync(W.long_runs, 0, 16, st);
+    if (e != hipSuccess) return e;
+  }
+  if (pl.trace) {
+    MsmTrace& tr = *pl.trace;
+    tr.c = pl.c; tr.nwin = pl.nwin; tr.nb = pl.nb; tr.seg = sg.seg; tr.nseg = sg.nseg; tr.w0 = pl.w0;
+    tr.nwin_total = pl.nwin_total ? pl.nwin_total : pl.nwin;
+    tr.run_serial = S.run_serial;
+    tr.d_long_runs = W.long_runs;
+  }
+  const dim3 mgrid(S.merge_grid.x, S.merge_grid.y);
+  if (S.merge == MSM_MERGE_TREE)
+    hipLaunchKernelGGL((k_msm_fixup_merge_tree<D, COOP>), mgrid, dim3(256), S.merge_lds, st, W.part_pts, W.part_meta, W.acc_start, W.buckets, av, sg,
+                       W.long_runs, S.run_serial);
+  else if (S.merge == MSM_MERGE_UNITS)
+    hipLaunchKernelGGL((k_msm_fixup_merge_units<D, COOP>), mgrid, dim3(256), S.merge_lds, st, W.part_pts, W.part_meta, W.acc_start, W.buckets, av, sg,
+                       W.long_runs, S.run_serial);
+  else
+    hipLaunchKernelGGL(k_msm_fixup_merge<D>, mgrid, dim3(256), 0, st, W.part_pts, W.part_meta, W.acc_start, W.buckets, av, sg, W.long_runs, S.run_serial);
+  e = msm_lds_limit<k_msm_fixup_long<D, COOP>>(W.dev, 128 * 1024);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_msm_fixup_long<D, COOP>), dim3(MSM_LONG_BLOCKS), dim3(MSM_TAIL_THREADS), S.long_lds, st, W.part_pts, W.buckets, av, sg,
+                     W.long_runs);
+  return hipSuccess;
+}
+
+// stage 4: the fold levels that are launches of their own, then the narrow levels and the grouping in k_msm_tail
+template <class C>
+static hipError_t msm_stage_fold(const MsmPlan& pl, const MsmSchedule& S, const MsmWs& W, hipStream_t st) {
+  using D = typename DeviceCurve<C>::type;
+  constexpr bool COOP = CoopOK<D>::value;
+  const MsmPlan& av = S.av;
+  const hipError_t e = msm_lds_limit<k_msm_tail<D, COOP>>(W.dev, 128 * 1024);
+  if (e != hipSuccess) return e;
+  const uint32_t* cur = W.buckets;
+  int narr = 1, n_in = av.nb;
+  for (int l = 0; l < S.nfold; l++, narr++, n_in >>= 1) {
+    uint32_t* out = W.red[l & 1];
     bool done = false;
-    if constexpr (CAN_COOP) {
-      if (coop && total <= coop_max_tasks) {
-        using K = TailOps<D, true>;
-        const size_t lds_b = (size_t)(256 >> K::UNIT_SHIFT) * COOP_SLOTS * G::FW * 4;
-        hipLaunchKernelGGL(k_msm_reduce_level_coop<D>, dim3((unsigned)(((total << K::UNIT_SHIFT) + 255) / 256)), dim3(256), lds_b, st,
-                           cur, red[flip], narr, av.nwin, n_in);
+    if constexpr (COOP) {
+      if (S.fold[l].coop) {
+        hipLaunchKernelGGL(k_msm_reduce_level_coop<D>, dim3(S.fold[l].grid), dim3(256), S.fold_coop_lds, st, cur, out, narr, av.nwin, n_in);
         done = true;
       }
     }
-    if (!done)
-      hipLaunchKernelGGL(k_msm_reduce_level<D>, dim3((unsigned)(((total << LS) + 255) / 256)), dim3(256), 0, st, cur, red[flip],
-                         narr, av.nwin, n_in);
-    cur = red[flip];
-    flip ^= 1;
-    narr++;
-    n_in >>= 1;
+    if (!done) hipLaunchKernelGGL(k_msm_reduce_level<D>, dim3(S.fold[l].grid), dim3(256), 0, st, cur, out, narr, av.nwin, n_in);
+    cur = out;
   }
-  const int ng = msm_ngroups(av.c);
-  {
-    uint32_t* t0 = (uint32_t*)(base + L.tail0);
-    uint32_t* t1 = (uint32_t*)(base + L.tail1);
-    uint32_t* fin = (uint32_t*)(base + L.fin);
-    using K = TailOps<D, CAN_COOP>;
-    hipLaunchKernelGGL((k_msm_tail<D, CAN_COOP>), dim3(av.nwin), dim3(MSM_TAIL_THREADS), (size_t)tail_units * K::LDS_WORDS * 4, st, cur,
-                       t0, t1, fin, narr, av.nwin, n_in, MSM_GROUP, ng,
-                       pl.top_tb ? (pl.nwin_total ? pl.nwin_total : pl.nwin) - 1 - pl.w0 : -1, pl.top_tb, pl.tail_flag, pl.tail_gen);
-    cur = fin;
-  }
-  *d_fin = cur;
-  if (d_bad) *d_bad = bad;
-  return hipGetLastError();
+  hipLaunchKernelGGL((k_msm_tail<D, COOP>), dim3(av.nwin), dim3(MSM_TAIL_THREADS), S.tail_lds, st, cur, W.tail0, W.tail1, W.fin, S.narr, av.nwin,
+                     S.n_in, MSM_GROUP, S.ngroups, S.top_w, pl.top_tb, pl.tail_flag, pl.tail_gen);
+  return hipSuccess;
 }
 
+// Device phase: everything up to the grouped window sums (ng x nwin accumulators, device memory,
+// inside the workspace).  Asynchronous on `st`.  The schedule is computed once; the stages launch what it says.
 template <class C>
-static size_t msm_fin_words_t(const MsmPlan& pl) {
-  return (size_t)msm_ngroups(pl.c) * msm_acc_view(pl).nwin * MsmGroup<C>::ACC_WORDS;
+static hipError_t msm_device_t(const MsmPlan& pl, const uint32_t* d_pts, const uint32_t* d_scalars, void* ws,
+                               const uint32_t** d_fin, hipStream_t st, const uint32_t** d_bad = nullptr,
+                               const MsmSide* side = nullptr) {
+  const MsmSchedule S = msm_schedule(pl, msm_shape(MsmCurveId<C>::value));
+  if ((!S.part_first || !S.part_last) && (pl.shared || pl.endo)) return hipErrorInvalidValue;  // parts: generic plans only
+  const MsmLayout& L = S.layout;
+  char* base = (char*)ws;
+  auto at = [&](size_t off) { return (uint32_t*)(base + off); };
+  MsmWs W{at(L.pts_mont), (int16_t*)(base + L.digits), at(L.counts), at(L.bucket_start), at(L.sorted), at(L.sort_tmp), at(L.shared_start),
+          at(L.buckets), at(L.part_pts), (int*)(base + L.part_meta), at(L.long_runs), at(L.bad), {at(L.red0), at(L.red1)}, at(L.tail0),
+          at(L.tail1), at(L.fin), nullptr, 0};
+  W.acc_start = pl.shared ? W.shared_start : W.bstart;
+  (void)hipGetDevice(&W.dev);
+  MsmSideGuard side_guard{side};
+  hipError_t e = msm_stage_points<C>(pl, S, W, d_pts, d_scalars, st, side_guard);
+  if (e == hipSuccess) e = msm_stage_sort(pl, S, W, d_scalars, MsmGroup<C>::ACC_WORDS, st);
+  if (e == hipSuccess) e = msm_stage_accumulate<C>(pl, S, W, st, side_guard);
+  if (e == hipSuccess && S.part_last) e = msm_stage_fold<C>(pl, S, W, st);  // not the last part: the buckets stay as they are
+  if (e != hipSuccess) return e;
+  *d_fin = S.part_last ? W.fin : nullptr;
+  if (d_bad) *d_bad = W.bad;
+  return hipGetLastError();
 }
 
 template <class C> struct FinishHelpers { static constexpr bool value = false; };   // curves whose host finish runs over helper threads
@@ -1824,7 +1631,7 @@ static hipError_t msm_enqueue_t(const MsmPlan& pl, const uint32_t* d_pts, const 
   const uint32_t *d_fin = nullptr, *d_bad = nullptr;
   hipError_t e = msm_device_t<C>(pl, d_pts, d_scalars, ws, &d_fin, st, &d_bad, side);
   if (e != hipSuccess) return e;
-  const size_t fin_words = msm_fin_words_t<C>(pl);
+  const size_t fin_words = msm_fin_words(MsmCurveId<C>::value, pl);
   e = hipMemcpyAsync(land, d_fin, fin_words * 4, hipMemcpyDeviceToHost, st);
   if (e != hipSuccess) return e;
   return hipMemcpyAsync(land + fin_words, d_bad, 4, hipMemcpyDeviceToHost, st);
@@ -1942,56 +1749,17 @@ void msm_finish_prewake(int curve) {
     h64::FinishPool::get().wake();
 }
 void msm_finish_host(int curve, int c, int nwin, const uint32_t* fin_host, uint32_t* out_affine_host, uint8_t* out_inf_host) {
-  switch (curve) {
-    case CURVE_SECP256K1: return msm_host_finish_any<CurveSecp>(fin_host, c, nwin, out_affine_host, out_inf_host);
-    case CURVE_BLS12_381_G1: return msm_host_finish_any<CurveG1>(fin_host, c, nwin, out_affine_host, out_inf_host);
-    case CURVE_BLS12_381_G2: return msm_host_finish_any<CurveG2>(fin_host, c, nwin, out_affine_host, out_inf_host);
-    case CURVE_ED25519: return msm_host_finish_any<CurveEd>(fin_host, c, nwin, out_affine_host, out_inf_host);
-    case CURVE_BN254_G1: return msm_host_finish_any<CurveBn254>(fin_host, c, nwin, out_affine_host, out_inf_host);
-    default: return;
-  }
+  (void)[&]() -> hipError_t {
+#define CALL(C) (msm_host_finish_any<C>(fin_host, c, nwin, out_affine_host, out_inf_host), hipSuccess)
+    NCG_MSM_DISPATCH(curve, CALL)
+#undef CALL
+  }();
 }
-size_t msm_fin_words(int curve, const MsmPlan& pl) {
-  switch (curve) {
-    case CURVE_SECP256K1: return msm_fin_words_t<CurveSecp>(pl);
-    case CURVE_BLS12_381_G1: return msm_fin_words_t<CurveG1>(pl);
-    case CURVE_BLS12_381_G2: return msm_fin_words_t<CurveG2>(pl);
-    case CURVE_ED25519: return msm_fin_words_t<CurveEd>(pl);
-    case CURVE_BN254_G1: return msm_fin_words_t<CurveBn254>(pl);
-    default: return 0;
-  }
-}
-size_t msm_acc_words(int curve) {
-  switch (curve) {
-    case CURVE_SECP256K1: return MsmGroup<CurveSecp>::ACC_WORDS;
-    case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::ACC_WORDS;
-    case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::ACC_WORDS;
-    case CURVE_ED25519: return MsmGroup<CurveEd>::ACC_WORDS;
-    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::ACC_WORDS;
-    default: return 0;
-  }
-}
-
+size_t msm_fin_words(int curve, const MsmPlan& pl) { return (size_t)msm_ngroups(pl.c) * msm_acc_view(pl).nwin * msm_shape(curve).acc_words; }
+size_t msm_acc_words(int curve) { return msm_shape(curve).acc_words; }
+size_t msm_stored_words_per_point(int curve) { return msm_shape(curve).aff_words; }
 size_t msm_workspace_bytes(int curve, const MsmPlan& pl) {
-  switch (curve) {
-    case CURVE_SECP256K1: return msm_layout<CurveSecp>(pl).total;
-    case CURVE_BLS12_381_G1: return msm_layout<CurveG1>(pl).total;
-    case CURVE_BLS12_381_G2: return msm_layout<CurveG2>(pl).total;
-    case CURVE_ED25519: return msm_layout<CurveEd>(pl).total;
-    case CURVE_BN254_G1: return msm_layout<CurveBn254>(pl).total;
-    default: return 0;
-  }
-}
-
-size_t msm_stored_words_per_point(int curve) {
-  switch (curve) {
-    case CURVE_SECP256K1: return MsmGroup<CurveSecp>::AFF_WORDS;
-    case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::AFF_WORDS;
-    case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::AFF_WORDS;
-    case CURVE_ED25519: return MsmGroup<CurveEd>::AFF_WORDS;
-    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::AFF_WORDS;
-    default: return 0;
-  }
+  return msm_shape(curve).acc_words ? msm_schedule(pl, msm_shape(curve)).layout.total : 0;
 }
 hipError_t msm_points_to_stored(int curve, const uint32_t* d_pts_wire, int n, uint32_t* d_out, hipStream_t st) {
 #define CALL(C) msm_points_to_stored_t<C>(d_pts_wire, n, d_out, st)
@@ -2005,14 +1773,9 @@ hipError_t msm_run(int curve, const MsmPlan& pl, const uint32_t* d_pts, const ui
   uint32_t dummy = 0xFFFFFFFFu;
   if (!bad_index) bad_index = &dummy;
   *bad_index = 0xFFFFFFFFu;
-  switch (curve) {
-    case CURVE_SECP256K1: return msm_run_t<CurveSecp>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
-    case CURVE_BLS12_381_G1: return msm_run_t<CurveG1>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
-    case CURVE_BLS12_381_G2: return msm_run_t<CurveG2>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
-    case CURVE_ED25519: return msm_run_t<CurveEd>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
-    case CURVE_BN254_G1: return msm_run_t<CurveBn254>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side);
-    default: return hipErrorInvalidValue;
-  }
+#define CALL(C) msm_run_t<C>(pl, d_pts, d_scalars, ws, out_affine_host, out_inf_host, st, bad_index, side)
+  NCG_MSM_DISPATCH(curve, CALL)
+#undef CALL
 }
 
 #endif  // NCG_MSM_TU_G1

@@ -57,6 +57,26 @@ inline const uint32_t* curve_order(int curve) {
   }
 }
 
+// The integers of a curve's MSM kernels that the host-side planning needs (msm.hip asserts each against the templates it restates:
+// MsmGroup<C>::AFF_WORDS, ACC_WORDS, WIRE_AFF, LaneShift<D>, CoopOK<D> of the device form D of the curve).
+struct MsmShape {
+  int aff_words;   // stored words per input point
+  int acc_words;   // words per bucket accumulator
+  int wire_words;  // wire words per input point
+  int ls;          // lanes per item = 1 << ls (lane-paired Fp2 kernels)
+  bool coop;       // the fix-up / fold / tail kernels have cooperative units (msm_coop.hpp)
+};
+constexpr MsmShape msm_shape(int curve) {
+  switch (curve) {
+    case CURVE_SECP256K1: return {18, 36, 16, 0, false};
+    case CURVE_BLS12_381_G1: return {28, 56, 24, 0, true};
+    case CURVE_BLS12_381_G2: return {56, 112, 48, 1, true};
+    case CURVE_ED25519: return {27, 36, 16, 0, false};
+    case CURVE_BN254_G1: return {18, 36, 16, 0, false};
+    default: return {0, 0, 0, 0, false};
+  }
+}
+
 inline int ilog2(unsigned x) {
   int r = 0;
   while (x >>= 1) r++;
@@ -135,7 +155,7 @@ inline int msm_make_plan_impl(int curve, int n, int c_override, MsmPlan* pl) {
   }
   c = std::max(2, std::min(16, c));
   pl->n = n;
-  pl->ls = curve == CURVE_BLS12_381_G2 ? 1 : 0;  // lane-paired kernels: 2 lanes per item
+  pl->ls = msm_shape(curve).ls;  // lane-paired kernels: 2 lanes per item
   // waves/SIMD the accumulate kernel runs at (registers): 4 for the 256-bit fields, 2 for bls12-381 G1, 1 for G2
   pl->accum_waves = (curve == CURVE_SECP256K1 || curve == CURVE_ED25519 || curve == CURVE_BN254_G1) ? 4
                     : curve == CURVE_BLS12_381_G2 ? G2_ACCUM_WAVES : 2;
@@ -162,6 +182,14 @@ struct MsmSeg {
   int seg;    // entries per lane
   int nseg;   // lanes per window = ceil(n / seg)
 };
+// A grid of at most two workgroups per CU is latency-bound (every lane's chain of `seg` additions on a wave that has its SIMD
+// to itself, or shares it with one other), and the dispatcher does not spread workgroups evenly: 238 workgroups on 256 CUs ran
+// 18.5 us per addition where 104 ran 12.  An LDS reservation the kernel never touches makes the placement explicit: with
+// 96 KB per workgroup a CU (160 KB) takes one, with 56 KB two.  The accumulate launch reserves it (msm_schedule), msm_seg prices it.
+struct MsmAccPin { long max_wgs; size_t lds; };
+constexpr MsmAccPin MSM_ACC_PIN[2] = {{256, 96 * 1024}, {512, 56 * 1024}};
+// workgroups per CU a grid of `wgs` workgroups is pinned to; 0 = the grid is not pinned
+constexpr int msm_acc_pinned(long wgs) { return wgs <= MSM_ACC_PIN[0].max_wgs ? 1 : wgs <= MSM_ACC_PIN[1].max_wgs ? 2 : 0; }
 inline MsmSeg msm_seg(const MsmPlan& pl) {
   MsmSeg sg;
   if (pl.seg_override > 0) {   // ncg_msm_set_tuning
@@ -192,9 +220,10 @@ inline MsmSeg msm_seg(const MsmPlan& pl) {
       const long rounds = (lanes + cap - 1) / cap;
       double cost;
       if (lanes <= cap) {
-        // waves per SIMD: the accumulate launch pins grids of up to 256 / 512 workgroups to one / two per CU (LDS reservation)
+        // waves per SIMD: the accumulate launch pins small grids to one / two workgroups per CU (MSM_ACC_PIN)
         const long wgs = (long)pl.nwin * (((nseg << pl.ls) + 255) / 256);
-        const double k = wgs <= 256 ? 1.0 : wgs <= 512 ? 2.0 : (double)((lanes + 65535) / 65536);
+        const int pin = msm_acc_pinned(wgs);
+        const double k = pin ? (double)pin : (double)((lanes + 65535) / 65536);
         // pieces of the fullest buckets: (m + 4 sqrt(m)) / seg + 1; the merge adds them as a tree of four units per bucket where the
         // curve has cooperative units (k_msm_fixup_merge_tree), one after the other elsewhere
         const double pieces = (m + 4.0 * std::sqrt(m)) / (double)seg + 1.0;
@@ -214,16 +243,5 @@ inline MsmSeg msm_seg(const MsmPlan& pl) {
   return sg;
 }
 
-
-inline size_t msm_acc_words_inl(int curve) {
-  switch (curve) {
-    case CURVE_SECP256K1: return MsmGroup<CurveSecp>::ACC_WORDS;
-    case CURVE_BLS12_381_G1: return MsmGroup<CurveG1>::ACC_WORDS;
-    case CURVE_BLS12_381_G2: return MsmGroup<CurveG2>::ACC_WORDS;
-    case CURVE_ED25519: return MsmGroup<CurveEd>::ACC_WORDS;
-    case CURVE_BN254_G1: return MsmGroup<CurveBn254>::ACC_WORDS;
-    default: return 0;
-  }
-}
 
 }  // namespace ncg

@@ -41,7 +41,7 @@ inline size_t msm_shard_max_fin_words(int curve) {
   for (int c = 2; c <= 16; c++) {
     MsmPlan pl;
     if (msm_make_plan_impl(curve, 1 << 20, c, &pl) != 0) continue;
-    best = std::max(best, (size_t)msm_ngroups(pl.c) * pl.nwin * msm_acc_words_inl(curve));
+    best = std::max(best, (size_t)msm_ngroups(pl.c) * pl.nwin * msm_shape(curve).acc_words);
   }
   return best;
 }
@@ -59,7 +59,7 @@ inline void msm_shard_window_range(int nwin, int part, int nparts, int* w0, int*
 
 // returns -1 if every header matches the whole plan `pl` and the mode's layout, else the first offending rank (message in `msg`)
 inline int msm_shard_check(const FinHeader* hs, int nparts, int curve, const MsmPlan& pl, uint32_t mode, char* msg, size_t msg_len) {
-  const size_t xw = msm_acc_words_inl(curve);
+  const size_t xw = msm_shape(curve).acc_words;
   const uint32_t ng = (uint32_t)msm_ngroups(pl.c);
   uint32_t next_w = 0;
   for (int r = 0; r < nparts; r++) {
@@ -101,7 +101,7 @@ inline int msm_shard_first_bad(const FinHeader* hs, int nparts, uint32_t* idx) {
 // SHARD_WINDOWS: the slots' [ngroups][wcnt_r] arrays (host memory, `stride` bytes apart) -> one [ngroups][nwin] array
 inline void msm_shard_assemble_windows(const uint8_t* slots, size_t stride, const FinHeader* hs, int nparts, int curve, const MsmPlan& pl,
                                        uint32_t* fin_out) {
-  const size_t xw = msm_acc_words_inl(curve);
+  const size_t xw = msm_shape(curve).acc_words;
   const int ng = msm_ngroups(pl.c);
   for (int r = 0; r < nparts; r++) {
     const uint32_t* src = (const uint32_t*)(slots + stride * (size_t)r + sizeof(FinHeader));

@@ -45,6 +45,7 @@ def lib():
         _lib.ht_msm_plan.argtypes = [i32, i32, vp]
         _lib.ht_msm_seg.argtypes = [i32, i32, i32, vp]
         _lib.ht_msm_plan_top.argtypes = [i32, i32, i32, vp]
+        _lib.ht_msm_schedule.argtypes = [i32, i32, i32, vp, vp]
         _lib.ht_h64_op.argtypes = [i32, vp, vp, vp, vp]
         _lib.ht_fe9_fused.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
         _lib.ht_jac_neg.argtypes = [i32, vp, vp, vp, vp]
@@ -364,3 +365,27 @@ def msm_seg(curve, n, c_override=0):
     out = np.zeros(8, dtype=np.int32)
     assert lib().ht_msm_seg(curve, n, c_override, out.ctypes.data) == 0
     return dict(zip(("c", "nwin", "nb", "seg", "nseg", "lanes", "accum_waves"), [int(x) for x in out[:7]]))
+
+
+MSM_LAYOUT_REGIONS = ("pts_mont", "digits", "counts", "bucket_start", "sorted", "sort_tmp", "shared_start", "buckets", "part_pts", "part_meta",
+                      "long_runs", "bad", "red0", "red1", "tail0", "tail1", "fin")
+MSM_SCHEDULE_FIELDS = MSM_LAYOUT_REGIONS + (
+    "total", "c", "nwin", "nb", "Q", "av_n", "av_nwin", "top_tb", "ls", "coop", "part_first", "part_last", "pts_in_place", "pts_grid",
+    "digits_grid", "sort", "s2_lgr", "sort_grid_x", "sort_grid_y", "small_lds", "hist_lds", "scan_lds", "split_totals", "totals_grid_x",
+    "totals_grid_y", "shared_grid", "scatter_n", "scatter_per", "seg", "nseg", "acc_grid_x", "acc_grid_y", "acc_reserve", "acc_sparse",
+    "seg_pin", "run_serial", "merge", "merge_grid_x", "merge_grid_y", "merge_lds", "long_lds", "nfold", "fold_coop_lds", "narr", "n_in",
+    "tail_units", "tail_lds", "ngroups", "top_w", "long_blocks", "tail_threads", "sort2_stage_lds")
+
+
+def msm_schedule(curve, n, c_override=0, endo=False, shared=False, part_flags=3, n_layout=0, w0=0, wcnt=0, seg=0, run_serial=-1,
+                 pts_stored=False):
+    """The launch schedule (csrc/msm_schedule.hpp) of the plan an entry point would build: a dict of MSM_SCHEDULE_FIELDS plus
+    "fold" = [(tasks, coop, grid)] of the stand-alone fold levels.  sort: 0 one-launch, 1 two-level, 2 one-level; merge: 0 plain,
+    1 units, 2 tree; seg_pin: workgroups per CU msm_seg prices the accumulate grid at (0: not pinned)."""
+    opt = np.array([endo, shared, part_flags, n_layout, w0, wcnt, seg, run_serial, pts_stored], dtype=np.int32)
+    out = np.zeros(len(MSM_SCHEDULE_FIELDS) + 48, dtype=np.int64)
+    assert lib().ht_msm_schedule(curve, n, c_override, opt.ctypes.data, out.ctypes.data) == len(MSM_SCHEDULE_FIELDS)
+    S = dict(zip(MSM_SCHEDULE_FIELDS, (int(x) for x in out)))
+    lv = out[len(MSM_SCHEDULE_FIELDS):].reshape(16, 3)
+    S["fold"] = [tuple(int(x) for x in lv[i]) for i in range(S["nfold"])]
+    return S
