@@ -11,6 +11,7 @@
 //   encodePoints(curveId, points)                    -> Uint8Array n * (EB + 1)  (encodings, ok flags)
 //   aggregateEncoded(curveId, encoded, zip215)       -> Uint8Array PB + 1 (flag); throws naming a bad index
 //   ntt(log2n, omega: Uint8Array 32, data, flags, field = 0) -> Uint8Array (same length); field: NCG_FIELD_* of ncg.h
+//   poly(kind, field, a, b, small, i1, i2)           -> Uint8Array; the ncg_poly_* family on packed 32-byte elements (see Poly below)
 //   mapToCurve(curveId, count, u)                    -> Uint8Array n * (PB + 1)
 //   pointBytes(curveId) / version()
 // Buffers use the wire format of include/ncg.h.  Build: make -C addon  (g++ + /usr/include/node).
@@ -712,6 +713,62 @@ static napi_value Ntt(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// poly(kind, field, a, b, small, i1, i2): one entry for the polynomial operations of include/ncg.h.  a, b: packed 32-byte
+// little-endian elements (or null); small: the host operands; returns the packed result.
+//   kind 0 pointwise   i1 = NCG_POLY_ADD | SUB | DOT                              -> n elements
+//        1 scale       small = scalar (32 bytes), i1 = powers (0: a[i] s, 1: a[i] s^i) -> n elements
+//        2 eval        sum a[i] b[i]                                              -> 1 element
+//        3 evalMonomial small = m points (m * 32 bytes)                           -> m elements
+//        4 lagrangeBasis small = omega || x (64 bytes), i1 = log2n, i2 = brp      -> 2^log2n elements
+//        5 mul         small = omega (32 bytes), i1 = log2n; a, b at most 2^log2n elements each -> 2^log2n elements
+static napi_value Poly(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind = -1, field = 0, i1 = 0, i2 = 0;
+  uint8_t *a = nullptr, *b = nullptr, *sm = nullptr, *out = nullptr;
+  size_t al = 0, bl = 0, sl = 0;
+  bool ok = argc >= 5 && napi_get_value_int32(env, argv[0], &kind) == napi_ok && napi_get_value_int32(env, argv[1], &field) == napi_ok;
+  if (ok) {
+    get_u8(env, argv[2], &a, &al);   // null / undefined leave the operand empty
+    get_u8(env, argv[3], &b, &bl);
+    get_u8(env, argv[4], &sm, &sl);
+    if (argc >= 6) napi_get_value_int32(env, argv[5], &i1);
+    if (argc >= 7) napi_get_value_int32(env, argv[6], &i2);
+    ok = al % 32 == 0 && bl % 32 == 0 && sl % 32 == 0;
+  }
+  const size_t n = al / 32;
+  const bool bits_ok = i1 >= 0 && i1 <= NCG_NTT_MAX_LOG2N;
+  switch (ok ? kind : -1) {
+    case 0: ok = bl == al; break;
+    case 1: ok = sl == 32; break;
+    case 2: ok = bl == al; break;
+    case 3: ok = sl >= 32 && sl <= 32 * NCG_POLY_MAX_POINTS; break;
+    case 4: ok = sl == 64 && bits_ok; break;
+    case 5: ok = sl == 32 && bits_ok && n <= ((size_t)1 << i1) && bl / 32 <= ((size_t)1 << i1); break;
+    default: ok = false;
+  }
+  if (!ok) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: poly(kind, field, a, b, small, i1, i2)");
+    return nullptr;
+  }
+  const size_t out_elems = kind <= 1 ? n : kind == 2 ? 1 : kind == 3 ? sl / 32 : (size_t)1 << i1;
+  napi_value res = make_u8(env, out_elems * 32, &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  switch (kind) {
+    case 0: rc = ncg_poly_pointwise(g_ctx, field, i1, n, a, b, out); break;
+    case 1: rc = ncg_poly_scale(g_ctx, field, n, a, sm, i1, out); break;
+    case 2: rc = ncg_poly_eval(g_ctx, field, n, a, b, out); break;
+    case 3: rc = ncg_poly_eval_monomial(g_ctx, field, n, a, (int)(sl / 32), sm, out); break;
+    case 4: rc = ncg_poly_lagrange_basis(g_ctx, field, i1, sm, sm + 32, i2, out); break;
+    default: rc = ncg_poly_mul(g_ctx, field, i1, sm, n, a, bl / 32, b, out); break;
+  }
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
 static napi_value MapToCurve(napi_env env, napi_callback_info info) {
   size_t argc = 3;
   napi_value argv[3];
@@ -824,7 +881,7 @@ NAPI_MODULE_INIT() {
              {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
-             {"ntt", Ntt},               {"mapToCurve", MapToCurve},
+             {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},
              {"packBigInts", PackBigInts}, {"unpackBigInts", UnpackBigInts}, {"uploadPoints", UploadPoints}, {"freePoints", FreePoints}, {"verifySubgroup", VerifySubgroup}, {"precomputePoints", PrecomputePoints}, {"inSubgroup", InSubgroup},
              {"msmResident", MsmResident}, {"mulVarResident", MulVarResident},
              {"ed25519VerifyMsgs", Ed25519VerifyMsgs}, {"ecdsaVerify", EcdsaVerify}, {"secpVerifyMsgs", SecpVerifyMsgs}, {"ecdsaRecover", EcdsaRecover},

@@ -6,6 +6,9 @@
 //                                            (src/abstract/weierstrass.ts:915-928)
 //   multiplyBaseBatch(c, scalars)          - array form of BASE.multiply (curve.ts:588-606)
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
+//   fftFr(values, opts)                    - FFT(roots, Fr).direct / .inverse (abstract/fft.ts:518-577)
+//   polyFr(opts)                           - poly(Fr, roots, ...) on arrays of bigint (abstract/fft.ts:583-926): add, sub, dot,
+//                                            mul, convolve, shift, eval, monomial.eval, lagrange.basis / eval
 // `c` is any Point constructor with the reference's CurvePointCons surface (BASE, ZERO, Fp, Fn,
 // fromAffine; curve.ts:159-195) that was registered with `register(c, curveId)`; points are
 // instances of it (toAffine()).  Plain CommonJS + BigInt so it also loads on old Node.
@@ -554,6 +557,109 @@ function fftFr(values, opts) {                  // opts: { inverse, brpInput, br
   return values.map((_, i) => leNumber(out, 32 * i, 32));
 }
 
+// ---- poly(Fr, roots, create?, fft?, length?) of the reference (fft.ts:583-926) over the same two fields, on arrays of bigint:
+// polyFr(opts) with opts.field / opts.generator as for fftFr (and opts.length, opts.fft: truthy = "an FFT was passed") returns
+// { add, sub, dot, mul, convolve, shift, eval, monomial: { eval }, lagrange: { eval } } with the reference's messages; the vector
+// work runs in ncg_poly_* (native.poly).
+function polyFr(opts) {
+  opts = opts || {};
+  const fld = FFT_FIELDS[opts.field || 'bls12_381'];
+  if (!fld) throw new Error('noble-gpu: polyFr: unknown field ' + opts.field + ' (bls12_381, bn254)');
+  const R = fld.order, length = opts.length, G = opts.generator || 7n;
+  const isPow2 = (n) => n > 0 && (n & (n - 1)) === 0;
+  const nextPow2 = (n) => { let p = 1; while (p < n) p *= 2; return p; };
+  const log2 = (n) => 31 - Math.clz32(n);
+  const omegaOf = (bits) => {
+    if (bits > fld.twoAdicity) throw new Error('rootsOfUnity: wrong bits ' + bits + ' powerOfTwo=' + fld.twoAdicity);
+    return powMod(G, (R - 1n) >> BigInt(bits), R);
+  };
+  const elem = (v) => {
+    if (typeof v !== 'bigint' || v < 0n || v >= R) throw new Error('invalid field element: outside of range 0..ORDER');
+    return v;
+  };
+  const pack = (vals) => { const d = new Uint8Array(vals.length * 32); vals.forEach((v, i) => leBytes(elem(v), 32, d, 32 * i)); return d; };
+  const unpack = (buf) => { const out = new Array(buf.length / 32); for (let i = 0; i < out.length; i++) out[i] = leNumber(buf, 32 * i, 32); return out; };
+  const checkPoly = (title, v) => { if (!Array.isArray(v)) throw new TypeError(`"${title}" expected polynomial, got type=${typeof v}`); };
+  const checkFixed = (L) => { if (length !== undefined && L !== length) throw new Error(`poly: expected fixed length ${length}, got ${L}`); };
+  const checkLength = (a, b) => {
+    checkPoly('a', a);
+    const L = a.length;
+    if (b !== undefined) {
+      checkPoly('b', b);
+      if (b.length !== L) throw new Error(`poly: mismatched lengths ${L} vs ${b.length}`);
+    }
+    checkFixed(L);
+    return L;
+  };
+  const call = (kind, a, b, small, i1, i2) => { init(); return native.poly(kind, fld.id, a, b, small, i1 || 0, i2 || 0); };
+  const pointwise = (op) => (a, b) => {
+    const L = checkLength(a, b), A = pack(a), B = pack(b);
+    return L ? unpack(call(0, A, B, null, op)) : [];
+  };
+  const cyclic = (bits, A, B) => call(5, A, B, pack([omegaOf(bits)]), bits);
+  const lagrangeBits = (n) => {
+    if (!isPow2(n)) throw new Error('poly.lagrange: expected power of two length, got ' + n);
+    return log2(n);
+  };
+  const lagrangeBasis = (x, n, brp) => {
+    const bits = lagrangeBits(n);
+    return call(4, null, null, pack([omegaOf(bits), elem(x)]), bits, brp ? 1 : 0);
+  };
+  const api = {
+    length,
+    add: pointwise(0),
+    sub: pointwise(1),
+    dot: pointwise(2),
+    mul(a, b) {
+      if (!Array.isArray(b)) {
+        const L = checkLength(a), A = pack(a), s = pack([b]);
+        return L ? unpack(call(1, A, null, s, 0)) : [];
+      }
+      const L = checkLength(a, b);
+      if (L && !isPow2(L) && opts.fft) throw new Error('FFT: Polynomial size should be power of two');
+      const A = pack(a), B = pack(b);
+      if (!L) return [];
+      if (isPow2(L)) return unpack(cyclic(log2(L), A, B));
+      const full = cyclic(log2(nextPow2(2 * L - 1)), A, B);   // the quadratic product mod x^L - 1 (:816-824): linear product, folded
+      return unpack(call(0, full.subarray(0, 32 * L), full.subarray(32 * L, 64 * L), null, 0));
+    },
+    convolve(a, b) {
+      checkPoly('a', a);
+      checkPoly('b', b);
+      const n = nextPow2(a.length + b.length - 1);
+      checkFixed(a.length); checkFixed(b.length); checkFixed(n);
+      return unpack(cyclic(log2(n), pack(a), pack(b)));
+    },
+    shift(p, factor) {
+      checkPoly('p', p);
+      checkFixed(p.length);
+      const P = pack(p), f = pack([factor]);
+      return p.length ? unpack(call(1, P, null, f, 1)) : [];
+    },
+    eval(a, basis) {
+      checkLength(a, basis);
+      return unpack(call(2, pack(a), pack(basis), null))[0];
+    },
+    monomial: {
+      eval(a, x) {
+        checkLength(a);
+        return unpack(call(3, pack(a), null, pack([x])))[0];
+      },
+    },
+    lagrange: {
+      basis: (x, n, brp) => unpack(lagrangeBasis(x, n, brp)),
+      eval(a, x, brp) {
+        const L = checkLength(a);
+        lagrangeBits(L);
+        const A = pack(a);
+        const basis = lagrangeBasis(x, L, brp);      // the delta when x is a root: the sum is then a[idx], the reference's fast path
+        return unpack(call(2, A, basis, null))[0];
+      },
+    },
+  };
+  return api;
+}
+
 // ---- hash-to-curve for bls12-381 G1 / G2: createHasher(...).hashToCurve (hash-to-curve.ts:441-548) -
 const BLS_P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaabn;
 function expandMessageXmd(msg, dst, len) {      // hash-to-curve.ts:189-228 with SHA-256
@@ -590,4 +696,4 @@ function hashToCurveBatch(c, msgs, DST) {
 
 module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, DEFAULT_MIN_POINTS, setPointCache, clearPointCache, packPoints, packScalars, pippenger, multiplyUnsafeBatch, multiplyBaseBatch, ed25519VerifyBatch,
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
-                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, hashToCurveBatch, native };
+                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, native };

@@ -190,6 +190,55 @@ int ncg_ntt(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* omega,
 int ncg_ntt_dev(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* omega,
                 const void* in_dev, void* out_dev, int flags, void* stream);
 
+/* ---- polynomial arithmetic on vectors of scalar-field elements ------------------------------------
+ * The device side of the reference's poly(field, roots, create?, fft?, length?) (src/abstract/fft.ts:583-926)
+ * for the two fields of the NTT (NCG_FIELD_BLS12_381_FR, NCG_FIELD_BN254_FR; every other field id returns
+ * NCG_ERR_UNSUPPORTED).  Elements: canonical residues, 32 bytes little-endian, in and out.  Every operation
+ * has a host-pointer form and a _dev form on resident, 16-byte aligned buffers with a trailing stream; the
+ * small operands (scalar, xs, x, omega) are HOST pointers in both forms, as omega is for ncg_ntt_dev.  The
+ * _dev forms share one workspace per context: one call at a time per context, and nothing synchronises
+ * with the host.
+ *   pointwise       out[i] = a[i] + b[i] | a[i] - b[i] | a[i] * b[i]  (add / sub / dot, :789-806); out may
+ *                   alias a or b.
+ *   scale           powers = 0: out[i] = a[i] * s  (mul by a scalar, :826-830);
+ *                   powers = 1: out[i] = a[i] * s^i  (shift, :838-850; 0^0 = 1).  out may alias a.
+ *   eval            out32 = sum a[i] * basis[i]  (:857-862).
+ *   eval_monomial   out[k] = sum a[i] * xs[k]^i for m <= NCG_POLY_MAX_POINTS points in one pass over a
+ *                   (monomial.eval, :873-879).
+ *   lagrange_basis  out[i] = L_i(x) over the N = 2^log2n roots of unity roots(log2n) of `omega` (the table of
+ *                   ncg_ntt, cached the same way; bit-reversed order when brp is set), :882-901.  If x is
+ *                   itself root i the result is the Kronecker delta at i (the reference's shortcut).
+ *   mul             out = inverse(direct(a, brpOutput) .* direct(b, brpOutput), brpInput) of length N =
+ *                   2^log2n: the cyclic product mod x^N - 1 (mul with an FFT, :810-814).  a and b hold
+ *                   na, nb <= N coefficients and are zero-extended on the device, so na + nb - 1 <= N gives
+ *                   convolve (:832-837).  na = 0 or nb = 0 gives the zero polynomial.  out may alias a or b.
+ * n = 0: the vector operations return NCG_OK and touch nothing; the two evaluations write zero, so their
+ * output is required even then. */
+#define NCG_POLY_ADD 0
+#define NCG_POLY_SUB 1
+#define NCG_POLY_DOT 2
+#define NCG_POLY_MAX_POINTS 8
+int ncg_poly_pointwise(ncg_ctx* ctx, int field, int op, size_t n, const void* a, const void* b, void* out);
+int ncg_poly_pointwise_dev(ncg_ctx* ctx, int field, int op, size_t n, const void* a_dev, const void* b_dev,
+                           void* out_dev, void* stream);
+int ncg_poly_scale(ncg_ctx* ctx, int field, size_t n, const void* a, const void* scalar, int powers, void* out);
+int ncg_poly_scale_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, const void* scalar, int powers,
+                       void* out_dev, void* stream);
+int ncg_poly_eval(ncg_ctx* ctx, int field, size_t n, const void* a, const void* basis, void* out32);
+int ncg_poly_eval_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, const void* basis_dev,
+                      void* out32_dev, void* stream);
+int ncg_poly_eval_monomial(ncg_ctx* ctx, int field, size_t n, const void* a, int m, const void* xs, void* out);
+int ncg_poly_eval_monomial_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, int m, const void* xs,
+                               void* out_dev, void* stream);
+int ncg_poly_lagrange_basis(ncg_ctx* ctx, int field, int log2n, const void* omega, const void* x, int brp,
+                            void* out);
+int ncg_poly_lagrange_basis_dev(ncg_ctx* ctx, int field, int log2n, const void* omega, const void* x, int brp,
+                                void* out_dev, void* stream);
+int ncg_poly_mul(ncg_ctx* ctx, int field, int log2n, const void* omega, size_t na, const void* a, size_t nb,
+                 const void* b, void* out);
+int ncg_poly_mul_dev(ncg_ctx* ctx, int field, int log2n, const void* omega, size_t na, const void* a_dev,
+                     size_t nb, const void* b_dev, void* out_dev, void* stream);
+
 /* ---- batch fixed-base scalar multiplication -----------------------------------------------
  * out[i] = scalars[i] * BASE.  Replaces, batch-wise, Point.BASE.multiply(k) / multiplyUnsafe(k)
  * through the cached window table (ScalarMultiplier.wnafCachedCT, src/abstract/curve.ts:588-606;

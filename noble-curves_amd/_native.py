@@ -17,6 +17,8 @@ POINT_BYTES = {SECP256K1: 64, ED25519: 64, BLS12_381_G1: 96, BLS12_381_G2: 192, 
 FIELD_BYTES = {SECP256K1: 32, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 48, BN254_G1: 32}
 FIELD_BLS12_381_FR = 0
 FIELD_BN254_FR = 5
+POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
+POLY_MAX_POINTS = 8
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -103,6 +105,18 @@ _OPTIONAL_PROTOS = {
     "ncg_map_to_curve_batch_dev": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _vp],
     "ncg_ntt": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _i32],
     "ncg_ntt_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _i32, _vp],
+    "ncg_poly_pointwise": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
+    "ncg_poly_pointwise_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp],
+    "ncg_poly_scale": [_vp, _i32, _sz, _vp, _vp, _i32, _vp],
+    "ncg_poly_scale_dev": [_vp, _i32, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_poly_eval": [_vp, _i32, _sz, _vp, _vp, _vp],
+    "ncg_poly_eval_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
+    "ncg_poly_eval_monomial": [_vp, _i32, _sz, _vp, _i32, _vp, _vp],
+    "ncg_poly_eval_monomial_dev": [_vp, _i32, _sz, _vp, _i32, _vp, _vp, _vp],
+    "ncg_poly_lagrange_basis": [_vp, _i32, _i32, _vp, _vp, _i32, _vp],
+    "ncg_poly_lagrange_basis_dev": [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
+    "ncg_poly_mul": [_vp, _i32, _i32, _vp, _sz, _vp, _sz, _vp, _vp],
+    "ncg_poly_mul_dev": [_vp, _i32, _i32, _vp, _sz, _vp, _sz, _vp, _vp, _vp],
     "ncg_normalize_batch": [_vp, _i32, _sz, _vp, _vp, _vp],
     "ncg_normalize_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
     "ncg_msm": [_vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_uint8)],
@@ -711,6 +725,88 @@ class Engine:
         om = np.frombuffer(int(omega).to_bytes(32, "little"), dtype=np.uint8).copy()
         self._check(self.lib.ncg_ntt_dev(self.h, field, log2n, batch, om.ctypes.data, d_in, d_out,
                                          self._ntt_flags(inverse, brp_input, brp_output), stream))
+
+    # ---- polynomial arithmetic on vectors of scalar-field elements (ncg_poly_*) ------------------
+    @staticmethod
+    def _fr_vec(data):
+        return np.ascontiguousarray(data, dtype=np.uint8).reshape(-1, 32)
+
+    @staticmethod
+    def _fr_small(values):
+        """ints -> the host operand of a poly call: uint8 [len, 32]"""
+        return ints_to_le([int(v) for v in values], 32)
+
+    def poly_pointwise(self, op, a, b, field=FIELD_BLS12_381_FR):
+        """a, b uint8 [n, 32] -> a[i] + b[i] (POLY_ADD), a[i] - b[i] (POLY_SUB) or a[i] * b[i] (POLY_DOT)"""
+        a, b = self._fr_vec(a), self._fr_vec(b)
+        if a.shape != b.shape:
+            raise ValueError("noble-gpu: poly_pointwise: operand arrays differ in length")
+        out = np.empty_like(a)
+        self._check(self.lib.ncg_poly_pointwise(self.h, field, op, a.shape[0], a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def poly_pointwise_dev(self, op, n, d_a, d_b, d_out, stream, field=FIELD_BLS12_381_FR):
+        self._check(self.lib.ncg_poly_pointwise_dev(self.h, field, op, n, d_a, d_b, d_out, stream))
+
+    def poly_scale(self, a, scalar, powers=False, field=FIELD_BLS12_381_FR):
+        """a uint8 [n, 32], scalar int -> a[i] * scalar, or a[i] * scalar^i with powers (the reference's shift)"""
+        a = self._fr_vec(a)
+        out = np.empty_like(a)
+        s = self._fr_small([scalar])
+        self._check(self.lib.ncg_poly_scale(self.h, field, a.shape[0], a.ctypes.data, s.ctypes.data, 1 if powers else 0, out.ctypes.data))
+        return out
+
+    def poly_scale_dev(self, n, d_a, scalar, powers, d_out, stream, field=FIELD_BLS12_381_FR):
+        s = self._fr_small([scalar])
+        self._check(self.lib.ncg_poly_scale_dev(self.h, field, n, d_a, s.ctypes.data, 1 if powers else 0, d_out, stream))
+
+    def poly_eval(self, a, basis, field=FIELD_BLS12_381_FR):
+        """sum a[i] * basis[i] -> int"""
+        a, basis = self._fr_vec(a), self._fr_vec(basis)
+        if a.shape != basis.shape:
+            raise ValueError("noble-gpu: poly_eval: operand arrays differ in length")
+        out = np.empty((1, 32), dtype=np.uint8)
+        self._check(self.lib.ncg_poly_eval(self.h, field, a.shape[0], a.ctypes.data, basis.ctypes.data, out.ctypes.data))
+        return le_to_ints(out, 32)[0]
+
+    def poly_eval_dev(self, n, d_a, d_basis, d_out32, stream, field=FIELD_BLS12_381_FR):
+        self._check(self.lib.ncg_poly_eval_dev(self.h, field, n, d_a, d_basis, d_out32, stream))
+
+    def poly_eval_monomial(self, a, xs, field=FIELD_BLS12_381_FR):
+        """[sum a[i] * x^i for x in xs] (1 to POLY_MAX_POINTS points, one pass over a) -> list of ints"""
+        a = self._fr_vec(a)
+        x = self._fr_small(xs)
+        out = np.empty((max(len(xs), 1), 32), dtype=np.uint8)
+        self._check(self.lib.ncg_poly_eval_monomial(self.h, field, a.shape[0], a.ctypes.data, len(xs), x.ctypes.data, out.ctypes.data))
+        return le_to_ints(out, 32)[:len(xs)]
+
+    def poly_eval_monomial_dev(self, n, d_a, xs, d_out, stream, field=FIELD_BLS12_381_FR):
+        x = self._fr_small(xs)
+        self._check(self.lib.ncg_poly_eval_monomial_dev(self.h, field, n, d_a, len(xs), x.ctypes.data, d_out, stream))
+
+    def poly_lagrange_basis(self, log2n, omega, x, brp=False, field=FIELD_BLS12_381_FR):
+        """L_i(x) over the 2^log2n roots of unity of omega (bit-reversed order with brp) -> uint8 [2^log2n, 32]"""
+        om, xx = self._fr_small([omega]), self._fr_small([x])
+        out = np.empty((1 << log2n, 32), dtype=np.uint8)
+        self._check(self.lib.ncg_poly_lagrange_basis(self.h, field, log2n, om.ctypes.data, xx.ctypes.data, 1 if brp else 0, out.ctypes.data))
+        return out
+
+    def poly_lagrange_basis_dev(self, log2n, omega, x, brp, d_out, stream, field=FIELD_BLS12_381_FR):
+        om, xx = self._fr_small([omega]), self._fr_small([x])
+        self._check(self.lib.ncg_poly_lagrange_basis_dev(self.h, field, log2n, om.ctypes.data, xx.ctypes.data, 1 if brp else 0, d_out, stream))
+
+    def poly_mul(self, log2n, omega, a, b, field=FIELD_BLS12_381_FR):
+        """cyclic product of length 2^log2n of a (na <= 2^log2n rows) and b (nb rows), zero-extended on the device"""
+        a, b = self._fr_vec(a), self._fr_vec(b)
+        om = self._fr_small([omega])
+        out = np.empty((1 << log2n, 32), dtype=np.uint8)
+        self._check(self.lib.ncg_poly_mul(self.h, field, log2n, om.ctypes.data, a.shape[0], a.ctypes.data, b.shape[0], b.ctypes.data,
+                                          out.ctypes.data))
+        return out
+
+    def poly_mul_dev(self, log2n, omega, na, d_a, nb, d_b, d_out, stream, field=FIELD_BLS12_381_FR):
+        om = self._fr_small([omega])
+        self._check(self.lib.ncg_poly_mul_dev(self.h, field, log2n, om.ctypes.data, na, d_a, nb, d_b, d_out, stream))
 
     def field_check(self, field, op, variant, a_words, b_words):
         """Device field code on raw operands (ncg_field_check): a_words, b_words uint32 [n, 9] (fields 0/1),

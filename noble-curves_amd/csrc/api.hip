@@ -227,6 +227,22 @@ static Rule ntt_rule(ncg_ctx* ctx, int field, int log2n, size_t batch) {
   else if (batch > 65535) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ntt: batch %zu too large (max 65535)", batch);
   return {"ntt", rc};
 }
+// the polynomial operations share one rule; `kind` names the entry point, the arguments an entry point does not have are passed as
+// values that pass (op 0, log2n 0, m 1, na = nb = 0)
+enum { POLY_POINTWISE, POLY_SCALE, POLY_EVAL, POLY_EVAL_MONOMIAL, POLY_LAGRANGE, POLY_MUL };
+static Rule poly_rule(ncg_ctx* ctx, int kind, int field, int op, int log2n, int m, size_t na, size_t nb) {
+  static const char* const names[] = {"poly_pointwise", "poly_scale", "poly_eval", "poly_eval_monomial", "poly_lagrange_basis", "poly_mul"};
+  int rc = NCG_OK;
+  if (field != NCG_FIELD_BLS12_381_FR && field != NCG_FIELD_BN254_FR) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: poly: unsupported field %d", field);
+  else if (kind == POLY_POINTWISE && (op < NCG_POLY_ADD || op > NCG_POLY_DOT)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: unknown op %d", op);
+  else if (kind == POLY_SCALE && op != 0 && op != 1) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: powers must be 0 or 1, got %d", op);
+  else if (log2n < 0 || log2n > NCG_NTT_MAX_LOG2N)
+    rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: log2n %d out of range 0..%d", log2n, NCG_NTT_MAX_LOG2N);
+  else if (m < 1 || m > NCG_POLY_MAX_POINTS) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: m %d out of range 1..%d", m, NCG_POLY_MAX_POINTS);
+  else if (na > ((size_t)1 << log2n) || nb > ((size_t)1 << log2n))
+    rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: %zu and %zu coefficients do not fit the length 2^%d", na, nb, log2n);
+  return {names[kind], rc};
+}
 static Rule no_rule(const char* op) { return {op, NCG_OK}; }  // nothing to check beyond the prologue
 static Rule handle_rule(ncg_ctx* ctx, const char* op, const ncg_points* pts) {
   return {op, pts && pts->ctx == ctx ? NCG_OK
@@ -356,6 +372,7 @@ void ncg_destroy(ncg_ctx* ctx) {
     for (int i = 0; i <= NCG_NTT_MAX_LOG2N; i++)
       if (ctx->ntt_tab[f][i]) (void)hipFree(ctx->ntt_tab[f][i]);
   if (ctx->ntt_ws) (void)hipFree(ctx->ntt_ws);
+  if (ctx->poly_ws) (void)hipFree(ctx->poly_ws);
   (void)ncg_comm_destroy(ctx);
   if (ctx->comm_buf) (void)hipFree(ctx->comm_buf);
   if (ctx->sync_land) (void)hipHostFree(ctx->sync_land);
@@ -1314,6 +1331,125 @@ int ncg_ntt(ncg_ctx* ctx, int field, int log2n, size_t batch, const void* omega,
   const int io = hc.inout(in, out, (batch << log2n) * 32);  // batch <= 2^16, log2n <= 28: below 2^49
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ntt_dev(ctx, field, log2n, batch, omega, hc.dev(io), hc.dev(io), flags, ctx->stream));
+}
+
+// ---- polynomial arithmetic on field vectors (poly.hip).  The _dev forms work on ctx->poly_ws, never on ctx->scratch.
+static int poly_misaligned(ncg_ctx* ctx, std::initializer_list<const void*> bufs) {
+  for (const void* p : bufs)
+    if (misaligned16(p)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: device buffers must be 16-byte aligned");
+  return NCG_OK;
+}
+static int poly_ensure_ws(ncg_ctx* ctx, int log2n_mul) {
+  const size_t need = ncg::poly_ws_bytes(log2n_mul);
+  return ncg_grow_buf(ctx, &ctx->poly_ws, &ctx->poly_ws_bytes, need, need, GrowWait::device);
+}
+// the evaluations of an empty polynomial are F.ZERO (fft.ts:859, :876): written, not refused, so the output is required even then
+static int poly_zero(ncg_ctx* ctx, void* out, size_t bytes, bool dev, void* stream) {
+  if (!out) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly: NULL output");
+  if (!dev) {
+    memset(out, 0, bytes);
+    return NCG_OK;
+  }
+  NCG_HIP(ctx, hipSetDevice(ctx->device));
+  NCG_HIP(ctx, hipMemsetAsync(out, 0, bytes, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+
+int ncg_poly_pointwise_dev(ncg_ctx* ctx, int field, int op, size_t n, const void* a_dev, const void* b_dev, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_POINTWISE, field, op, 0, 1, 0, 0), n, a_dev, b_dev, out_dev);
+  if (int rc = poly_misaligned(ctx, {a_dev, b_dev, out_dev})) return rc;
+  NCG_HIP(ctx, ncg::poly_pointwise(field, op, n, (const uint32_t*)a_dev, (const uint32_t*)b_dev, (uint32_t*)out_dev, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_pointwise(ncg_ctx* ctx, int field, int op, size_t n, const void* a, const void* b, void* out) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_POINTWISE, field, op, 0, 1, 0, 0), n, a, b, out);
+  HostCall hc(ctx);
+  const int ia = hc.inout(a, out, n * 32), ib = hc.in(b, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_pointwise_dev(ctx, field, op, n, hc.dev(ia), hc.dev(ib), hc.dev(ia), ctx->stream));
+}
+
+int ncg_poly_scale_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, const void* scalar, int powers, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_SCALE, field, powers, 0, 1, 0, 0), n, a_dev, scalar, out_dev);
+  if (int rc = poly_misaligned(ctx, {a_dev, out_dev})) return rc;
+  NCG_HIP(ctx, ncg::poly_scale(field, n, (const uint32_t*)a_dev, (const uint32_t*)scalar, powers, (uint32_t*)out_dev, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_scale(ncg_ctx* ctx, int field, size_t n, const void* a, const void* scalar, int powers, void* out) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_SCALE, field, powers, 0, 1, 0, 0), n, a, scalar, out);
+  HostCall hc(ctx);
+  const int io = hc.inout(a, out, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_scale_dev(ctx, field, n, hc.dev(io), scalar, powers, hc.dev(io), ctx->stream));
+}
+
+int ncg_poly_eval_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, const void* basis_dev, void* out32_dev, void* stream) {
+  NCG_BEGIN_OR(ctx, poly_rule(ctx, POLY_EVAL, field, 0, 0, 1, 0, 0), n, poly_zero(ctx, out32_dev, 32, true, stream), a_dev, basis_dev, out32_dev);
+  if (int rc = poly_misaligned(ctx, {a_dev, basis_dev, out32_dev})) return rc;
+  if (int rc = poly_ensure_ws(ctx, -1)) return rc;
+  NCG_HIP(ctx, ncg::poly_eval(field, n, (const uint32_t*)a_dev, (const uint32_t*)basis_dev, ctx->poly_ws, (uint32_t*)out32_dev, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_eval(ncg_ctx* ctx, int field, size_t n, const void* a, const void* basis, void* out32) {
+  NCG_BEGIN_OR(ctx, poly_rule(ctx, POLY_EVAL, field, 0, 0, 1, 0, 0), n, poly_zero(ctx, out32, 32, false, nullptr), a, basis, out32);
+  HostCall hc(ctx);
+  const int ia = hc.in(a, n * 32), ib = hc.in(basis, n * 32), o = hc.out(out32, 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_eval_dev(ctx, field, n, hc.dev(ia), hc.dev(ib), hc.dev(o), ctx->stream));
+}
+
+int ncg_poly_eval_monomial_dev(ncg_ctx* ctx, int field, size_t n, const void* a_dev, int m, const void* xs, void* out_dev, void* stream) {
+  NCG_BEGIN_OR(ctx, poly_rule(ctx, POLY_EVAL_MONOMIAL, field, 0, 0, m, 0, 0), n, poly_zero(ctx, out_dev, (size_t)m * 32, true, stream), a_dev, xs,
+               out_dev);
+  if (int rc = poly_misaligned(ctx, {a_dev, out_dev})) return rc;
+  if (int rc = poly_ensure_ws(ctx, -1)) return rc;
+  NCG_HIP(ctx, ncg::poly_eval_monomial(field, n, (const uint32_t*)a_dev, m, (const uint32_t*)xs, ctx->poly_ws, (uint32_t*)out_dev,
+                                       stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_eval_monomial(ncg_ctx* ctx, int field, size_t n, const void* a, int m, const void* xs, void* out) {
+  NCG_BEGIN_OR(ctx, poly_rule(ctx, POLY_EVAL_MONOMIAL, field, 0, 0, m, 0, 0), n, poly_zero(ctx, out, (size_t)m * 32, false, nullptr), a, xs, out);
+  HostCall hc(ctx);
+  const int ia = hc.in(a, n * 32), o = hc.out(out, (size_t)m * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_eval_monomial_dev(ctx, field, n, hc.dev(ia), m, xs, hc.dev(o), ctx->stream));
+}
+
+int ncg_poly_lagrange_basis_dev(ncg_ctx* ctx, int field, int log2n, const void* omega, const void* x, int brp, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_LAGRANGE, field, 0, log2n, 1, 0, 0), 1, omega, x, out_dev);
+  if (int rc = poly_misaligned(ctx, {out_dev})) return rc;
+  if (int rc = ensure_ntt_table(ctx, field, log2n, (const uint32_t*)omega)) return rc;
+  if (int rc = poly_ensure_ws(ctx, -1)) return rc;
+  NCG_HIP(ctx, ncg::poly_lagrange_basis(field, log2n, ctx->ntt_tab[ntt_field_slot(field)][log2n], (const uint32_t*)x, brp ? 1 : 0, ctx->poly_ws,
+                                        (uint32_t*)out_dev, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_lagrange_basis(ncg_ctx* ctx, int field, int log2n, const void* omega, const void* x, int brp, void* out) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_LAGRANGE, field, 0, log2n, 1, 0, 0), 1, omega, x, out);
+  HostCall hc(ctx);
+  const int o = hc.out(out, (size_t)32 << log2n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_lagrange_basis_dev(ctx, field, log2n, omega, x, brp, hc.dev(o), ctx->stream));
+}
+
+int ncg_poly_mul_dev(ncg_ctx* ctx, int field, int log2n, const void* omega, size_t na, const void* a_dev, size_t nb, const void* b_dev,
+                     void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_MUL, field, 0, log2n, 1, na, nb), 1, omega, out_dev);
+  if ((na && !a_dev) || (nb && !b_dev)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly_mul: NULL buffer");
+  if (int rc = poly_misaligned(ctx, {a_dev, b_dev, out_dev})) return rc;
+  if (int rc = ensure_ntt_table(ctx, field, log2n, (const uint32_t*)omega)) return rc;
+  if (int rc = poly_ensure_ws(ctx, log2n)) return rc;
+  NCG_HIP(ctx, ncg::poly_mul(field, log2n, ctx->ntt_tab[ntt_field_slot(field)][log2n], na, (const uint32_t*)a_dev, nb, (const uint32_t*)b_dev,
+                             ctx->poly_ws, (uint32_t*)out_dev, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_poly_mul(ncg_ctx* ctx, int field, int log2n, const void* omega, size_t na, const void* a, size_t nb, const void* b, void* out) {
+  NCG_BEGIN(ctx, poly_rule(ctx, POLY_MUL, field, 0, log2n, 1, na, nb), 1, omega, out);
+  if ((na && !a) || (nb && !b)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: poly_mul: NULL buffer");
+  HostCall hc(ctx);
+  const int ia = hc.in(a, na * 32), ib = hc.in(b, nb * 32), o = hc.out(out, (size_t)32 << log2n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_poly_mul_dev(ctx, field, log2n, omega, na, hc.dev(ia), nb, hc.dev(ib), hc.dev(o), ctx->stream));
 }
 
 static int ensure_ed_table(ncg_ctx* ctx) {

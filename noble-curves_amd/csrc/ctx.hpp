@@ -58,6 +58,10 @@ struct ncg_ctx {
   uint32_t ntt_omega[2][NCG_NTT_MAX_LOG2N + 1][8] = {};
   void* ntt_ws = nullptr;
   size_t ntt_ws_bytes = 0;
+  // polynomial operations (poly.hip): partial sums, the root-index word and the 2 N transform buffer of a product; like ntt_ws it
+  // serves one call at a time
+  void* poly_ws = nullptr;
+  size_t poly_ws_bytes = 0;
   // multi-GPU (comm.hip): RCCL communicator of this rank and the gather buffer of the sharded MSM
   void* comm = nullptr;  // ncclComm_t
   int comm_rank = 0, comm_size = 1;

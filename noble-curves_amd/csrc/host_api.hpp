@@ -53,6 +53,23 @@ hipError_t ntt_run(int field, int n, size_t batch, const uint32_t* src, uint32_t
                    int tab_log, int flags, hipStream_t st);
 int ntt_host(int field, int n, const uint32_t* omega_wire, const uint32_t* src, uint32_t* dst, int flags, int t0max = 10, int tmax = 8);
 
+// polynomial arithmetic over the same two fields on resident vectors (poly.hip; reference poly(), fft.ts:583-926).  Small operands
+// (s, xs, x) are HOST pointers to canonical residues; ws: poly_ws_bytes(log2n of a product, or -1) bytes of device memory, whose head holds
+// the partial sums and the root-index word; tab: the cached twiddle table of (field, log2n)
+size_t poly_ws_bytes(int log2n_mul);
+hipError_t poly_pointwise(int field, int op, size_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, hipStream_t st);
+hipError_t poly_scale(int field, size_t n, const uint32_t* a, const uint32_t* s_host, int powers, uint32_t* out, hipStream_t st);
+hipError_t poly_eval(int field, size_t n, const uint32_t* a, const uint32_t* basis, void* ws, uint32_t* out, hipStream_t st);
+hipError_t poly_eval_monomial(int field, size_t n, const uint32_t* a, int m, const uint32_t* xs_host, void* ws, uint32_t* out, hipStream_t st);
+hipError_t poly_lagrange_basis(int field, int log2n, const uint32_t* tab, const uint32_t* x_host, int brp, void* ws, uint32_t* out,
+                               hipStream_t st);
+hipError_t poly_mul(int field, int log2n, const uint32_t* tab, size_t na, const uint32_t* a, size_t nb, const uint32_t* b, void* ws,
+                    uint32_t* out, hipStream_t st);
+// host twin: kind 0 pointwise (op), 1 scale (op = powers), 2 dot-sum, 3 monomial evaluation at m points, 4 small^n; T threads (0: the device's)
+int poly_host(int field, int kind, int op, size_t n, const uint32_t* a, const uint32_t* b, int m, const uint32_t* small, size_t T, uint32_t* out);
+int poly_host_lagrange(int field, int log2n, const uint32_t* omega_wire, const uint32_t* x_wire, int brp, size_t T, uint32_t* out,
+                       uint32_t* root_out);
+
 struct MsmPlan;
 // Optional second stream of a context: the wire -> storage conversion of the points has no consumer before
 // the accumulate kernel, so it runs beside the digit / sort kernels (LDS- and memory-bound) instead of in

@@ -9,6 +9,7 @@
 #include "ed25519.hip"  // single-TU inclusion: lane function + host table builder
 #include "decode.hip"
 #include "ntt.hip"
+#include "poly.hip"
 #include "h2c.hip"
 #include "endo.hpp"
 #include "ecdsa.hip"
@@ -517,6 +518,31 @@ int ht_ntt_schedule(int n, int flags, int* out) {
   }
   return sc.np;
 }
+// poly.hip on the CPU: the per-element and per-run functions of the kernels, T threads executed one after the other (T = 0: the
+// thread count the device launches).  Each returns the overflow count of fr29.hpp's host checks (the table entries are the only
+// fr29 values poly.hip touches), or -1 for an unknown request.
+int ht_poly_pointwise(int field, int op, size_t n, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  return poly_host(field, 0, op, n, a, b, 1, nullptr, 0, out);
+}
+int ht_poly_scale(int field, size_t n, const uint32_t* a, const uint32_t* s, int powers, size_t T, uint32_t* out) {
+  return poly_host(field, 1, powers, n, a, nullptr, 1, s, T, out);
+}
+int ht_poly_eval(int field, size_t n, const uint32_t* a, const uint32_t* basis, size_t T, uint32_t* out) {
+  return poly_host(field, 2, 0, n, a, basis, 1, nullptr, T, out);
+}
+int ht_poly_eval_monomial(int field, size_t n, const uint32_t* a, int m, const uint32_t* xs, size_t T, uint32_t* out) {
+  if (m < 1 || m > NCG_POLY_MAX_POINTS) return -1;
+  return poly_host(field, 3, 0, n, a, nullptr, m, xs, T, out);
+}
+// s^start: the start power of the run that begins at index `start`
+int ht_poly_pow(int field, const uint32_t* s, uint64_t start, uint32_t* out) {
+  return poly_host(field, 4, 0, (size_t)start, nullptr, nullptr, 1, s, 0, out);
+}
+int ht_poly_lagrange(int field, int log2n, const uint32_t* omega, const uint32_t* x, int brp, size_t T, uint32_t* out, uint32_t* root_out) {
+  if (log2n < 0 || log2n > 20) return -1;
+  return poly_host_lagrange(field, log2n, omega, x, brp, T, out, root_out);
+}
+int ht_poly_lag_run() { return POLY_LAG_RUN; }
 int ht_ntt_max_log2n() { return NCG_NTT_MAX_LOG2N; }
 // the pass planner of ntt_run: writes s_lo/T pairs, returns the number of passes
 int ht_ntt_plan(int n, int* out) {

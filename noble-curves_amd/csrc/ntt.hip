@@ -32,14 +32,11 @@
 #include <algorithm>
 #include "fp.hpp"
 #include "fr29.hpp"
+#include "ntt_io.hpp"  // fr_load_g / fr_store_g, ntt_load_tw / ntt_store_tw, NTT_TW
 #include "host_api.hpp"
 #include "../../include/ncg.h"
 
 namespace ncg {
-
-using Fr = Fp<ParamsBlsR>;  // also the 8-word container of the pass code (loads, stores, word <-> limb conversion) for either field
-template <class F>
-using FrOf = Fp<typename F::M8>;  // the field the twiddle table is computed in
 
 struct NttPass {
   int n;          // log2 N
@@ -55,22 +52,6 @@ struct NttPass {
                   // of a natural -> natural transform, whose bit-reversed store then writes runs of 2^logC elements
   int tshift;     // log2(table size) - n
 };
-
-template <class T = Fr>
-NCG_DI T fr_load_g(const uint32_t* __restrict__ p) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  uint4 a = q[0], b = q[1];
-  T r;
-  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
-  r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
-  return r;
-}
-template <class T>
-NCG_DI void fr_store_g(uint32_t* __restrict__ p, const T& r) {
-  uint4* q = reinterpret_cast<uint4*>(p);
-  q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
-}
 
 // One pass: tile = 2^T rows (the index bits this pass transforms) x 2^logC contiguous elements.
 // src/dst hold `batch` polynomials of N elements (8 LE words each); blockIdx.y = polynomial.
@@ -103,38 +84,9 @@ NCG_DI size_t ntt_tile_index(const NttPass& ps, const NttTile& t, int e) {
   if (ps.colhi) return t.base | ((size_t)(e & (t.C - 1)) << (ps.n - ps.logC)) | (size_t)(e >> ps.logC);
   return t.base | ((size_t)(e >> ps.logC) << t.L) | (size_t)(e & (t.C - 1));
 }
-NCG_DI uint32_t ntt_brev32(uint32_t x) {
-#ifdef __HIP_DEVICE_COMPILE__
-  return __brev(x);
-#else
-  uint32_t r = 0;
-  for (int i = 0; i < 32; i++) r |= ((x >> i) & 1u) << (31 - i);
-  return r;
-#endif
-}
 NCG_DI Fr29 fr29_load_g(const uint32_t* __restrict__ p) {
   const Fr x = fr_load_g(p);
   return fr29_from_words(x.v);
-}
-// twiddle table entry: the 9 limbs of w 2^261 mod r, no conversion on load.  Nine words per entry since the third session of round 6 (36 bytes at
-// 4-byte alignment; twelve words = three aligned 16-byte loads before): a 2^22 transform reads its table about twice, a quarter less of it is 1-3 % of
-// the transform (profiles/r06_ntt_tw36_ab.txt) and 50 MB less device memory per 2^22 table
-constexpr int NTT_TW = 9;   // words per twiddle entry
-struct __attribute__((packed, aligned(4))) NttTw9 { uint32_t v[9]; };
-NCG_DI Fr29 ntt_load_tw(const uint32_t* __restrict__ p) {
-  const NttTw9 t = *reinterpret_cast<const NttTw9*>(p);
-  Fr29 r;
-#pragma unroll
-  for (int i = 0; i < 9; i++) r.v[i] = t.v[i];
-  return r;
-}
-template <class T>
-NCG_DI void ntt_store_tw(uint32_t* __restrict__ p, const T& canonical) {
-  const Fr29 l = fr29_from_words(canonical.v);
-  NttTw9 t;
-#pragma unroll
-  for (int i = 0; i < 9; i++) t.v[i] = l.v[i];
-  *reinterpret_cast<NttTw9*>(p) = t;
 }
 template <int E, class LDS>
 NCG_DI Fr29 fr29_load_l(const LDS lds, int e) {

@@ -1,8 +1,10 @@
-"""Host mirror of the reference's FFT interface for the bls12-381 and bn254 scalar fields
+"""Host mirror of the reference's FFT and poly interfaces for the bls12-381 and bn254 scalar fields
 (src/abstract/fft.ts): `rootsOfUnity(Fr, 7)` / `FFT(roots, Fr).direct|inverse(values, brpInput,
 brpOutput)` with the same names, argument meaning and error messages; the transform itself runs in
 `libncg.so` (`ncg_ntt`, field NCG_FIELD_BLS12_381_FR or NCG_FIELD_BN254_FR by the ORDER of the field).  The host side only does what the reference does once per field: the
 2-adic chain of primitive roots (:238-241) - a handful of modular exponentiations.
+`poly(Fr, roots, create, fft, length)` (:583-926) keeps the reference's names and messages too; its vector work runs in
+`ncg_poly_*`, only create / degree / extend / clone / vanishing stay on the host.
 """
 import numpy as np
 
@@ -160,3 +162,247 @@ class FFT:
 
     def inverse(self, values, brpInput=False, brpOutput=False):
         return self._run(values, True, bool(brpInput), bool(brpOutput))
+
+
+# ---------------------------------------------------------------- poly (fft.ts:583-926)
+def _js_typeof(v):
+    """the word the reference's messages print for a value of this kind (`typeof`)"""
+    if v is None:
+        return "undefined"
+    if isinstance(v, bool):
+        return "boolean"
+    if isinstance(v, int):
+        return "bigint"
+    if isinstance(v, float):
+        return "number"
+    if isinstance(v, str):
+        return "string"
+    if callable(v):
+        return "function"
+    return "object"
+
+
+class _PolyGroup:
+    """a namespace of functions (`monomial`, `lagrange`)"""
+
+    def __init__(self, **fns):
+        self.__dict__.update(fns)
+
+
+class Poly:
+    """fft.ts:710-926 for the two device fields.  Polynomials are lists of ints in [0, r) or uint8 arrays [N, 32] (little-endian
+    canonical residues), returned in kind; with a `create` of the caller's, list results are copied into create(len)."""
+
+    def __init__(self, field, roots, create=None, fft=None, length=None, engine=None):
+        if getattr(field, "ORDER", None) not in _DEVICE_FIELDS:
+            raise ValueError("noble-gpu: the device poly is built for the bls12-381 and bn254 scalar fields only")
+        if not isinstance(roots, RootsOfUnity):
+            raise TypeError("noble-gpu: poly expects the RootsOfUnity returned by rootsOfUnity()")
+        self.field = field
+        self.roots = roots
+        self._own_create = create
+        self.create = create or (lambda n, elm=None: [field.ZERO if elm is None else elm] * n)
+        self.fft = fft
+        self.length = length
+        self._engine = engine
+        self._fid = _DEVICE_FIELDS[field.ORDER]
+        self.monomial = _PolyGroup(basis=self._monomial_basis, eval=self._monomial_eval)
+        self.lagrange = _PolyGroup(basis=self._lagrange_basis, eval=self._lagrange_eval)
+
+    # ---- argument handling: the reference's checks and messages, raised before the engine is touched
+    @staticmethod
+    def _is_poly(x):
+        return isinstance(x, (list, tuple)) or (isinstance(x, np.ndarray) and x.ndim >= 1)
+
+    def _check_poly(self, title, value):
+        if not self._is_poly(value):
+            raise TypeError('"%s" expected polynomial, got type=%s' % (title, _js_typeof(value)))
+
+    @staticmethod
+    def _len(p):
+        return p.shape[0] if isinstance(p, np.ndarray) else len(p)
+
+    def _check_fixed(self, L):
+        if self.length is not None and L != self.length:
+            raise ValueError("poly: expected fixed length %d, got %d" % (self.length, L))
+
+    def _check_length(self, a, b=None):
+        self._check_poly("a", a)
+        L = self._len(a)
+        if b is not None:
+            self._check_poly("b", b)
+            if self._len(b) != L:
+                raise ValueError("poly: mismatched lengths %d vs %d" % (L, self._len(b)))
+        self._check_fixed(L)
+        return L
+
+    def _elem(self, v):
+        if not isinstance(v, int) or isinstance(v, bool) or not (0 <= v < self.field.ORDER):
+            raise ValueError("invalid field element: outside of range 0..ORDER")
+        return v
+
+    def _wire(self, p):
+        if isinstance(p, np.ndarray):
+            return np.ascontiguousarray(p, dtype=np.uint8).reshape(-1, 32)
+        return _native.ints_to_le([self._elem(v) for v in p], 32)
+
+    def _ints(self, p):
+        return _native.le_to_ints(p, 32) if isinstance(p, np.ndarray) else list(p)
+
+    def _back(self, data, like):
+        if isinstance(like, np.ndarray):
+            return data
+        vals = _native.le_to_ints(data, 32)
+        if self._own_create is None:
+            return vals
+        out = self._own_create(len(vals))
+        for i, v in enumerate(vals):
+            out[i] = v
+        return out
+
+    def _eng(self):
+        return self._engine or get_engine()
+
+    @staticmethod
+    def _pow2(n, what="poly.lagrange"):
+        if not isPowerOfTwo(n):
+            raise ValueError("%s: expected power of two length, got %s" % (what, n))
+        return log2(n)
+
+    # ---- host side
+    def extend(self, a, n):                                   # :776-783
+        self._check_length(a)
+        out = self.create(n, self.field.ZERO)
+        vals = self._ints(a)
+        for i in range(min(len(vals), n)):
+            out[i] = vals[i]
+        return out
+
+    def degree(self, a):                                      # :784-788
+        self._check_length(a)
+        vals = self._ints(a)
+        for i in range(len(vals) - 1, -1, -1):
+            if vals[i] != 0:
+                return i
+        return -1
+
+    def clone(self, a):                                       # :851-856
+        self._check_length(a)
+        if isinstance(a, np.ndarray):
+            return a.copy()
+        out = self.create(len(a))
+        for i, v in enumerate(a):
+            out[i] = v
+        return out
+
+    def vanishing(self, roots):                               # :912-924
+        self._check_poly("roots", roots)
+        rs = self._ints(roots)
+        self._check_fixed(len(rs))
+        r = self.field.ORDER
+        out = self.create(len(rs) + 1, self.field.ZERO)
+        out[0] = self.field.ONE
+        for root in rs:
+            neg = (r - self._elem(root)) % r
+            for j in range(len(rs), 0, -1):
+                out[j] = (out[j] * neg + out[j - 1]) % r
+            out[0] = out[0] * neg % r
+        return out
+
+    # ---- device side
+    def _pointwise(self, op, a, b):
+        L = self._check_length(a, b)
+        A, B = self._wire(a), self._wire(b)
+        if L == 0:
+            return self._back(A, a)
+        return self._back(self._eng().poly_pointwise(op, A, B, field=self._fid), a)
+
+    def add(self, a, b):                                      # :789-794
+        return self._pointwise(_native.POLY_ADD, a, b)
+
+    def sub(self, a, b):                                      # :795-800
+        return self._pointwise(_native.POLY_SUB, a, b)
+
+    def dot(self, a, b):                                      # :801-806
+        return self._pointwise(_native.POLY_DOT, a, b)
+
+    def _cyclic(self, bits, A, B):
+        return self._eng().poly_mul(bits, self.roots.omega(bits), A, B, field=self._fid)
+
+    def mul(self, a, b):                                      # :807-831
+        if not self._is_poly(b):
+            L = self._check_length(a)
+            A = self._wire(a)
+            s = self._elem(b)
+            return self._back(self._eng().poly_scale(A, s, field=self._fid) if L else A, a)
+        L = self._check_length(a, b)
+        if L and not isPowerOfTwo(L) and self.fft is not None:
+            return self.fft.inverse(self.fft.direct(a, False, True), True, False)   # raises the FFT's power-of-two error
+        A, B = self._wire(a), self._wire(b)
+        if L == 0:
+            return self._back(A, a)
+        if isPowerOfTwo(L):
+            return self._back(self._cyclic(log2(L), A, B), a)
+        # the quadratic product mod x^L - 1 (:816-824): the linear product, folded once
+        full = self._cyclic(log2(nextPowerOfTwo(2 * L - 1)), A, B)
+        return self._back(self._eng().poly_pointwise(_native.POLY_ADD, full[:L], full[L:2 * L], field=self._fid), a)
+
+    def convolve(self, a, b):                                 # :832-837
+        self._check_poly("a", a)
+        self._check_poly("b", b)
+        n = nextPowerOfTwo(self._len(a) + self._len(b) - 1)
+        self._check_fixed(self._len(a))
+        self._check_fixed(self._len(b))
+        self._check_fixed(n)
+        A, B = self._wire(a), self._wire(b)
+        return self._back(self._cyclic(log2(n), A, B), a)
+
+    def shift(self, p, factor):                               # :838-850
+        self._check_poly("p", p)
+        self._check_fixed(self._len(p))
+        P = self._wire(p)
+        f = self._elem(factor)
+        return self._back(self._eng().poly_scale(P, f, powers=True, field=self._fid) if self._len(p) else P, p)
+
+    def eval(self, a, basis):                                 # :857-862
+        self._check_length(a, basis)
+        A, B = self._wire(a), self._wire(basis)
+        return self._eng().poly_eval(A, B, field=self._fid)
+
+    def _monomial_basis(self, x, n):                          # :864-872
+        ones = _native.ints_to_le([self.field.ONE] * n, 32)
+        x = self._elem(x)
+        return self._back(self._eng().poly_scale(ones, x, powers=True, field=self._fid) if n else ones, None)
+
+    def _monomial_eval(self, a, x):                           # :873-879
+        self._check_length(a)
+        A, x = self._wire(a), self._elem(x)
+        return self._eng().poly_eval_monomial(A, [x], field=self._fid)[0]
+
+    def _find_omega_index(self, x, n, brp=False):             # :764-770
+        bits = self._pow2(n)
+        if pow(x, n, self.field.ORDER) != 1:
+            return -1
+        table = self.roots.brp(bits) if brp else self.roots.roots(bits)
+        return table.index(x)
+
+    def _lagrange_basis(self, x, n, brp=False):               # :882-901
+        bits = self._pow2(n)
+        x = self._elem(x)
+        out = self._eng().poly_lagrange_basis(bits, self.roots.omega(bits), x, brp=bool(brp), field=self._fid)
+        return self._back(out, None)
+
+    def _lagrange_eval(self, a, x, brp=False):                # :902-910
+        L = self._check_length(a)
+        self._pow2(L)
+        A = self._wire(a)
+        idx = self._find_omega_index(self._elem(x), L, bool(brp))
+        if idx != -1:
+            return _native.le_to_ints(A[idx:idx + 1], 32)[0]
+        bits = log2(L)
+        basis = self._eng().poly_lagrange_basis(bits, self.roots.omega(bits), x, brp=bool(brp), field=self._fid)
+        return self._eng().poly_eval(A, basis, field=self._fid)
+
+
+def poly(field, roots, create=None, fft=None, length=None, engine=None):
+    return Poly(field, roots, create, fft, length, engine)
