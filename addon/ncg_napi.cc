@@ -7,6 +7,8 @@
 //   mulVarBatch(curveId, points, scalars[, out])     -> Uint8Array n * (PB + 1)  (points then flags; `out`: reuse the caller's array)
 //   mulBaseBatch(curveId, scalars)                   -> Uint8Array n * (PB + 1)
 //   ed25519VerifyBatch(sigs, pks, ks, zip215: bool)  -> Uint8Array n (0 / 1)
+//   x25519(kind, scalars | null, rows)               -> Uint8Array n * 33 (32-byte results, then ok flags); kind 0 scalarMult
+//                                                       (scalars: n rows, or ONE row used for every u), 1 getPublicKey, 2 toMontgomery
 //   decodePoints(curveId, encoded, zip215: bool)     -> Uint8Array n * (PB + 2)  (points, ok flags, inf flags)
 //   encodePoints(curveId, points)                    -> Uint8Array n * (EB + 1)  (encodings, ok flags)
 //   aggregateEncoded(curveId, encoded, zip215)       -> Uint8Array PB + 1 (flag); throws naming a bad index
@@ -231,6 +233,33 @@ static napi_value Ed25519VerifyBatch(napi_env env, napi_callback_info info) {
   napi_value res = make_u8(env, n, &out);
   if (!res) return nullptr;
   if (n && ncg_ed25519_verify_batch(g_ctx, n, sig, pk, k, zip215 ? 1 : 0, out) != 0) return throw_native(env);
+  return res;
+}
+
+// X25519 and ed25519.utils.toMontgomery on packed 32-byte rows (ncg_x25519_batch, ncg_x25519_base_batch,
+// ncg_ed25519_to_montgomery_batch): kind 0 (scalars, us) - one scalar row against n > 1 rows of u selects NCG_X25519_ONE_SCALAR -
+// kind 1 (null, secret keys), kind 2 (null, Ed25519 public keys).  Result: n x 32 bytes, then n ok flags (a refused row is zero).
+static napi_value X25519(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind;
+  uint8_t *sc = nullptr, *rows, *out;
+  size_t sl = 0, rl;
+  if (argc < 3 || napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 2 || !get_u8(env, argv[2], &rows, &rl) ||
+      rl % 32 || (kind == 0 && (!get_u8(env, argv[1], &sc, &sl) || (sl != rl && sl != 32)))) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: x25519(kind, scalars | null, rows of 32 bytes)");
+    return nullptr;
+  }
+  const size_t n = rl / 32;
+  napi_value res = make_u8(env, n * 33, &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (n && kind == 0) rc = ncg_x25519_batch(g_ctx, n, sc, rows, sl != rl ? NCG_X25519_ONE_SCALAR : 0, out, out + n * 32);
+  else if (n && kind == 1) rc = ncg_x25519_base_batch(g_ctx, n, rows, out, out + n * 32);
+  else if (n) rc = ncg_ed25519_to_montgomery_batch(g_ctx, n, rows, out, out + n * 32);
+  if (rc != 0) return throw_native(env);
   return res;
 }
 
@@ -878,7 +907,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -6,6 +6,8 @@
 //                                            (src/abstract/weierstrass.ts:915-928)
 //   multiplyBaseBatch(c, scalars)          - array form of BASE.multiply (curve.ts:588-606)
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
+//   x25519ScalarMultBatch(items)           - array form of x25519.scalarMult / getSharedSecret (abstract/montgomery.ts:314-331);
+//   x25519GetPublicKeyBatch(secretKeys)      x25519.getPublicKey; ed25519ToMontgomeryBatch(publicKeys): ed25519.utils.toMontgomery
 //   fftFr(values, opts)                    - FFT(roots, Fr).direct / .inverse (abstract/fft.ts:518-577)
 //   polyFr(opts)                           - poly(Fr, roots, ...) on arrays of bigint (abstract/fft.ts:583-926): add, sub, dot,
 //                                            mul, convolve, shift, eval, monomial.eval, lagrange.basis / eval
@@ -484,6 +486,79 @@ function ed25519VerifyBatch(items, zip215) {   // items: [{sig, msg, publicKey}]
   return Array.from(native.ed25519VerifyBatch(sig, pk, ks, zip215 !== false)).map((x) => x === 1);
 }
 
+// ---- X25519 (abstract/montgomery.ts:247-420, ed25519.ts:266-292) and ed25519.utils.toMontgomery (ed25519.ts:128-134) ----------
+// Batch forms return arrays of Uint8Array | null: null where the reference throws.  The single-item helpers throw its message.
+const X25519_INVALID = 'invalid private or public key received';
+function abytes32(b, title) {                   // utils abytes(value, 32, title)
+  const bytes = b instanceof Uint8Array;
+  if (!bytes || b.length !== 32)
+    throw new Error((title && `"${title}" `) + 'expected Uint8Array of length 32, got ' + (bytes ? `length=${b.length}` : `type=${typeof b}`));
+  return b;
+}
+function x25519Rows(packed, n) {
+  const out = new Array(n);
+  for (let i = 0; i < n; i++) out[i] = packed[32 * n + i] === 1 ? packed.slice(32 * i, 32 * i + 32) : null;
+  return out;
+}
+// items: [{scalar, u}] - or {scalar, us}: ONE secret against many peer keys (the secret crosses once).  The u coordinate of a row is
+// checked before its scalar (montgomery.ts:324-326).
+function x25519ScalarMultBatch(items) {
+  const one = !Array.isArray(items);
+  const us = one ? items.us : items.map((it) => it.u);
+  const n = us.length;
+  const U = new Uint8Array(32 * n), S = new Uint8Array(one ? 32 : 32 * n);
+  for (let i = 0; i < n; i++) {
+    U.set(abytes32(us[i], 'uCoordinate'), 32 * i);
+    if (!one) S.set(abytes32(items[i].scalar, 'scalar'), 32 * i);
+  }
+  if (one) S.set(abytes32(items.scalar, 'scalar'), 0);
+  if (n === 0) return [];
+  init();
+  // (the native call tells the two forms apart by the length of S; for n = 1 they are the same call)
+  return x25519Rows(native.x25519(0, S, U), n);
+}
+function x25519GetPublicKeyBatch(secretKeys) {
+  const n = secretKeys.length, S = new Uint8Array(32 * n);
+  secretKeys.forEach((k, i) => S.set(abytes32(k, 'scalar'), 32 * i));
+  if (n === 0) return [];
+  init();
+  return x25519Rows(native.x25519(1, null, S), n);
+}
+function ed25519ToMontgomeryBatch(publicKeys) {
+  const n = publicKeys.length, K = new Uint8Array(32 * n);
+  publicKeys.forEach((k, i) => K.set(abytes32(k, 'point'), 32 * i));
+  if (n === 0) return [];
+  init();
+  return x25519Rows(native.x25519(2, null, K), n);
+}
+const X25519_P = (1n << 255n) - 19n;
+const X25519_LOW = [0n, 1n, X25519_P - 1n, 325606250916557431795983626356110631294008115727848805560023387167927233504n,
+                    39382357235489614581723060781553021112529911719440698176882885853963445705823n];
+function x25519ScalarMult(scalar, u) {          // montgomery.ts:314-331 with its order of checks: u, low order, then the scalar
+  abytes32(u, 'uCoordinate');
+  const pu = (leNumber(u, 0, 32) & ((1n << 255n) - 1n)) % X25519_P;
+  if (X25519_LOW.includes(pu)) throw new Error(X25519_INVALID);
+  const r = x25519ScalarMultBatch([{ scalar, u }])[0];
+  if (r === null) throw new Error(X25519_INVALID);
+  return r;
+}
+function x25519GetPublicKey(secretKey) {
+  const r = x25519GetPublicKeyBatch([secretKey])[0];
+  if (r === null) throw new Error(X25519_INVALID);
+  return r;
+}
+const ED_D = 37095705934669439343138083508754565189542113879843219016388785533085940283555n;
+function ed25519ToMontgomery(publicKey) {        // the message of a refused key is re-derived on host integers (rare path)
+  const r = ed25519ToMontgomeryBatch([publicKey])[0];
+  if (r !== null) return r;
+  const P = X25519_P, y = leNumber(publicKey, 0, 32) & ((1n << 255n) - 1n);
+  if (y >= P) throw new Error('expected valid point.y: 0 <= n < ' + P + ', got ' + y);
+  const x2 = (y * y - 1n + P) % P * powMod((ED_D * y % P * y + 1n) % P, P - 2n, P) % P;
+  if (x2 !== 0n && powMod(x2, (P - 1n) / 2n, P) !== 1n) throw new Error('bad point: invalid y coordinate');
+  if (x2 === 0n && (publicKey[31] & 0x80)) throw new Error('bad point: x=0 and x_0=1');
+  throw new Error('invert: expected non-zero number');
+}
+
 
 // ---- codecs: array forms of Point.fromBytes / toBytes (compressed) --------------------------------
 //   weierstrass.ts:541-605, bls12-381.ts:377-459 (+ subgroup checks :567-577, :599-601), edwards.ts:405-436,620-628
@@ -696,4 +771,5 @@ function hashToCurveBatch(c, msgs, DST) {
 
 module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, DEFAULT_MIN_POINTS, setPointCache, clearPointCache, packPoints, packScalars, pippenger, multiplyUnsafeBatch, multiplyBaseBatch, ed25519VerifyBatch,
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
-                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, native };
+                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch,
+                   x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery, native };

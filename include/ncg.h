@@ -445,6 +445,38 @@ int ncg_ed25519_challenge_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_de
                                     const void* msgs_dev, const uint64_t* msg_off_dev, void* out_k32_dev,
                                     void* stream);
 
+/* ---- X25519 (RFC 7748) and the Ed25519 -> Curve25519 key conversion ---------------------------------
+ * Every row is 32 bytes as on the wire (little-endian), 4-byte aligned; out32[i] is the 32-byte result and out_ok[i] = 1,
+ * or 32 zero bytes and out_ok[i] = 0 where the reference throws.  n = 0 returns NCG_OK and touches nothing.
+ *
+ * ncg_x25519_batch: out32[i] = x25519.scalarMult(scalars[i], u[i]) = x25519.getSharedSecret(secret, peer)
+ * (src/abstract/montgomery.ts:314-331).  The scalar bytes are RAW: the call clamps them (adjustScalarBytes: b[0] &= 248,
+ * b[31] &= 127, b[31] |= 64).  Bit 255 of u is ignored and u is reduced mod p = 2^255 - 19, so the non-canonical encodings
+ * 2^255 - 19 .. 2^255 - 1 are accepted (RFC 7748 section 5).  The five u of low order - 0, 1, p - 1 and the two of order 8,
+ * in any encoding (p and p + 1 included) - give out_ok = 0 ('invalid private or public key received'), as would a zero
+ * result.  flags: NCG_X25519_ONE_SCALAR = `scalars` holds ONE 32-byte secret used for every row (a server's static key
+ * against n peer keys); any other bit returns NCG_ERR_INVALID_ARG.
+ *
+ * ncg_x25519_base_batch: out32[i] = x25519.getPublicKey(scalars[i]) = scalarMult(scalars[i], 9), computed like the
+ * reference's own hook (src/ed25519.ts:281-290): [k]B on the fixed-base Edwards table, then u = (Z + Y) / (Z - Y).
+ *
+ * ncg_ed25519_to_montgomery_batch: out32[i] = ed25519.utils.toMontgomery(pk32[i]) = (1 + y) / (1 - y) of
+ * Point.fromBytes(pk32[i]) under the strict rules (zip215 = false: y < p, a point of the curve, no sign bit on x = 0);
+ * out_ok = 0 where the decoding fails and for y = 1 (the identity: the reference's inversion of zero throws).
+ *
+ * Each lane runs the same instructions whatever its scalar (the ladder swaps by selects, nothing branches or indexes on
+ * a scalar bit), but the library makes no constant-time claim. */
+#define NCG_X25519_ONE_SCALAR 1
+int ncg_x25519_batch(ncg_ctx* ctx, size_t n, const void* scalars, const void* u, int flags, void* out32, uint8_t* out_ok);
+int ncg_x25519_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, const void* u_dev, int flags, void* out32_dev,
+                         uint8_t* out_ok_dev, void* stream);
+int ncg_x25519_base_batch(ncg_ctx* ctx, size_t n, const void* scalars, void* out32, uint8_t* out_ok);
+int ncg_x25519_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, void* out32_dev, uint8_t* out_ok_dev,
+                              void* stream);
+int ncg_ed25519_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk32, void* out32, uint8_t* out_ok);
+int ncg_ed25519_to_montgomery_batch_dev(ncg_ctx* ctx, size_t n, const void* pk32_dev, void* out32_dev, uint8_t* out_ok_dev,
+                                        void* stream);
+
 /* ---- measurement helpers (not on the product path) ------------------------------------ */
 /* ---- secp256k1 ECDSA batch verification --------------------------------------------------------
  * out_ok[i] = ecdsa.verify(sig[i], msgHash[i], publicKey[i], { prehash: false, format: 'compact', lowS })
@@ -545,6 +577,12 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * row, blocks of 64 lanes): 8 CoopXyzz::add(a, b) -> out, 9 the same with out aliasing a (the row is copied to out, then added
  * in place), 10 with out aliasing b, 11 CoopXyzz::dbl(a) -> out, 12 dbl in place, 13 CoopXyzz::copy; on the other fields ops
  * 8-13 leave out zero, as does any other op.  `variant` is ignored.
+ * field 16 = the X25519 ladder pieces (csrc/x25519.hpp), RAW words in and out: a = 36 words, b = 9 words, out = 36 words
+ * (field 15 is unassigned and refused).  op 0 one x25519_step with the swap bit `variant` & 1: a = x2 z2 x3 z3, b = x1, 9 raw
+ * limbs each at the bound the ladder stores them at (1: limbs below 2^29 + 2^19); out = x2 z2 x3 z3, 9 limbs each, again
+ * below that bound.  op 1 decodeU and the low-order test: a[0..8) = the LE words of an encoded u; out[0..8) = the canonical
+ * residue, out[8] = 0 for the five low-order values, else 1.  op 2 adjustScalarBytes: a[0..8) -> out[0..8).  Any other op
+ * leaves out zero.
  * bn254 G1 (NCG_BN254_G1) takes the MSM (every entry point, resident / precomputed / async / split / sharded), the batch
  * variable-base multiply, the pairwise add and normalize_batch; the reference has no byte format for it, so decode /
  * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch

@@ -19,6 +19,7 @@ FIELD_BLS12_381_FR = 0
 FIELD_BN254_FR = 5
 POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
+X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -128,6 +129,12 @@ _OPTIONAL_PROTOS = {
     "ncg_ed25519_verify_batch_msgs": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp],
     "ncg_ed25519_verify_batch_msgs_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "ncg_ed25519_challenge_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_x25519_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_x25519_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_x25519_base_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_x25519_base_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed25519_to_montgomery_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed25519_to_montgomery_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_points_upload": [_vp, _i32, _sz, _vp, ctypes.POINTER(_vp)],
     "ncg_points_from_encoded": [_vp, _i32, _sz, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)],
     "ncg_points_curve": [_vp],
@@ -563,6 +570,38 @@ class Engine:
                                                           ks.ctypes.data, 1 if zip215 else 0, ok.ctypes.data))
         return ok.astype(bool)
 
+    # ---- X25519 / toMontgomery: rows of 32 bytes -> (out uint8 [n, 32], ok bool [n]); a refused row is zero ----------------
+    def x25519_batch(self, scalars, us, one_scalar=False):
+        """x25519.scalarMult per row: scalars uint8 [n, 32] raw (clamped by the library), or ONE row with one_scalar; us [n, 32]."""
+        us = np.ascontiguousarray(us, dtype=np.uint8).reshape(-1, 32)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        n = us.shape[0]
+        if scalars.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of scalars and u coordinates must have equal length")
+        out, ok = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_x25519_batch(self.h, n, scalars.ctypes.data, us.ctypes.data, X25519_ONE_SCALAR if one_scalar else 0,
+                                                  out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def x25519_base_batch(self, scalars):
+        """x25519.getPublicKey per row"""
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        n = scalars.shape[0]
+        out, ok = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_x25519_base_batch(self.h, n, scalars.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ed25519_to_montgomery_batch(self, pks):
+        """ed25519.utils.toMontgomery per row"""
+        pks = np.ascontiguousarray(pks, dtype=np.uint8).reshape(-1, 32)
+        n = pks.shape[0]
+        out, ok = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed25519_to_montgomery_batch(self.h, n, pks.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
     def ed25519_verify_batch_msgs(self, sigs, pks, msgs_blob, msg_off, zip215=True):
         """sigs uint8 [n,64], pks [n,32], msgs_blob uint8 [total], msg_off uint64 [n+1] -> bool array [n];
         the challenge hash SHA-512(R || A || M) mod L runs on the device."""
@@ -818,16 +857,18 @@ class Engine:
         Fields 10-14: the group law of the MSM buckets on STORED accumulators (secp256k1, ed25519, bls12-381 G1, lane-paired G2,
         bn254 G1): a, b and the result [n, 36 | 36 | 56 | 112 | 36] raw words in acc_load's layout (for ops 0 / 1 b starts with a
         stored input point).  ops 0 madd(a, b), 1 madd(a, -b), 2 add, 3 dbl; fields 12 / 13 also the four-lane form: 8 add, 9 / 10
-        add with out aliasing a / b, 11 dbl, 12 dbl in place, 13 copy (elsewhere those leave out zero)."""
+        add with out aliasing a / b, 11 dbl, 12 dbl in place, 13 copy (elsewhere those leave out zero).
+        Field 16: the X25519 ladder pieces, a [n, 36], b [n, 9] -> [n, 36] (op 0 one ladder step on raw limbs, 1 decodeU + low-order
+        flag, 2 adjustScalarBytes; include/ncg.h)."""
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)
         n = a.shape[0]
         acc = {10: 36, 11: 36, 12: 56, 13: 112, 14: 36}
-        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18),
+        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18), 16: (36, 9),
                   **{f: (w, w) for f, w in acc.items()}}.get(field, (9, 9))
         if a.shape != (n, wa) or b.shape != (n, wb):   # the library reads n * wa and n * wb words
             raise ValueError("field_check: field %d takes a [n, %d] and b [n, %d]" % (field, wa, wb))
-        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, **acc}.get(field, 8)), dtype=np.uint32)
+        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, 16: 36, **acc}.get(field, 8)), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_field_check(self.h, field, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out

@@ -582,24 +582,29 @@ int ncg_add_pairs_batch(ncg_ctx* ctx, int curve, size_t n, const void* a, const 
   return hc.finish(ncg_add_pairs_batch_dev(ctx, curve, n, hc.dev(da), hc.dev(db), subtract, hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
 }
 
+// the ed25519 fixed-base table: computed on the host (33 x 128 affine Niels points), cached per context
+static int ensure_ed_base_table(ncg_ctx* ctx) {
+  if (ctx->base_tab[NCG_ED25519]) return NCG_OK;
+  std::vector<uint32_t> host(ncg::ed25519_fixed_table_words());
+  ncg::ed25519_build_fixed_table(host.data());
+  uint32_t* tab = nullptr;
+  NCG_HIP(ctx, hipMalloc((void**)&tab, host.size() * 4));
+  hipError_t e = hipMemcpy(tab, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    return set_err(ctx, NCG_ERR_HIP, "noble-gpu: uploading the ed25519 fixed-base table failed: %s", hipGetErrorString(e));
+  }
+  ctx->base_tab[NCG_ED25519] = tab;
+  return NCG_OK;
+}
+
 int ncg_mul_base_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* scalars_dev, void* out_affine_dev,
                            uint8_t* out_is_inf_dev, void* stream) {
   NCG_BEGIN(ctx, mul_base_rule(ctx, curve), n, scalars_dev, out_affine_dev, out_is_inf_dev);
   const hipStream_t st = stream_of(ctx, stream);
   if (int rc = ensure_mul_ws(ctx, curve, n > 8192 ? n : 8192, st)) return rc;
-  if (curve == NCG_ED25519) {  // table computed on the host (33 x 128 affine Niels points), cached per context
-    if (!ctx->base_tab[curve]) {
-      std::vector<uint32_t> host(ncg::ed25519_fixed_table_words());
-      ncg::ed25519_build_fixed_table(host.data());
-      uint32_t* tab = nullptr;
-      NCG_HIP(ctx, hipMalloc((void**)&tab, host.size() * 4));
-      hipError_t e = hipMemcpy(tab, host.data(), host.size() * 4, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(tab);
-        return set_err(ctx, NCG_ERR_HIP, "noble-gpu: uploading the ed25519 fixed-base table failed: %s", hipGetErrorString(e));
-      }
-      ctx->base_tab[curve] = tab;
-    }
+  if (curve == NCG_ED25519) {
+    if (int rc = ensure_ed_base_table(ctx)) return rc;
     NCG_HIP(ctx, ncg::ed25519_mul_base_batch(ctx->base_tab[curve], (const uint32_t*)scalars_dev, (uint32_t*)out_affine_dev,
                                              out_is_inf_dev, (int)n, (uint32_t*)ctx->mul_ws, st));
     return NCG_OK;
@@ -1701,16 +1706,66 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
   return hc.finish(ncg_ecdsa_verify_batch_dev(ctx, curve, n, hc.dev(sig), hc.dev(hash), hc.dev(pub), flags, hc.dev<uint8_t>(ok), ctx->stream));
 }
 
+// ---- X25519 (x25519.hip).  Rows are 32 bytes, read as 8 LE words: 4-byte aligned like every other byte row of this ABI.
+static Rule x25519_rule(ncg_ctx* ctx, int flags) {
+  return {"x25519_batch", (flags & ~NCG_X25519_ONE_SCALAR) == 0 ? NCG_OK
+                              : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: x25519_batch: unknown flag bits 0x%x", flags)};
+}
+int ncg_x25519_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, const void* u_dev, int flags, void* out32_dev,
+                         uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, x25519_rule(ctx, flags), n, scalars_dev, u_dev, out32_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::x25519_batch((const uint32_t*)scalars_dev, (const uint32_t*)u_dev, flags & NCG_X25519_ONE_SCALAR, (uint32_t*)out32_dev,
+                                 out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_x25519_batch(ncg_ctx* ctx, size_t n, const void* scalars, const void* u, int flags, void* out32, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, x25519_rule(ctx, flags), n, scalars, u, out32, out_ok);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, (flags & NCG_X25519_ONE_SCALAR) ? 32 : n * 32), du = hc.in(u, n * 32);
+  const int o = hc.out(out32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_x25519_batch_dev(ctx, n, hc.dev(sc), hc.dev(du), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_x25519_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, void* out32_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("x25519_base_batch"), n, scalars_dev, out32_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  const size_t need = ncg::x25519_base_tmp_words((int)n) * 4;
+  if (int rc = ncg_grow_buf(ctx, &ctx->mul_ws, &ctx->mul_ws_bytes, need, need, GrowWait::stream, st, true)) return rc;
+  if (int rc = ensure_ed_base_table(ctx)) return rc;
+  NCG_HIP(ctx, ncg::x25519_base_batch(ctx->base_tab[NCG_ED25519], (const uint32_t*)scalars_dev, (uint32_t*)out32_dev, out_ok_dev, (int)n,
+                                      (uint32_t*)ctx->mul_ws, st));
+  return NCG_OK;
+}
+int ncg_x25519_base_batch(ncg_ctx* ctx, size_t n, const void* scalars, void* out32, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("x25519_base_batch"), n, scalars, out32, out_ok);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, n * 32), o = hc.out(out32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_x25519_base_batch_dev(ctx, n, hc.dev(sc), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ed25519_to_montgomery_batch_dev(ncg_ctx* ctx, size_t n, const void* pk32_dev, void* out32_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ed25519_to_montgomery_batch"), n, pk32_dev, out32_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ed25519_to_montgomery_batch((const uint32_t*)pk32_dev, (uint32_t*)out32_dev, out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed25519_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk32, void* out32, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("ed25519_to_montgomery_batch"), n, pk32, out32, out_ok);
+  HostCall hc(ctx);
+  const int pk = hc.in(pk32, n * 32), o = hc.out(out32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed25519_to_montgomery_batch_dev(ctx, n, hc.dev(pk), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+
 // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
 // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
 // bn254 Fe9 Montgomery raw limbs 9 / 9 / 9; the MSM groups (fields 10-14: secp256k1, ed25519, bls12-381 G1, lane-paired G2, bn254 G1):
-// one stored accumulator, 4 FW words, for each of a, b and out
-static const size_t k_field_wa[15] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36},
-                    k_field_wb[15] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36},
-                    k_field_wo[15] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36};
+// one stored accumulator, 4 FW words, for each of a, b and out; the X25519 ladder pieces (field 16; 15 is unassigned) 36 / 9 / 36
+static const size_t k_field_wa[17] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36},
+                    k_field_wb[17] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36, 0, 9},
+                    k_field_wo[17] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36};
 static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {
   int rc = NCG_OK;
-  if (field < 0 || field > 14) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 16 || field == 15) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   else if (n > (1u << 24)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: batch too large (max 2^24)");
   return {"field_check", rc};
 }

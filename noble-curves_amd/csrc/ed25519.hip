@@ -456,6 +456,13 @@ hipError_t ed25519_mul_base_batch(const uint32_t* table, const uint32_t* scalars
   return hipGetLastError();
 }
 
+// the table walk alone: (X, Y, Z) per item (ED_PROJ_WORDS stored words) for a caller with its own finish (x25519.hip)
+hipError_t ed25519_mul_base_proj(const uint32_t* table, const uint32_t* scalars, uint32_t* proj_out, int n, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ed_mul_base, dim3((n + 255) / 256), dim3(256), 0, st, table, scalars, proj_out, n);
+  return hipGetLastError();
+}
+
 void ed25519_mul_var_host(const uint32_t* pt, const uint32_t* k, uint32_t* out, uint8_t* out_inf) {
   std::vector<uint32_t> tab(EdCfgGtab::TA * ED_NIELS_WORDS);
   ed25519_mul_var_lane<EdCfgGtab, false>(pt, k, out, out_inf, true, tab.data(), 1);

@@ -181,8 +181,24 @@ size_t ed25519_fixed_table_words();
 void ed25519_build_fixed_table(uint32_t* out_words);
 hipError_t ed25519_mul_base_batch(const uint32_t* table, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, int n,
                                   uint32_t* proj_tmp, hipStream_t st);
+hipError_t ed25519_mul_base_proj(const uint32_t* table, const uint32_t* scalars, uint32_t* proj_out, int n, hipStream_t st);
 void ed25519_mul_var_host(const uint32_t* pt, const uint32_t* k, uint32_t* out, uint8_t* out_inf);
 bool ed25519_verify_host(const uint32_t* sig, const uint32_t* pk, const uint32_t* k, const uint32_t* btab, bool zip215);
+
+// X25519 and ed25519.utils.toMontgomery (x25519.hip): rows of 8 LE words (32 bytes) in and out, out_ok = 0 and a zero row where
+// the reference throws.  one_scalar: `scalars` is one row used for every item.  x25519_base_batch walks the fixed-base Edwards
+// table of ed25519_build_fixed_table; tmp: x25519_base_tmp_words(n) words of device memory.
+hipError_t x25519_batch(const uint32_t* scalars, const uint32_t* u, int one_scalar, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+size_t x25519_base_tmp_words(int n);
+hipError_t x25519_base_batch(const uint32_t* table, const uint32_t* scalars, uint32_t* out, uint8_t* out_ok, int n, uint32_t* tmp,
+                             hipStream_t st);
+hipError_t ed25519_to_montgomery_batch(const uint32_t* pk, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+// the ladder pieces on raw words (ncg_field_check field 16): a 36, b 9, out 36 words per row
+hipError_t x25519_field_check(int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st);
+void x25519_host(const uint32_t* scalars, const uint32_t* u, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
+void x25519_base_host(const uint32_t* scalars, uint32_t* out, uint8_t* out_ok, int n);
+void ed25519_to_montgomery_host(const uint32_t* pk, uint32_t* out, uint8_t* out_ok, int n);
+int x25519_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
 // field-level self-check (ubench.hip): out[i] = op(a[i], b[i]) on the device field code
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,

@@ -18,6 +18,7 @@
 #include "msm_schedule.hpp"
 #include "fe9m_check.hpp"
 #include "group_check.hpp"
+#include "x25519.hip"
 
 using namespace ncg;
 
@@ -414,6 +415,23 @@ int ht_ed25519_mul_var(const uint32_t* pts, const uint32_t* scalars, uint32_t* o
   for (int i = 0; i < n; i++) ed25519_mul_var_host(pts + (size_t)i * 16, scalars + (size_t)i * 8, out + (size_t)i * 16, out_inf + i);
   return 0;
 }
+
+// X25519 on the CPU twins of x25519.hip: rows of 32 bytes (8 LE words); flags as ncg_x25519_batch.  ht_x25519_op: the pieces of
+// ncg_field_check field 16 (a 36, b 9, out 36 words), -1 for an unknown op.
+int ht_x25519(const uint32_t* scalars, const uint32_t* u, int flags, uint32_t* out, uint8_t* ok, int n) {
+  if (flags & ~1) return -1;
+  x25519_host(scalars, u, flags & 1, out, ok, n);
+  return 0;
+}
+int ht_x25519_base(const uint32_t* scalars, uint32_t* out, uint8_t* ok, int n) {
+  x25519_base_host(scalars, out, ok, n);
+  return 0;
+}
+int ht_ed25519_to_montgomery(const uint32_t* pk, uint32_t* out, uint8_t* ok, int n) {
+  ed25519_to_montgomery_host(pk, out, ok, n);
+  return 0;
+}
+int ht_x25519_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return x25519_check_host(op, variant, a, b, out); }
 
 // Fp2 square root lane: in = c0 c1 wire (24 words); out = root wire; returns 1 if a root exists
 int ht_fp2_sqrt(const uint32_t* in, uint32_t* out) {

@@ -5,6 +5,9 @@ The shim does the argument checks of the reference and hands (sig, pk, msg) to t
 SHA-512 challenge k = SHA-512(R || A || M) mod L (edwards.ts:984, :900-906, :866-868; @noble/hashes in
 the reference) and the curve arithmetic both run in HIP kernels (`ncg_ed25519_verify_batch_msgs`).
 `hash_on_device=False` computes k with hashlib instead and uses the k32 entry point.
+
+`toMontgomery` / `toMontgomery_batch` (ed25519.utils.toMontgomery: the X25519 key of an Ed25519 public key) run on the device
+(`ncg_ed25519_to_montgomery_batch`); `toMontgomerySecret` is one SHA-512 on the host.
 """
 import hashlib
 
@@ -63,3 +66,52 @@ def verify_batch(sigs, msgs, publicKeys, zip215=True, engine=None, hash_on_devic
 def verify(sig, msg, publicKey, zip215=True, engine=None):
     """eddsa.verify (edwards.ts:942): one signature = a batch of one."""
     return verify_batch([sig], [msg], [publicKey], zip215, engine)[0]
+
+
+# ---- ed25519.utils.toMontgomery / toMontgomerySecret (src/ed25519.ts:128-143, edwards.ts:1022-1031)
+P = 2**255 - 19
+_D = -121665 * pow(121666, -1, P) % P
+
+
+def toMontgomery_batch(publicKeys, engine=None):
+    """u = (1 + y) / (1 - y) of Point.fromBytes(publicKey) (strict rules) for every key, on the device
+    (`ncg_ed25519_to_montgomery_batch`): (list of bytes-or-None, list of bool), None where the reference throws."""
+    K = np.zeros((len(publicKeys), 32), np.uint8)
+    for i, pk in enumerate(publicKeys):
+        K[i] = np.frombuffer(_abytes(pk, 32, "point"), np.uint8)
+    out, ok = (engine or get_engine()).ed25519_to_montgomery_batch(K)
+    ok = [bool(x) for x in ok]
+    return [out[i].tobytes() if ok[i] else None for i in range(len(ok))], ok
+
+
+def _to_montgomery_error(pk):
+    """the message of the error the reference throws for a key the device refused (rare path: host integers)"""
+    y = int.from_bytes(pk, "little") & ((1 << 255) - 1)
+    if y >= P:
+        return "expected valid point.y: 0 <= n < %d, got %d" % (P, y)
+    x2 = (y * y - 1) * pow(_D * y * y + 1, -1, P) % P
+    if x2 and pow(x2, (P - 1) // 2, P) != 1:
+        return "bad point: invalid y coordinate"
+    if x2 == 0 and pk[31] & 0x80:
+        return "bad point: x=0 and x_0=1"
+    return "invert: expected non-zero number"   # y = 1
+
+
+def toMontgomery(publicKey, engine=None):
+    """ed25519.utils.toMontgomery: a batch of one; raises ValueError with the reference's message where it throws"""
+    out, ok = toMontgomery_batch([publicKey], engine)
+    if not ok[0]:
+        raise ValueError(_to_montgomery_error(_abytes(publicKey, 32, "point")))
+    return out[0]
+
+
+def toMontgomerySecret(secretKey):
+    """ed25519.utils.toMontgomerySecret: the clamped first half of SHA-512(secretKey), on the host"""
+    if not isinstance(secretKey, (bytes, bytearray, memoryview, np.ndarray)):   # abytes without a title (ed25519.ts:138)
+        raise TypeError("expected Uint8Array of length 32, got type=%s" % type(secretKey).__name__)
+    if len(bytes(secretKey)) != 32:
+        raise ValueError("expected Uint8Array of length 32, got length=%d" % len(bytes(secretKey)))
+    h = bytearray(hashlib.sha512(bytes(secretKey)).digest()[:32])
+    h[0] &= 248
+    h[31] = (h[31] & 127) | 64
+    return bytes(h)
