@@ -9,6 +9,11 @@
 //   ed25519VerifyBatch(sigs, pks, ks, zip215: bool)  -> Uint8Array n (0 / 1)
 //   x25519(kind, scalars | null, rows)               -> Uint8Array n * 33 (32-byte results, then ok flags); kind 0 scalarMult
 //                                                       (scalars: n rows, or ONE row used for every u), 1 getPublicKey, 2 toMontgomery
+//   ristretto(mode, a, b | null)                     -> ristretto255 on packed rows; mode 0 decode (a: n x 32) -> n x 64 points + n ok flags,
+//                                                       1 encode (a: n x 64) -> n x 32, 2 equals (a, b: n x 64) -> n flags,
+//                                                       3 deriveToCurve (a: n x 64) -> n x 32, 4 multiply (a: n x 32 encodings, b: n or ONE
+//                                                       scalar row) -> n x 32 + n ok flags, 5 BASE.multiply (a: n x 32 scalars) -> n x 32,
+//                                                       6 msm (a: encodings, b: scalars) -> 32 bytes; throws naming a bad index
 //   decodePoints(curveId, encoded, zip215: bool)     -> Uint8Array n * (PB + 2)  (points, ok flags, inf flags)
 //   encodePoints(curveId, points)                    -> Uint8Array n * (EB + 1)  (encodings, ok flags)
 //   aggregateEncoded(curveId, encoded, zip215)       -> Uint8Array PB + 1 (flag); throws naming a bad index
@@ -259,6 +264,43 @@ static napi_value X25519(napi_env env, napi_callback_info info) {
   if (n && kind == 0) rc = ncg_x25519_batch(g_ctx, n, sc, rows, sl != rl ? NCG_X25519_ONE_SCALAR : 0, out, out + n * 32);
   else if (n && kind == 1) rc = ncg_x25519_base_batch(g_ctx, n, rows, out, out + n * 32);
   else if (n) rc = ncg_ed25519_to_montgomery_batch(g_ctx, n, rows, out, out + n * 32);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
+// ristretto255 on packed rows (ncg_ristretto_*): one entry, the operation chosen by `mode` (see the list at the top of this file).
+static napi_value Ristretto(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  static const size_t in_row[7] = {32, 64, 64, 64, 32, 32, 32}, out_row[7] = {65, 32, 1, 32, 33, 32, 0};
+  int32_t mode;
+  uint8_t *a, *b = nullptr, *out;
+  size_t al, bl = 0;
+  bool ok = argc >= 3 && napi_get_value_int32(env, argv[0], &mode) == napi_ok && mode >= 0 && mode <= 6 && get_u8(env, argv[1], &a, &al) &&
+            al % in_row[mode] == 0;
+  const bool two = ok && (mode == 2 || mode == 4 || mode == 6);
+  if (two) ok = get_u8(env, argv[2], &b, &bl);
+  const size_t n = ok ? al / in_row[mode] : 0;
+  if (ok && mode == 2) ok = bl == al;
+  if (ok && mode == 4) ok = bl == al || bl == 32;
+  if (ok && mode == 6) ok = bl == al;
+  if (!ok) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: ristretto(mode, rows, rows | null)");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, mode == 6 ? 32 : n * out_row[mode], &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (mode == 6) rc = ncg_ristretto_msm(g_ctx, n, a, b, out, nullptr);
+  else if (n == 0) rc = 0;
+  else if (mode == 0) rc = ncg_ristretto_decode_batch(g_ctx, n, a, out, out + n * 64);
+  else if (mode == 1) rc = ncg_ristretto_encode_batch(g_ctx, n, a, out);
+  else if (mode == 2) rc = ncg_ristretto_equals_batch(g_ctx, n, a, b, out);
+  else if (mode == 3) rc = ncg_ristretto_from_uniform_batch(g_ctx, n, a, out, nullptr);
+  else if (mode == 4) rc = ncg_ristretto_mul_batch(g_ctx, n, a, b, bl != al ? NCG_RISTRETTO_ONE_SCALAR : 0, out, out + n * 32);
+  else rc = ncg_ristretto_mul_base_batch(g_ctx, n, a, out);
   if (rc != 0) return throw_native(env);
   return res;
 }
@@ -907,7 +949,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ristretto", Ristretto}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -8,6 +8,9 @@
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
 //   x25519ScalarMultBatch(items)           - array form of x25519.scalarMult / getSharedSecret (abstract/montgomery.ts:314-331);
 //   x25519GetPublicKeyBatch(secretKeys)      x25519.getPublicKey; ed25519ToMontgomeryBatch(publicKeys): ed25519.utils.toMontgomery
+//   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
+//                                            BASE.multiply, an MSM from encodings and ristretto255_hasher.deriveToCurve
+//                                            (src/ed25519.ts:443-668), with single-item forms that throw the reference's messages
 //   fftFr(values, opts)                    - FFT(roots, Fr).direct / .inverse (abstract/fft.ts:518-577)
 //   polyFr(opts)                           - poly(Fr, roots, ...) on arrays of bigint (abstract/fft.ts:583-926): add, sub, dot,
 //                                            mul, convolve, shift, eval, monomial.eval, lagrange.basis / eval
@@ -559,6 +562,103 @@ function ed25519ToMontgomery(publicKey) {        // the message of a refused key
   throw new Error('invert: expected non-zero number');
 }
 
+// ---- ristretto255 (src/ed25519.ts:443-668, RFC 9496).  An element is its 32-byte encoding on this side; fromBytes hands back the
+// Edwards representative as a 64-byte ed25519 wire point (x || y), which the NCG_ED25519 calls take.  Batch forms return null where
+// the reference throws; the single-item forms throw its messages ('encoding 1' decided here from canonicity and parity).
+const RISTRETTO_ENC1 = 'invalid ristretto255 encoding 1', RISTRETTO_ENC2 = 'invalid ristretto255 encoding 2';
+function abytesN(b, len) {                       // utils abytes(value, length) without a title
+  const bytes = b instanceof Uint8Array;
+  if (!bytes || b.length !== len) throw new Error('expected Uint8Array of length ' + len + ', got ' + (bytes ? `length=${b.length}` : `type=${typeof b}`));
+  return b;
+}
+function ristrettoPack(items, len) {
+  const out = new Uint8Array(len * items.length);
+  items.forEach((b, i) => out.set(abytesN(b, len), len * i));
+  return out;
+}
+function ristrettoScalars(ks, lo) {              // Point.multiply: 1 <= k < L (the MSM also takes 0)
+  const out = new Uint8Array(32 * ks.length);
+  ks.forEach((k, i) => {
+    if (typeof k !== 'bigint' || k < lo || k >= ED_L) throw new Error('invalid scalar: expected 1 <= sc < curve.n');
+    leBytes(k, 32, out, 32 * i);
+  });
+  return out;
+}
+function ristrettoSplit(packed, n, len, flags) {
+  const out = new Array(n);
+  for (let i = 0; i < n; i++) out[i] = !flags || packed[len * n + i] === 1 ? packed.slice(len * i, len * i + len) : null;
+  return out;
+}
+function ristrettoFromBytesBatch(encodings) {    // -> 64-byte wire points (x || y) or null
+  const n = encodings.length, E = ristrettoPack(encodings, 32);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.ristretto(0, E, null), n, 64, true);
+}
+function ristrettoToBytesBatch(points) {         // 64-byte wire points -> encodings
+  const n = points.length, A = ristrettoPack(points, 64);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.ristretto(1, A, null), n, 32, false);
+}
+function ristrettoEqualsBatch(as, bs) {
+  if (as.length !== bs.length) throw new Error('arrays of points must have equal length');
+  const A = ristrettoPack(as, 64), B = ristrettoPack(bs, 64);
+  if (as.length === 0) return [];
+  init();
+  return Array.from(native.ristretto(2, A, B)).map((x) => x === 1);
+}
+function ristrettoDeriveToCurveBatch(rows64) {
+  const n = rows64.length, A = ristrettoPack(rows64, 64);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.ristretto(3, A, null), n, 32, false);
+}
+// encodings x scalars (bigint[]), or ONE bigint against every row -> encodings of the products, null where a row does not decode
+function ristrettoMultiplyBatch(encodings, scalars) {
+  const one = typeof scalars === 'bigint';
+  if (!one && scalars.length !== encodings.length) throw new Error('arrays of points and scalars must have equal length');
+  const n = encodings.length, E = ristrettoPack(encodings, 32), K = ristrettoScalars(one ? [scalars] : scalars, 1n);
+  if (n === 0) return [];
+  init();
+  // (the native call tells the two forms apart by the length of K; for n = 1 they are the same call)
+  return ristrettoSplit(native.ristretto(4, E, K), n, 32, true);
+}
+function ristrettoMultiplyBaseBatch(scalars) {
+  const n = scalars.length, K = ristrettoScalars(scalars, 1n);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.ristretto(5, K, null), n, 32, false);
+}
+function ristrettoCanonicalEven(b) { return (b[0] & 1) === 0 && leNumber(b, 0, 32) < X25519_P; }
+function ristrettoMsm(encodings, scalars) {      // -> the encoding of sum k_i P_i; throws like fromBytes on a bad encoding
+  if (scalars.length !== encodings.length) throw new Error('arrays of points and scalars must have equal length');
+  const E = ristrettoPack(encodings, 32), K = ristrettoScalars(scalars, 0n);
+  encodings.forEach((b) => { if (!ristrettoCanonicalEven(b)) throw new Error(RISTRETTO_ENC1); });
+  init();
+  try {
+    return native.ristretto(6, E, K);
+  } catch (e) {
+    if (/invalid ristretto255 encoding at index/.test(e.message)) throw new Error(RISTRETTO_ENC2);
+    throw e;
+  }
+}
+function ristrettoFromBytes(b) {
+  abytesN(b, 32);
+  if (!ristrettoCanonicalEven(b)) throw new Error(RISTRETTO_ENC1);
+  const r = ristrettoFromBytesBatch([b])[0];
+  if (r === null) throw new Error(RISTRETTO_ENC2);
+  return r;
+}
+function ristrettoToBytes(point) { return ristrettoToBytesBatch([point])[0]; }
+function ristrettoEquals(a, b) { return ristrettoEqualsBatch([a], [b])[0]; }
+function ristrettoMultiply(encoding, k) {
+  ristrettoFromBytes(encoding);                  // the reference decodes first: its messages come first
+  return ristrettoMultiplyBatch([encoding], [k])[0];
+}
+function ristrettoMultiplyBase(k) { return ristrettoMultiplyBaseBatch([k])[0]; }
+function ristrettoDeriveToCurve(bytes64) { return ristrettoDeriveToCurveBatch([bytes64])[0]; }
+
 
 // ---- codecs: array forms of Point.fromBytes / toBytes (compressed) --------------------------------
 //   weierstrass.ts:541-605, bls12-381.ts:377-459 (+ subgroup checks :567-577, :599-601), edwards.ts:405-436,620-628
@@ -772,4 +872,7 @@ function hashToCurveBatch(c, msgs, DST) {
 module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, DEFAULT_MIN_POINTS, setPointCache, clearPointCache, packPoints, packScalars, pippenger, multiplyUnsafeBatch, multiplyBaseBatch, ed25519VerifyBatch,
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
                    fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch,
-                   x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery, native };
+                   x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery,
+                   ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
+                   ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
+                   ristrettoDeriveToCurve, native };

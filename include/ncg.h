@@ -477,6 +477,60 @@ int ncg_ed25519_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk32, vo
 int ncg_ed25519_to_montgomery_batch_dev(ncg_ctx* ctx, size_t n, const void* pk32_dev, void* out32_dev, uint8_t* out_ok_dev,
                                         void* stream);
 
+/* ---- ristretto255 (RFC 9496): codecs, equals, hash-to-group, multiply and MSM ---------------------------
+ * The prime-order group over curve25519: _RistrettoPoint and ristretto255_hasher of src/ed25519.ts:443-668.  An element crosses
+ * as its 32-byte encoding; on the device it is an ed25519 wire point (x || y, 64 bytes), its Edwards REPRESENTATIVE.  A
+ * representative is one of four (P + the points of order 1, 2, 4 encode alike), so it may be fed to every NCG_ED25519 entry
+ * point - MSM, resident sets, add pairs, multiplies - but two elements are compared only through ncg_ristretto_equals_batch or
+ * their encodings, never through their coordinates.  Rows are 32 bytes (64 for uniform input and for wire points), 4-byte
+ * aligned; n = 0 returns NCG_OK and touches nothing (ncg_ristretto_msm excepted, below).
+ *
+ * ncg_ristretto_decode_batch: out_affine[i] = the representative of RistrettoPoint.fromBytes(enc[i]) (:510-533), out_ok[i] = 1;
+ * a zero row and out_ok[i] = 0 where the reference throws: s >= p - bit 255 set included, the opposite of the rule the map's
+ * parser has - or s odd ('invalid ristretto255 encoding 1'); no square root, t odd or y = 0 ('... encoding 2').
+ * ncg_ristretto_encode_batch: out32[i] = toBytes() (:548-572) of the wire point i.  Any point of the curve is accepted, as in
+ * the reference's fromAffine; the result for a pair that is not on the curve is unspecified.
+ * ncg_ristretto_equals_batch: out_eq[i] = a[i].equals(b[i]) (:578-586) on wire points: x1 y2 == y1 x2 or y1 y2 == x1 x2.
+ * ncg_ristretto_from_uniform_batch: out32[i] = ristretto255_hasher.deriveToCurve(bytes64[i]).toBytes() (:658-666; the Elligator
+ * map :443-461 on each half, bit 255 of a half masked and the rest reduced mod p, then one addition).  out_affine may be
+ * NULL; otherwise it also receives the representative R1 + R2.  hashToCurve is this after expand_message_xmd(msg, DST, 64,
+ * SHA-512), which the host shim computes.
+ * ncg_ristretto_mul_batch: out32[i] = fromBytes(enc[i]).multiply(k[i]).toBytes(): decode, the ed25519 variable-base multiply,
+ * encode, all on the device - only bytes cross.  flags: NCG_RISTRETTO_ONE_SCALAR = `scalars` holds ONE 32-byte scalar used for
+ * every row (broadcast on the device: an OPRF server's blindEvaluate); any other bit returns NCG_ERR_INVALID_ARG.  A rejected
+ * encoding gives out_ok[i] = 0 and a zero row (its lane multiplies the identity).  Scalars as for ncg_mul_var_batch on
+ * NCG_ED25519: any k below 2^256, exact integer multiples, k = 0 gives the identity (32 zero bytes); the reference's range
+ * 1 <= k < L is the host shim's to enforce.
+ * ncg_ristretto_mul_base_batch: out32[i] = BASE.multiply(k[i]).toBytes() on the fixed-base Edwards table of
+ * ncg_mul_base_batch, encoded from the projective result without the inversion of an affine conversion.
+ * ncg_ristretto_msm: out32 = toBytes(sum_i k[i] fromBytes(enc[i])): decode, then the NCG_ED25519 path of ncg_msm on the decoded
+ * points where they lie, then the encoding of the one result.  out32 is HOST memory in both forms.  Scalars and their error
+ * as for ncg_msm (below the group order).  An encoding the reference rejects fails the call with NCG_ERR_INVALID_ARG and
+ * *out_bad_index = its position (else -1), as ncg_aggregate_encoded does.  A zero sum gives 32 zero bytes - the identity is a
+ * valid element.  n = 0 does what ncg_msm does: it WRITES the identity (32 zero bytes) and therefore requires out32.
+ * The library makes no constant-time claim. */
+#define NCG_RISTRETTO_ONE_SCALAR 1
+int ncg_ristretto_decode_batch(ncg_ctx* ctx, size_t n, const void* enc, void* out_affine, uint8_t* out_ok);
+int ncg_ristretto_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, void* out_affine_dev, uint8_t* out_ok_dev,
+                                   void* stream);
+int ncg_ristretto_encode_batch(ncg_ctx* ctx, size_t n, const void* affine, void* out32);
+int ncg_ristretto_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine_dev, void* out32_dev, void* stream);
+int ncg_ristretto_equals_batch(ncg_ctx* ctx, size_t n, const void* a, const void* b, uint8_t* out_eq);
+int ncg_ristretto_equals_batch_dev(ncg_ctx* ctx, size_t n, const void* a_dev, const void* b_dev, uint8_t* out_eq_dev,
+                                   void* stream);
+int ncg_ristretto_from_uniform_batch(ncg_ctx* ctx, size_t n, const void* bytes64, void* out32, void* out_affine);
+int ncg_ristretto_from_uniform_batch_dev(ncg_ctx* ctx, size_t n, const void* bytes64_dev, void* out32_dev,
+                                         void* out_affine_dev, void* stream);
+int ncg_ristretto_mul_batch(ncg_ctx* ctx, size_t n, const void* enc, const void* scalars, int flags, void* out32,
+                            uint8_t* out_ok);
+int ncg_ristretto_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, int flags,
+                                void* out32_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_ristretto_mul_base_batch(ncg_ctx* ctx, size_t n, const void* scalars, void* out32);
+int ncg_ristretto_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, void* out32_dev, void* stream);
+int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scalars, void* out32, int64_t* out_bad_index);
+int ncg_ristretto_msm_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, void* out32,
+                          int64_t* out_bad_index, void* stream);
+
 /* ---- measurement helpers (not on the product path) ------------------------------------ */
 /* ---- secp256k1 ECDSA batch verification --------------------------------------------------------
  * out_ok[i] = ecdsa.verify(sig[i], msgHash[i], publicKey[i], { prehash: false, format: 'compact', lowS })
@@ -583,6 +637,12 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * below that bound.  op 1 decodeU and the low-order test: a[0..8) = the LE words of an encoded u; out[0..8) = the canonical
  * residue, out[8] = 0 for the five low-order values, else 1.  op 2 adjustScalarBytes: a[0..8) -> out[0..8).  Any other op
  * leaves out zero.
+ * field 17 = the ristretto255 pieces (csrc/ristretto.hpp), RAW words in and out: a = 36 words, b = 9 words, out = 36 words,
+ * every input a field element of 9 raw limbs below 2^29 + 2^19.  op 0 SQRT_RATIO_M1(u, v) (uvRatio, src/ed25519.ts:107-125):
+ * a[0..9) = u, b = v; out[0..9) = the raw limbs of the value (the non-negative root of u / v, or of sqrt(-1) u / v where u / v
+ * is no square), out[9] = 1 if u / v is a square.  op 1 the encoder: a = X Y Z T of an extended point; out[0..8) = the LE
+ * words of its encoding.  op 2 the Elligator map: a[0..9) = r0; out = X Y Z T of the extended representative, 9 raw limbs
+ * each.  Any other op leaves out zero.  `variant` is ignored.
  * bn254 G1 (NCG_BN254_G1) takes the MSM (every entry point, resident / precomputed / async / split / sharded), the batch
  * variable-base multiply, the pairwise add and normalize_batch; the reference has no byte format for it, so decode /
  * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch

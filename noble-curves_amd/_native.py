@@ -20,6 +20,7 @@ FIELD_BN254_FR = 5
 POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
 X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
+RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -135,6 +136,20 @@ _OPTIONAL_PROTOS = {
     "ncg_x25519_base_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ed25519_to_montgomery_batch": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ed25519_to_montgomery_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ristretto_decode_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ristretto_encode_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ristretto_encode_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_equals_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_equals_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ristretto_from_uniform_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_from_uniform_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ristretto_mul_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_ristretto_mul_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_ristretto_mul_base_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ristretto_mul_base_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_msm": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
+    "ncg_ristretto_msm_dev": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
     "ncg_points_upload": [_vp, _i32, _sz, _vp, ctypes.POINTER(_vp)],
     "ncg_points_from_encoded": [_vp, _i32, _sz, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)],
     "ncg_points_curve": [_vp],
@@ -602,6 +617,84 @@ class Engine:
             self._check(self.lib.ncg_ed25519_to_montgomery_batch(self.h, n, pks.ctypes.data, out.ctypes.data, ok.ctypes.data))
         return out, ok.astype(bool)
 
+    # ---- ristretto255: encodings and scalars uint8 [n, 32], Edwards representatives (ed25519 wire points) [n, 64] ------------
+    def ristretto_decode_batch(self, enc):
+        """RistrettoPoint.fromBytes per row -> (representatives [n, 64], ok bool [n]); a rejected row is zero"""
+        enc = np.ascontiguousarray(enc, dtype=np.uint8).reshape(-1, 32)
+        n = enc.shape[0]
+        out, ok = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ristretto_decode_batch(self.h, n, enc.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ristretto_encode_batch(self, pts):
+        """toBytes of every wire point -> [n, 32]"""
+        pts = np.ascontiguousarray(pts, dtype=np.uint8).reshape(-1, 64)
+        out = np.zeros((pts.shape[0], 32), dtype=np.uint8)
+        if pts.shape[0]:
+            self._check(self.lib.ncg_ristretto_encode_batch(self.h, pts.shape[0], pts.ctypes.data, out.ctypes.data))
+        return out
+
+    def ristretto_equals_batch(self, a, b):
+        """a[i].equals(b[i]) on wire points -> bool [n]"""
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 64)
+        b = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, 64)
+        if a.shape != b.shape:
+            raise ValueError("arrays of points must have equal length")
+        out = np.zeros((a.shape[0],), dtype=np.uint8)
+        if a.shape[0]:
+            self._check(self.lib.ncg_ristretto_equals_batch(self.h, a.shape[0], a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out.astype(bool)
+
+    def ristretto_from_uniform_batch(self, bytes64, want_affine=False):
+        """deriveToCurve(bytes64[i]).toBytes() -> (encodings [n, 32], representatives [n, 64] or None)"""
+        b = np.ascontiguousarray(bytes64, dtype=np.uint8).reshape(-1, 64)
+        n = b.shape[0]
+        out = np.zeros((n, 32), dtype=np.uint8)
+        aff = np.zeros((n, 64), dtype=np.uint8) if want_affine else None
+        if n:
+            self._check(self.lib.ncg_ristretto_from_uniform_batch(self.h, n, b.ctypes.data, out.ctypes.data,
+                                                                  aff.ctypes.data if want_affine else None))
+        return out, aff
+
+    def ristretto_mul_batch(self, enc, scalars, one_scalar=False):
+        """fromBytes(enc[i]).multiply(k[i]).toBytes() -> (out [n, 32], ok bool [n]); scalars [n, 32], or ONE row with one_scalar"""
+        enc = np.ascontiguousarray(enc, dtype=np.uint8).reshape(-1, 32)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        n = enc.shape[0]
+        if scalars.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of points and scalars must have equal length")
+        out, ok = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ristretto_mul_batch(self.h, n, enc.ctypes.data, scalars.ctypes.data,
+                                                         RISTRETTO_ONE_SCALAR if one_scalar else 0, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ristretto_mul_base_batch(self, scalars):
+        """BASE.multiply(k[i]).toBytes() -> [n, 32]"""
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((scalars.shape[0], 32), dtype=np.uint8)
+        if scalars.shape[0]:
+            self._check(self.lib.ncg_ristretto_mul_base_batch(self.h, scalars.shape[0], scalars.ctypes.data, out.ctypes.data))
+        return out
+
+    def ristretto_msm(self, enc, scalars):
+        """toBytes(sum k[i] fromBytes(enc[i])) -> uint8 [32]; NativeError naming the index of an encoding that does not decode
+        (its position is also the `bad_index` attribute of the error)"""
+        enc = np.ascontiguousarray(enc, dtype=np.uint8).reshape(-1, 32)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        n = enc.shape[0]
+        if scalars.shape[0] != n:
+            raise ValueError("arrays of points and scalars must have equal length")
+        out, bad = np.zeros((32,), dtype=np.uint8), ctypes.c_int64(-1)
+        rc = self.lib.ncg_ristretto_msm(self.h, n, enc.ctypes.data if n else None, scalars.ctypes.data if n else None, out.ctypes.data,
+                                        ctypes.byref(bad))
+        if rc:
+            err = NativeError((self.lib.ncg_last_error(self.h) or b"").decode() or "noble-gpu: native call failed (%d)" % rc)
+            err.bad_index = int(bad.value)
+            raise err
+        return out
+
     def ed25519_verify_batch_msgs(self, sigs, pks, msgs_blob, msg_off, zip215=True):
         """sigs uint8 [n,64], pks [n,32], msgs_blob uint8 [total], msg_off uint64 [n+1] -> bool array [n];
         the challenge hash SHA-512(R || A || M) mod L runs on the device."""
@@ -859,16 +952,17 @@ class Engine:
         stored input point).  ops 0 madd(a, b), 1 madd(a, -b), 2 add, 3 dbl; fields 12 / 13 also the four-lane form: 8 add, 9 / 10
         add with out aliasing a / b, 11 dbl, 12 dbl in place, 13 copy (elsewhere those leave out zero).
         Field 16: the X25519 ladder pieces, a [n, 36], b [n, 9] -> [n, 36] (op 0 one ladder step on raw limbs, 1 decodeU + low-order
-        flag, 2 adjustScalarBytes; include/ncg.h)."""
+        flag, 2 adjustScalarBytes; include/ncg.h).  Field 17: the ristretto255 pieces, the same shapes (op 0 SQRT_RATIO_M1, 1 the
+        encoder on X Y Z T, 2 the Elligator map)."""
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)
         n = a.shape[0]
         acc = {10: 36, 11: 36, 12: 56, 13: 112, 14: 36}
-        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18), 16: (36, 9),
+        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18), 16: (36, 9), 17: (36, 9),
                   **{f: (w, w) for f, w in acc.items()}}.get(field, (9, 9))
         if a.shape != (n, wa) or b.shape != (n, wb):   # the library reads n * wa and n * wb words
             raise ValueError("field_check: field %d takes a [n, %d] and b [n, %d]" % (field, wa, wb))
-        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, 16: 36, **acc}.get(field, 8)), dtype=np.uint32)
+        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, 16: 36, 17: 36, **acc}.get(field, 8)), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_field_check(self.h, field, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out

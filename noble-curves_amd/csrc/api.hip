@@ -373,6 +373,7 @@ void ncg_destroy(ncg_ctx* ctx) {
       if (ctx->ntt_tab[f][i]) (void)hipFree(ctx->ntt_tab[f][i]);
   if (ctx->ntt_ws) (void)hipFree(ctx->ntt_ws);
   if (ctx->poly_ws) (void)hipFree(ctx->poly_ws);
+  if (ctx->rist_ws) (void)hipFree(ctx->rist_ws);
   (void)ncg_comm_destroy(ctx);
   if (ctx->comm_buf) (void)hipFree(ctx->comm_buf);
   if (ctx->sync_land) (void)hipHostFree(ctx->sync_land);
@@ -1756,16 +1757,166 @@ int ncg_ed25519_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk32, vo
   return hc.finish(ncg_ed25519_to_montgomery_batch_dev(ctx, n, hc.dev(pk), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
+// ---- ristretto255 (ristretto.hip).  Encodings and scalars are rows of 32 bytes read as 8 LE words, Edwards representatives are
+// ed25519 wire points.  The _dev forms keep what lies between their kernels in ctx->rist_ws, never in ctx->scratch.
+static int ensure_rist_ws(ncg_ctx* ctx, size_t bytes, hipStream_t st) {
+  return ncg_grow_buf(ctx, &ctx->rist_ws, &ctx->rist_ws_bytes, bytes, bytes + (bytes >> 2), GrowWait::stream, st);
+}
+int ncg_ristretto_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, void* out_affine_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ristretto_decode_batch"), n, enc_dev, out_affine_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ristretto_decode_batch((const uint32_t*)enc_dev, (uint32_t*)out_affine_dev, out_ok_dev, 0, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ristretto_decode_batch(ncg_ctx* ctx, size_t n, const void* enc, void* out_affine, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("ristretto_decode_batch"), n, enc, out_affine, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc, n * 32), o = hc.out(out_affine, n * 64), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_decode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ristretto_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine_dev, void* out32_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ristretto_encode_batch"), n, affine_dev, out32_dev);
+  NCG_HIP(ctx, ncg::ristretto_encode_batch((const uint32_t*)affine_dev, (uint32_t*)out32_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ristretto_encode_batch(ncg_ctx* ctx, size_t n, const void* affine, void* out32) {
+  NCG_BEGIN(ctx, no_rule("ristretto_encode_batch"), n, affine, out32);
+  HostCall hc(ctx);
+  const int in = hc.in(affine, n * 64), o = hc.out(out32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_encode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), ctx->stream));
+}
+int ncg_ristretto_equals_batch_dev(ncg_ctx* ctx, size_t n, const void* a_dev, const void* b_dev, uint8_t* out_eq_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ristretto_equals_batch"), n, a_dev, b_dev, out_eq_dev);
+  NCG_HIP(ctx, ncg::ristretto_equals_batch((const uint32_t*)a_dev, (const uint32_t*)b_dev, out_eq_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ristretto_equals_batch(ncg_ctx* ctx, size_t n, const void* a, const void* b, uint8_t* out_eq) {
+  NCG_BEGIN(ctx, no_rule("ristretto_equals_batch"), n, a, b, out_eq);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * 64), db = hc.in(b, n * 64), o = hc.out(out_eq, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_equals_batch_dev(ctx, n, hc.dev(da), hc.dev(db), hc.dev<uint8_t>(o), ctx->stream));
+}
+// out_affine_dev / out_affine may be NULL: the encodings alone
+int ncg_ristretto_from_uniform_batch_dev(ncg_ctx* ctx, size_t n, const void* bytes64_dev, void* out32_dev, void* out_affine_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ristretto_from_uniform_batch"), n, bytes64_dev, out32_dev);
+  NCG_HIP(ctx, ncg::ristretto_from_uniform_batch((const uint32_t*)bytes64_dev, (uint32_t*)out32_dev, (uint32_t*)out_affine_dev, (int)n,
+                                                 stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ristretto_from_uniform_batch(ncg_ctx* ctx, size_t n, const void* bytes64, void* out32, void* out_affine) {
+  NCG_BEGIN(ctx, no_rule("ristretto_from_uniform_batch"), n, bytes64, out32);
+  HostCall hc(ctx);
+  const int in = hc.in(bytes64, n * 64), o = hc.out(out32, n * 32), aff = out_affine ? hc.out(out_affine, n * 64) : -1;
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_from_uniform_batch_dev(ctx, n, hc.dev(in), hc.dev(o), aff < 0 ? nullptr : hc.dev(aff), ctx->stream));
+}
+
+static Rule ristretto_mul_rule(ncg_ctx* ctx, int flags) {
+  return {"ristretto_mul_batch", (flags & ~NCG_RISTRETTO_ONE_SCALAR) == 0 ? NCG_OK
+                                     : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ristretto_mul_batch: unknown flag bits 0x%x", flags)};
+}
+// decode (a rejected row becomes the identity), the ed25519 variable-base multiply, encode: three launches, only bytes cross
+int ncg_ristretto_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, int flags, void* out32_dev,
+                                uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ristretto_mul_rule(ctx, flags), n, enc_dev, scalars_dev, out32_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  const bool one = (flags & NCG_RISTRETTO_ONE_SCALAR) != 0;
+  const size_t pts_b = align256(n * 64), inf_b = align256(n);
+  if (int rc = ensure_rist_ws(ctx, 2 * pts_b + inf_b + (one ? n * 32 : 0), st)) return rc;
+  char* d_pts = (char*)ctx->rist_ws;
+  char* d_prod = d_pts + pts_b;
+  char* d_inf = d_prod + pts_b;
+  const void* d_sc = scalars_dev;
+  NCG_HIP(ctx, ncg::ristretto_decode_batch((const uint32_t*)enc_dev, (uint32_t*)d_pts, out_ok_dev, 1, (int)n, st));
+  if (one) {  // the multiply reads one scalar per item
+    NCG_HIP(ctx, ncg::ristretto_broadcast_scalar((const uint32_t*)scalars_dev, (uint32_t*)(d_inf + inf_b), (int)n, st));
+    d_sc = d_inf + inf_b;
+  }
+  if (int rc = ncg_mul_var_batch_dev(ctx, NCG_ED25519, n, d_pts, d_sc, d_prod, (uint8_t*)d_inf, st)) return rc;
+  NCG_HIP(ctx, ncg::ristretto_encode_batch((const uint32_t*)d_prod, (uint32_t*)out32_dev, (int)n, st));
+  return NCG_OK;
+}
+int ncg_ristretto_mul_batch(ncg_ctx* ctx, size_t n, const void* enc, const void* scalars, int flags, void* out32, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ristretto_mul_rule(ctx, flags), n, enc, scalars, out32, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc, n * 32), sc = hc.in(scalars, (flags & NCG_RISTRETTO_ONE_SCALAR) ? 32 : n * 32);
+  const int o = hc.out(out32, n * 32), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_mul_batch_dev(ctx, n, hc.dev(in), hc.dev(sc), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+// the fixed-base table walk, then the encoder on its projective rows: no inversion
+int ncg_ristretto_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, void* out32_dev, void* stream) {
+  NCG_BEGIN(ctx, no_rule("ristretto_mul_base_batch"), n, scalars_dev, out32_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_rist_ws(ctx, ncg::ristretto_proj_words((int)n) * 4, st)) return rc;
+  if (int rc = ensure_ed_base_table(ctx)) return rc;
+  NCG_HIP(ctx, ncg::ed25519_mul_base_proj(ctx->base_tab[NCG_ED25519], (const uint32_t*)scalars_dev, (uint32_t*)ctx->rist_ws, (int)n, st));
+  NCG_HIP(ctx, ncg::ristretto_encode_proj_batch((const uint32_t*)ctx->rist_ws, (uint32_t*)out32_dev, (int)n, st));
+  return NCG_OK;
+}
+int ncg_ristretto_mul_base_batch(ncg_ctx* ctx, size_t n, const void* scalars, void* out32) {
+  NCG_BEGIN(ctx, no_rule("ristretto_mul_base_batch"), n, scalars, out32);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, n * 32), o = hc.out(out32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_mul_base_batch_dev(ctx, n, hc.dev(sc), hc.dev(o), ctx->stream));
+}
+
+// An empty sum is the identity, whose encoding is 32 zero bytes: written, not refused, as ncg_msm writes (0, 1).
+static int ristretto_msm_identity(ncg_ctx* ctx, void* out32) {
+  if (!out32) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ristretto_msm: NULL output");
+  memset(out32, 0, 32);
+  return NCG_OK;
+}
+// decode on the device, the ed25519 MSM on the decoded points where they lie, the one resulting point encoded by the lane
+// function on the host (the MSM hands its result over in host memory)
+int ncg_ristretto_msm_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, void* out32, int64_t* out_bad_index,
+                          void* stream) {
+  if (out_bad_index) *out_bad_index = -1;
+  NCG_BEGIN_OR(ctx, no_rule("ristretto_msm"), n, ristretto_msm_identity(ctx, out32), enc_dev, scalars_dev, out32);
+  const hipStream_t st = stream_of(ctx, stream);
+  const size_t pts_b = align256(n * 64);
+  if (int rc = ensure_rist_ws(ctx, pts_b + n, st)) return rc;
+  char* d_pts = (char*)ctx->rist_ws;
+  uint8_t* d_ok = (uint8_t*)(d_pts + pts_b);
+  NCG_HIP(ctx, ncg::ristretto_decode_batch((const uint32_t*)enc_dev, (uint32_t*)d_pts, d_ok, 0, (int)n, st));
+  std::vector<uint8_t> ok(n);
+  NCG_HIP(ctx, hipMemcpyAsync(ok.data(), d_ok, n, hipMemcpyDeviceToHost, st));
+  NCG_HIP(ctx, hipStreamSynchronize(st));
+  for (size_t i = 0; i < n; i++)
+    if (!ok[i]) {  // the reference throws in fromBytes
+      if (out_bad_index) *out_bad_index = (int64_t)i;
+      return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ristretto_msm: invalid ristretto255 encoding at index %zu", i);
+    }
+  uint32_t aff[16], enc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint8_t inf = 0;
+  if (int rc = ncg_msm_dev(ctx, NCG_ED25519, n, d_pts, scalars_dev, aff, &inf, st)) return rc;
+  if (!inf) ncg::ristretto_encode_host(aff, enc, 1);
+  memcpy(out32, enc, 32);
+  return NCG_OK;
+}
+int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scalars, void* out32, int64_t* out_bad_index) {
+  if (out_bad_index) *out_bad_index = -1;
+  NCG_BEGIN_OR(ctx, no_rule("ristretto_msm"), n, ristretto_msm_identity(ctx, out32), enc, scalars, out32);
+  HostCall hc(ctx);
+  const int in = hc.in(enc, n * 32), sc = hc.in(scalars, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_msm_dev(ctx, n, hc.dev(in), hc.dev(sc), out32, out_bad_index, ctx->stream));
+}
+
 // words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
 // Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
 // bn254 Fe9 Montgomery raw limbs 9 / 9 / 9; the MSM groups (fields 10-14: secp256k1, ed25519, bls12-381 G1, lane-paired G2, bn254 G1):
-// one stored accumulator, 4 FW words, for each of a, b and out; the X25519 ladder pieces (field 16; 15 is unassigned) 36 / 9 / 36
-static const size_t k_field_wa[17] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36},
-                    k_field_wb[17] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36, 0, 9},
-                    k_field_wo[17] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36};
+// one stored accumulator, 4 FW words, for each of a, b and out; the X25519 ladder pieces (field 16; 15 is unassigned) and the
+// ristretto255 pieces (field 17) 36 / 9 / 36
+static const size_t k_field_wa[18] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36, 36},
+                    k_field_wb[18] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36, 0, 9, 9},
+                    k_field_wo[18] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36, 36};
 static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {
   int rc = NCG_OK;
-  if (field < 0 || field > 16 || field == 15) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (field < 0 || field > 17 || field == 15) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   else if (n > (1u << 24)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: batch too large (max 2^24)");
   return {"field_check", rc};
 }

@@ -62,6 +62,10 @@ struct ncg_ctx {
   // serves one call at a time
   void* poly_ws = nullptr;
   size_t poly_ws_bytes = 0;
+  // ristretto255 (ristretto.hip): what lies between a decode and an encode - the decoded points, their flags, the products,
+  // the (X, Y, Z) rows of the fixed-base walk, a broadcast scalar; one call at a time
+  void* rist_ws = nullptr;
+  size_t rist_ws_bytes = 0;
   // multi-GPU (comm.hip): RCCL communicator of this rank and the gather buffer of the sharded MSM
   void* comm = nullptr;  // ncclComm_t
   int comm_rank = 0, comm_size = 1;

@@ -200,6 +200,27 @@ void x25519_base_host(const uint32_t* scalars, uint32_t* out, uint8_t* out_ok, i
 void ed25519_to_montgomery_host(const uint32_t* pk, uint32_t* out, uint8_t* out_ok, int n);
 int x25519_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// ristretto255 (ristretto.hip): encodings and scalars are rows of 8 LE words, Edwards representatives ed25519 wire points (16
+// words), uniform input 16 words.  A rejected encoding gives out_ok = 0 and a zero row - or the identity (0, 1) with
+// identity_on_reject, for a caller that multiplies what comes out.  ristretto_encode_proj_batch takes the (X, Y, Z) rows of
+// ed25519_mul_base_proj (ristretto_proj_words(n) words).  out_affine of ristretto_from_uniform_batch may be null.
+hipError_t ristretto_decode_batch(const uint32_t* enc, uint32_t* out_affine, uint8_t* out_ok, int identity_on_reject, int n, hipStream_t st);
+hipError_t ristretto_encode_batch(const uint32_t* affine, uint32_t* out, int n, hipStream_t st);
+hipError_t ristretto_encode_proj_batch(const uint32_t* proj, uint32_t* out, int n, hipStream_t st);
+hipError_t ristretto_equals_batch(const uint32_t* a, const uint32_t* b, uint8_t* out_eq, int n, hipStream_t st);
+hipError_t ristretto_from_uniform_batch(const uint32_t* bytes64, uint32_t* out, uint32_t* out_affine, int n, hipStream_t st);
+hipError_t ristretto_broadcast_scalar(const uint32_t* scalar, uint32_t* out, int n, hipStream_t st);
+size_t ristretto_proj_words(int n);
+// the pieces on raw words (ncg_field_check field 17): a 36, b 9, out 36 words per row
+hipError_t ristretto_field_check(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st);
+void ristretto_decode_host(const uint32_t* enc, uint32_t* out_affine, uint8_t* out_ok, int identity_on_reject, int n);
+void ristretto_encode_host(const uint32_t* affine, uint32_t* out, int n);
+void ristretto_encode_proj_host(const uint32_t* proj_wire, uint32_t* out, int n);  // X Y Z as wire words, 24 per row
+void ristretto_equals_host(const uint32_t* a, const uint32_t* b, uint8_t* out_eq, int n);
+void ristretto_from_uniform_host(const uint32_t* bytes64, uint32_t* out, uint32_t* out_affine, int n);
+void ristretto_mul_host(const uint32_t* enc, const uint32_t* scalars, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
+int ristretto_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 // field-level self-check (ubench.hip): out[i] = op(a[i], b[i]) on the device field code
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
                            hipStream_t st);

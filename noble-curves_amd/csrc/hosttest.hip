@@ -19,6 +19,7 @@
 #include "fe9m_check.hpp"
 #include "group_check.hpp"
 #include "x25519.hip"
+#include "ristretto.hip"
 
 using namespace ncg;
 
@@ -432,6 +433,44 @@ int ht_ed25519_to_montgomery(const uint32_t* pk, uint32_t* out, uint8_t* ok, int
   return 0;
 }
 int ht_x25519_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return x25519_check_host(op, variant, a, b, out); }
+
+// ristretto255 on the CPU twins of ristretto.hip: encodings and scalars 8 LE words per row, Edwards representatives 16, uniform
+// bytes 16; flags as ncg_ristretto_mul_batch.  ht_ristretto_encode_proj: X Y Z as wire words (24 per row).  ht_ristretto_op: the
+// pieces of ncg_field_check field 17 (a 36, b 9, out 36 words), -1 for an unknown op.  ht_ristretto_consts: the four constants
+// of src/ed25519.ts:410-424 as the lane code holds them, 8 wire words each (sqrt(ad - 1), 1 / sqrt(a - d), 1 - d^2, (d - 1)^2).
+int ht_ristretto_decode(const uint32_t* enc, uint32_t* out_affine, uint8_t* ok, int n) {
+  ristretto_decode_host(enc, out_affine, ok, 0, n);
+  return 0;
+}
+int ht_ristretto_encode(const uint32_t* affine, uint32_t* out, int n) {
+  ristretto_encode_host(affine, out, n);
+  return 0;
+}
+int ht_ristretto_encode_proj(const uint32_t* proj_wire, uint32_t* out, int n) {
+  ristretto_encode_proj_host(proj_wire, out, n);
+  return 0;
+}
+int ht_ristretto_equals(const uint32_t* a, const uint32_t* b, uint8_t* eq, int n) {
+  ristretto_equals_host(a, b, eq, n);
+  return 0;
+}
+int ht_ristretto_from_uniform(const uint32_t* bytes64, uint32_t* out, uint32_t* out_affine, int n) {
+  ristretto_from_uniform_host(bytes64, out, out_affine, n);
+  return 0;
+}
+int ht_ristretto_mul(const uint32_t* enc, const uint32_t* scalars, int flags, uint32_t* out, uint8_t* ok, int n) {
+  if (flags & ~1) return -1;
+  ristretto_mul_host(enc, scalars, flags & 1, out, ok, n);
+  return 0;
+}
+int ht_ristretto_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) { return ristretto_check_host(op, a, b, out); }
+int ht_ristretto_consts(uint32_t* out32) {
+  fe9_to_wire(out32, RistrettoConsts::sqrt_ad_minus_one());
+  fe9_to_wire(out32 + 8, RistrettoConsts::invsqrt_a_minus_d());
+  fe9_to_wire(out32 + 16, RistrettoConsts::one_minus_d_sq());
+  fe9_to_wire(out32 + 24, RistrettoConsts::d_minus_one_sq());
+  return 0;
+}
 
 // Fp2 square root lane: in = c0 c1 wire (24 words); out = root wire; returns 1 if a root exists
 int ht_fp2_sqrt(const uint32_t* in, uint32_t* out) {

@@ -535,6 +535,7 @@ hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, 
   else if (field == 13) group_check_launch<CurveG2P>(op, d_a, d_b, d_out, n, st);
   else if (field == 14) group_check_launch<CurveBn254>(op, d_a, d_b, d_out, n, st);
   else if (field == 16) return x25519_field_check(op, variant, d_a, d_b, d_out, n, st);  // x25519.hip
+  else if (field == 17) return ristretto_field_check(op, d_a, d_b, d_out, n, st);         // ristretto.hip
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

@@ -118,7 +118,24 @@ def main():
     out += field("ParamsEdP", ep, 8, {"D": ed, "D2": 2 * ed % ep, "SQRT_M1": sqrtm1}, fold=(38, 0, 2))
     out += field("ParamsBlsP", bp, 12, {})
     out += field9("Fe9SecpPR", kp, {"BETA": beta})
-    out += field9("Fe9EdPR", ep, {"D": ed, "D2": 2 * ed % ep, "SQRT_M1": sqrtm1})
+    # ristretto255 (src/ed25519.ts:410-424), from d and sqrt(-1) with a = -1.  p = 5 (mod 8): a square root of a residue v is
+    # v^((p+3)/8), times sqrt(-1) when that squares to -v.  a d - 1 and a - d are the same number, -1 - d: the reference's
+    # sqrt(a d - 1) is its ODD root and 1 / sqrt(a - d) the inverse of its EVEN root (RFC 9496 section 4.1 lists the same values;
+    # the test of the fixture compares them with the decimals of src/ed25519.ts).
+    def ed_sqrt_even(v):
+        v %= ep
+        x = pow(v, (ep + 3) // 8, ep)
+        if x * x % ep != v:
+            x = x * sqrtm1 % ep
+        assert x * x % ep == v, "not a square"
+        return x if x % 2 == 0 else ep - x
+    assert sqrtm1 * sqrtm1 % ep == ep - 1
+    sqrt_ad_minus_one = ep - ed_sqrt_even(-ed - 1)
+    invsqrt_a_minus_d = pow(ed_sqrt_even(-1 - ed), -1, ep)
+    assert sqrt_ad_minus_one ** 2 % ep == (-ed - 1) % ep and invsqrt_a_minus_d ** 2 * (-1 - ed) % ep == 1
+    rist = {"SQRT_AD_MINUS_ONE": sqrt_ad_minus_one, "INVSQRT_A_MINUS_D": invsqrt_a_minus_d,
+            "ONE_MINUS_D_SQ": (1 - ed * ed) % ep, "D_MINUS_ONE_SQ": (ed - 1) ** 2 % ep}
+    out += field9("Fe9EdPR", ep, {"D": ed, "D2": 2 * ed % ep, "SQRT_M1": sqrtm1, **rist})
     g1_beta = 0x5F19672FDF76CE51BA69C6076A0F77EADDB3A93BE6F89688DE17D813620A00022E01FFFFFFFEFFFE
     # G2 psi endomorphism coefficients (src/abstract/tower.ts:240-241 with base 1/(u+1),
     # src/bls12-381.ts:283): PSI_X = base^((p-1)/3), PSI_Y = base^((p-1)/2) in Fp2 = Fp[u]/(u^2+1)
