@@ -639,8 +639,10 @@ NCG_DI void fe9_to_wire(uint32_t* __restrict__ p, const Fe9<PR, A>& a) {
 // Fermat inversion by addition chains (value of modular.ts:159-182 invert; 0 -> 0).
 //   secp256k1: p - 2 = 2^256 - 2^32 - 979: 255 squarings + 15 multiplications
 //   ed25519:   p - 2 = 2^255 - 21:         254 squarings + 11 multiplications
+// This is f_inv for the Montgomery kind (bn254) only.  For the two plain primes f_inv is the division-step inversion of
+// fe9_inv.hpp, and their chains stay as its cross-check (tests) and as the way out of its loop cap.
 template <class PR, int A>
-NCG_DI Fe9<PR, 1> f_inv(const Fe9<PR, A>& a_in) {
+NCG_DI Fe9<PR, 1> f_inv_fermat(const Fe9<PR, A>& a_in) {
   using F = Fe9<PR, 1>;
   const F x = fe9_norm(a_in);
   if constexpr (Fe9IsMont<PR>::value) {  // bn254: x^(p - 2) by 4-bit windows, 252 squarings + 63 + 14 multiplications
@@ -688,6 +690,19 @@ NCG_DI Fe9<PR, 1> f_inv(const Fe9<PR, A>& a_in) {
     F z2_250_0 = fe9_sqr_n(z2_200_0, 50) * z2_50_0;
     return fe9_sqr_n(z2_250_0, 5) * z11;
   }
+}
+
+}  // namespace ncg
+#include "fe9_inv.hpp"
+namespace ncg {
+
+// 1 / a, 0 -> 0 (value of modular.ts:159-182 invert).  secp256k1, ed25519: division steps (fe9_inv.hpp), about 520 cheap steps on
+// the low limb in 18 batches of 30, each batch followed by one 2 x 2 matrix applied to four 9-limb numbers, instead of
+// 270 dependent field products; the result is the canonical residue.  bn254 (Montgomery form): the Fermat chain above.
+template <class PR, int A>
+NCG_DI Fe9<PR, 1> f_inv(const Fe9<PR, A>& a_in) {
+  if constexpr (Fe9IsMont<PR>::value) return f_inv_fermat(a_in);
+  else return fe9_inv_divsteps(a_in);
 }
 
 // storage types used by the curve templates: coordinates are kept with limbs below 2*U

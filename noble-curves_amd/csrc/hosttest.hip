@@ -304,6 +304,20 @@ static int fr29_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* 
   return fr29_overflows();
 }
 
+// inversion of n operands of 9 raw limbs at the bound A (1, 2 or 7): which = 0 f_inv (division steps, fe9_inv.hpp), 1 the kept Fermat
+// chain; out: 8 canonical wire words per operand and, in raw[9 n] when given, the limbs f_inv returned
+template <class PR, int A>
+static void ht_fe9_inv_batch_t(int which, const uint32_t* a, uint32_t* out, uint32_t* raw, int n) {
+  for (int k = 0; k < n; k++) {
+    Fe9<PR, A> x;
+    for (int i = 0; i < 9; i++) x.v[i] = a[(size_t)k * 9 + i];
+    const Fe9<PR, 1> z = which ? f_inv_fermat(x) : f_inv(x);
+    fe9_to_wire(out + (size_t)k * 8, z);
+    if (raw)
+      for (int i = 0; i < 9; i++) raw[(size_t)k * 9 + i] = z.v[i];
+  }
+}
+
 extern "C" {
 
 // field: 0 secp256k1 p, 1 ed25519 p (radix-2^29 lazy form, fe9.hpp); a, b: 9 raw limbs; r: 8 wire words
@@ -311,6 +325,15 @@ int ht_fe9_op(int field, int op, int variant, const uint32_t* a, const uint32_t*
   if (field == 0) return ht_fe9_t<Fe9SecpPR>(op, variant, a, b, r);
   if (field == 1) return ht_fe9_t<Fe9EdPR>(op, variant, a, b, r);
   return -1;
+}
+
+int ht_fe9_inv_batch(int field, int A, int which, const uint32_t* a, uint32_t* out, uint32_t* raw, int n) {
+  if (field < 0 || field > 1 || (A != 1 && A != 2 && A != 7)) return -1;
+#define CALL(PR) (A == 1 ? ht_fe9_inv_batch_t<PR, 1>(which, a, out, raw, n) : A == 2 ? ht_fe9_inv_batch_t<PR, 2>(which, a, out, raw, n) : ht_fe9_inv_batch_t<PR, 7>(which, a, out, raw, n))
+  if (field == 0) CALL(Fe9SecpPR);
+  else CALL(Fe9EdPR);
+#undef CALL
+  return 0;
 }
 
 int ht_mul_var(int curve, const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, int n) {

@@ -91,6 +91,16 @@ def field9(name, p, extra=None):
     s += "  static constexpr uint32_t PINV = 0x%08xu;  // p^-1 mod 2^29\n" % pow(p, -1, 1 << 29)
     s += "  static constexpr int JMAX = %d;  // a value with limbs < B*U is below JMAX*B*p\n" % (
         (U * sum(1 << (29 * i) for i in range(9)) + p - 1) // p)
+    # the division-step inversion (fe9_inv.hpp): p in balanced signed limbs of 30 bits (all but three are zero for a
+    # prime 2^k - c with a small c) and p^-1 mod 2^30
+    p30, cy = [], 0
+    for i in range(9):
+        l = ((p >> (30 * i)) & ((1 << 30) - 1)) + cy
+        cy = 1 if (l >= (1 << 29) and i < 8) else 0
+        p30.append(l - (cy << 30))
+    assert sum(l << (30 * i) for i, l in enumerate(p30)) == p and all(abs(l) < (1 << 17) for l in p30)
+    s += "  static constexpr int32_t P30[9] = {%s};  // p in signed limbs of 30 bits\n" % ", ".join("%d" % l for l in p30)
+    s += "  static constexpr uint32_t PINV30 = 0x%08xu;  // p^-1 mod 2^30\n" % pow(p, -1, 1 << 30)
     s += "  static constexpr uint32_t BIAS[8][9] = {\n"
     for k in range(8):
         base = sum((k * U) << (29 * i) for i in range(9))
