@@ -265,6 +265,49 @@ NCG_DI Jac<Fe9<PR, B>> jac_madd_neg(const Jac<Fe9<PR, B>>& p, const Fe9<PR, BX>&
   return {X3, W, Z3};
 }
 
+// jac_madd_neg for the fused ladder (mulvar.hpp), without its exceptional cases: no test of Q = O or P = O, no doubling, no
+// select - the same ten reductions and one zero test.  H = 0 (P = +-Q) is ORed into `degenerate` and the result is then
+// garbage within the limb bounds; the caller recomputes a flagged lane with the complete ladder.  What the caller guarantees:
+//   * Q != O.  Q is an entry j P (j odd, below 2^W) of the table of a lane that is not flagged: P != O has prime order, so
+//     j P != O, and no finite point of y^2 = x^3 + 7 is the literal (0, 0).
+//   * P = O only in a lane that is flagged already.  The ladder starts from a finite point (aff_add_neg_nx); a doubling of a
+//     finite point is finite (no point of order 2), and an addition gives O only through H = 0, which sets the flag for good.
+// qy feeds a product only, so it may come from f_cneg_lin.
+template <class PR, int B, int BX, int BY>
+NCG_DI Jac<Fe9<PR, B>> jac_madd_neg_nx(const Jac<Fe9<PR, B>>& p, const Fe9<PR, BX>& qx, const Fe9<PR, BY>& qy, bool& degenerate) {
+  auto Z1Z1 = f_sqr(p.Z);
+  auto Z1Z1Z1 = p.Z * Z1Z1;
+  auto H = f_mul_add(qx, Z1Z1, f_neg_lin(p.X));
+  auto R = f_mul_add(qy, Z1Z1Z1, f_neg_lin(p.Y));
+  degenerate |= f_eqz(H);
+  auto HH = f_sqr(H);
+  auto HHH = H * HH;
+  auto V = p.X * HH;
+  auto X3 = f_sqr_add(R, f_neg_lin(HHH, V));
+  auto W = f_mul_mul(R, X3 - V, p.Y, HHH);
+  auto Z3 = p.Z * H;
+  return {X3, W, Z3};
+}
+
+// -(P1 + P2) for two AFFINE points P1 = (x1, y1), P2 = (b x2, y2) (b: the endomorphism's constant, psi(x, y) = (b x, y)): the
+// first window of the GLV ladder, where both operands are table entries.  jac_madd_neg_nx with Z1 = 1, so Z^2, Z^3 and Z H
+// cost nothing and b x2 rides in the reduction of H: 4M + 2S in six reductions, Z3 = H = b x2 - x1.
+//   R = y2 - y1,  X3 = R^2 - H^3 - 2V (V = x1 H^2),  -Y3 = R (X3 - V) + y1 H^3
+// Bounds: R (X3 - V) + y1 H^3 is 1*3 + BY*1 <= 7.  H = 0 (P1 = +-P2) sets `degenerate` as above; neither operand is O.
+template <class PR, int B, int BY>
+NCG_DI Jac<Fe9<PR, B>> aff_add_neg_nx(const Fe9<PR, B>& x1, const Fe9<PR, BY>& y1, const Fe9<PR, B>& x2, const Fe9<PR, 1>& b,
+                                      const Fe9<PR, BY>& y2, bool& degenerate) {
+  auto H = f_mul_add(x2, b, f_neg_lin(x1));
+  auto R = fe9_norm(y2 - y1);
+  degenerate |= f_eqz(H);
+  auto HH = f_sqr(H);
+  auto HHH = H * HH;
+  auto V = x1 * HH;
+  auto X3 = f_sqr_add(R, f_neg_lin(HHH, V));
+  auto W = f_mul_mul(R, X3 - V, y1, HHH);
+  return {X3, W, H};
+}
+
 // ----------------------------------------------------------------- XYZZ
 template <class F>
 NCG_DI Xyzz<F> xyzz_from_affine(const Affine<F>& p) {

@@ -463,6 +463,14 @@ NCG_DI Fe9<PR, 2 * S2 + 1> f_neg_lin2(const Fe9<PR, S2>& s2) {
   for (int i = 0; i < 9; i++) r.v[i] = PR::BIAS[2 * S2][i] - (s2.v[i] << 1);
   return r;
 }
+// c ? -a : a without f_neg's literal-zero rule: for an operand of a product, never for a stored coordinate
+template <class PR, int A>
+NCG_DI Fe9<PR, A + 1> f_cneg_lin(const Fe9<PR, A>& a, bool c) {
+  Fe9<PR, A + 1> r;
+#pragma unroll
+  for (int i = 0; i < 9; i++) r.v[i] = c ? PR::BIAS[A][i] - a.v[i] : a.v[i];
+  return r;
+}
 // a / 2 (mod p): add p when a is odd - the parity of the value is that of limb 0 - then shift the limbs right by one, the low
 // bit of limb i + 1 going to bit 28 of limb i.  Limbs below U + 2^29 before the shift, so below U / 2 + 2^28 + 2^28 < 2U after.
 template <class PR>

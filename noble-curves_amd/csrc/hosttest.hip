@@ -391,6 +391,33 @@ int ht_jac_neg(int op, const uint32_t* p, const uint32_t* qx, const uint32_t* qy
   return 0;
 }
 
+// the exception-free additions of the fused ladder (ec_sw.hpp) on the same raw limbs; out = X, Y, Z and the `degenerate` verdict
+// (28 words).  op 0: jac_madd_neg_nx(P, qx, qy);  op 1: aff_add_neg_nx((P.X, P.Y), (beta qx, qy)) - P.Z is not read
+int ht_jac_neg_nx(int op, const uint32_t* p, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
+  Jac<FeSecp> P;
+  Fe9<Fe9SecpPR, 2> x;
+  Fe9<Fe9SecpPR, 3> y;
+  for (int i = 0; i < 9; i++) {
+    P.X.v[i] = p[i];
+    P.Y.v[i] = p[9 + i];
+    P.Z.v[i] = p[18 + i];
+    x.v[i] = qx[i];
+    y.v[i] = qy[i];
+  }
+  Jac<FeSecp> R;
+  bool degenerate = false;
+  if (op == 0) R = jac_madd_neg_nx(P, x, y, degenerate);
+  else if (op == 1) R = aff_add_neg_nx(P.X, Fe9<Fe9SecpPR, 3>(P.Y), x, CurveSecpI::beta(), y, degenerate);
+  else return -1;
+  for (int i = 0; i < 9; i++) {
+    out[i] = R.X.v[i];
+    out[9 + i] = R.Y.v[i];
+    out[18 + i] = R.Z.v[i];
+  }
+  out[27] = degenerate ? 1u : 0u;
+  return 0;
+}
+
 // secp_glv_split followed by secp_glv_make_odd; layout of ht_glv_split
 int ht_glv_split_odd(const uint32_t* k, uint32_t* out) {
   uint32_t kk[8];

@@ -90,7 +90,7 @@ NCG_DI Jac<typename C::F> mul_var_slow(const uint32_t* __restrict__ pt_wire, con
 
 // Curve traits of the ladder (absent = false).  ODD_HALVES: the GLV halves come out odd (secp_glv_make_odd), so there is no
 // was_even fix-up at the end.  K1_ODD: k1 odd and both halves below 2^128 (secp_glv_make_k1_odd): a 128-bit window register and
-// one was_even fix-up, for k2.  FUSED_LADDER: Fe9 ladder with the negated fused formulas jac_dbl_neg / jac_madd_neg.
+// one was_even fix-up, for k2.  FUSED_LADDER: Fe9 ladder with the negated fused formulas jac_dbl_neg / jac_madd_neg_nx; it needs K1_ODD.
 template <class C, class = void> struct OddGlvHalves { static constexpr bool value = false; };
 template <class C> struct OddGlvHalves<C, std::void_t<decltype(C::ODD_HALVES)>> { static constexpr bool value = C::GLV && C::ODD_HALVES; };
 template <class C, class = void> struct OddK1Half { static constexpr bool value = false; };
@@ -202,6 +202,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   // of +-Q then adds the point with y negated once more when sg is set.  With W doublings and two additions per window the
   // sign is static per window position; it is fixed once after the loop.
   constexpr bool FUSED = FusedLadder<C>::value;
+  static_assert(!FUSED || (C::GLV && OddK1Half<C>::value), "the fused ladder is the GLV ladder with k1 odd");
   bool sg = false;
   auto dbl = [&](const Jac<F>& r) -> Jac<F> {
     if constexpr (FUSED) {
@@ -211,23 +212,37 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
       return jac_dbl(r);
     }
   };
+  // FUSED: the additions have no exceptional cases (ec_sw.hpp jac_madd_neg_nx).  A lane that meets one - R = +-Q, which random
+  // scalars never do (tests/ladder32.py) - is flagged `degenerate`, goes on with garbage and is redone by mul_var_slow below.
   auto madd = [&](const Jac<F>& r, const auto& qx, const F& qy, bool ng) -> Jac<F> {
     if constexpr (FUSED) {
       const bool s = sg;
       sg = !sg;
-      return jac_madd_neg(r, qx, f_cneg(qy, ng != s));
+      return jac_madd_neg_nx(r, qx, f_cneg_lin(qy, ng != s), degenerate);
     } else {
       return jac_madd_q(r, qx, f_cneg(qy, ng));
     }
   };
   Jac<F> R = Jac<F>::inf();
-  for (int i = 0; i < M; i++) {
-    if (i > 0) {
+  if constexpr (FUSED) {
+    // window 0 is ONE addition of two table entries, +-T[d1] + psi(+-T[d2]), both at Z = 1 (ec_sw.hpp aff_add_neg_nx: 4M + 2S
+    // against the 8M + 3S of a mixed addition).  It returns the negated sum, so it is given the negated operands and `sg`
+    // stays clear.  Every later window then starts with its doublings.
+    const int d1 = w1.pop(), d2 = w2.pop();
+    const int e1 = ((d1 < 0 ? -d1 : d1) - 1) >> 1, e2 = ((d2 < 0 ? -d2 : d2) - 1) >> 1;
+    const F x1 = FieldIO<F>::load_strided(tab + (e1 * 2 * TW) * stride, stride);
+    const F y1 = FieldIO<F>::load_strided(tab + (e1 * 2 * TW + TW) * stride, stride);
+    const F x2 = FieldIO<F>::load_strided(tab + (e2 * 2 * TW) * stride, stride);
+    const F y2 = FieldIO<F>::load_strided(tab + (e2 * 2 * TW + TW) * stride, stride);
+    R = aff_add_neg_nx(x1, f_cneg_lin(y1, (d1 < 0) == neg1), x2, beta, f_cneg_lin(y2, (d2 < 0) == neg2), degenerate);
+  }
+  for (int i = FUSED ? 1 : 0; i < M; i++) {
+    if (FUSED || i > 0) {
 #pragma unroll(NCG_MUL_INLINE ? 1 : W)
       for (int d = 0; d < W; d++) R = dbl(R);
     }
     // one mixed addition per stream
-    if constexpr (NCG_MUL_INLINE && C::GLV) {
+    if constexpr (NCG_MUL_INLINE && C::GLV && !FUSED) {
       // field multiply inlined: the two additions of the GLV pair are ONE loop body run twice (the window body - 4
       // doublings through one rolled body + this - then fits the 64 KB instruction cache; as straight-line code it
       // was 69 KB and re-fetched every window)
@@ -242,6 +257,9 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
         R = madd(R, qx, qy, (d < 0) != ng);
       }
     } else {
+      // (FUSED with the field multiply inlined comes here too: without an inlined doubling in its additions the pair fits as
+      // straight-line code - a window body of 35 KB - so R is not moved back into place between the two and the beta product is
+      // not behind a branch)
       {
         int d1 = w1.pop();
         int e = ((d1 < 0 ? -d1 : d1) - 1) >> 1;
@@ -272,12 +290,15 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   }
   if constexpr (FUSED) {
     if (sg) R.Y = f_neg(R.Y);   // the one fix-up of the negated forms (f_neg keeps a literal zero literal)
+    // a lane whose result is known beforehand (P = O, where the table build sets the flag, or k = 0, whose last addition is
+    // R = -Q) must not send its wave through the complete ladder
+    degenerate = degenerate && !trivial_zero;
   }
   // back from the isomorphic curve, then to affine (weierstrass.ts:951-969 toAffine)
   const bool ladder_inf = R.is_inf();  // tested before the product: not every field keeps 0 * Zg literal
   R.Z = R.Z * Zg;
   if (ladder_inf) R = Jac<F>::inf();
-  if (degenerate) R = mul_var_slow<C>(pt_wire, k_wire);  // small-order P: complete ladder instead
+  if (degenerate) R = mul_var_slow<C>(pt_wire, k_wire);  // small-order P, or an exceptional addition in the fused ladder: complete ladder instead
   bool inf = trivial_zero || R.is_inf();
   if constexpr (JAC_OUT) {
     if (inf) R = Jac<F>::inf();
