@@ -589,10 +589,13 @@ int ncg_schnorr_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig64_
  * returns the kernel time in milliseconds. */
 int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float* out_ms);
 /* Field-level self-check: out[i] = op(a[i], b[i]) computed by the device field code, one lane per element
- * (host buffers).  field 0 / 1 = secp256k1 / ed25519 base field in the radix-2^29 lazy form (fe9.hpp): a, b
+ * (host buffers; csrc/selfcheck.hpp lists the fields and the words per row of a, b and out, csrc/selfcheck.hip holds the
+ * kernels).  field 0 / 1 = secp256k1 / ed25519 base field in the radix-2^29 lazy form (fe9.hpp): a, b
  * are 9 RAW 32-bit limbs per element, `variant` = 10 A + B names the operand bound types; out = 8 canonical
- * LE words.  field 2 = bls12-381 Fp: 12-word canonical operands and results.  op: 0 mul, 1 sqr, 2 add, 3 sub,
- * 4 neg, 5 inv, 6 normalise, 7 is-zero-mod-p, 9 largest output limb of the product.
+ * LE words (variants 11 12 17 71 23 32 22 15 33 77 46; any other leaves out zero).  op: 0 mul, 1 sqr (of the normalised
+ * operand when A > 2), 2 add, 3 sub, 4 neg, 5 inv, 6 normalise, 10 double; 7 out[0] = is-zero-mod-p, 8 out[0] = the largest
+ * limb of the normalised a, 9 out[0] = the largest output limb of the product.  An op the bounds do not admit leaves out
+ * zero.  field 2 = bls12-381 Fp: 12-word canonical operands and results, ops 0-5 of the same list.
  * field 3 = bls12-381 Fp on RAW radix-2^29 limbs (fe29.hpp, Montgomery R = 2^406): a = [a, c], b = [b, d], 14 limbs
  * each, values up to the top of the lazy bounds (a, c < 4096 p; b, d < 4096 p for op 0, 2048 p for op 6);
  * field 4 = the lane-paired Fp2 form: every element c0 then c1 (28 limbs), a, c < 4096 p (2048 p for op 1), b, d <
@@ -605,7 +608,8 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * field 7 = the secp256k1 ladder pieces, RAW limbs in and out: a = 27 words, b = 18 words, out = 27 words.  op 0
  * jac_dbl_neg(P), op 1 jac_madd_neg(P, qx, qy) (ec_sw.hpp) with P = a (X, Y, Z at bound 2), qx = b[0..9) at bound 2,
  * qy = b[9..18) at bound 3: out = X, Y, Z; op 2 secp_glv_split + secp_glv_make_odd (scalar.hpp) of the scalar in
- * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg.
+ * a[0..8): out[0..12) = k1[5] k2[5] k1neg k2neg; op 3 secp_glv_split + secp_glv_make_k1_odd (the split of the fused ladder),
+ * the same layout.  Any other op leaves out zero.
  * field 8 = fr29.hpp, the bls12-381 Fr form of the NTT butterflies, RAW limbs in and out: a, b, out = 9 words each.
  * ops 0 mont(a, b), 1 a + b, 2 a + 3 r - b, 3 weak(a), 4 reduce256(a), 5 cond_sub(a), 6 from_words(a[0..8)),
  * 7 to_words(a) (8 words, then 0), 8 one fold (fr29_fold255).  `variant` 0 = bls12-381 Fr, 1 = bn254 Fr (the same

@@ -21,6 +21,11 @@ POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
 X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
 RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
+# ncg_field_check: {field: words per row of (a, b, out)}, the table of csrc/selfcheck.hpp (15 is unassigned)
+FIELD_CHECK_WORDS = {
+    0: (9, 9, 8), 1: (9, 9, 8), 2: (12, 12, 12), 3: (28, 28, 12), 4: (56, 56, 24), 5: (18, 18, 9), 6: (18, 18, 9), 7: (27, 18, 27),
+    8: (9, 9, 9), 9: (9, 9, 9), 10: (36, 36, 36), 11: (36, 36, 36), 12: (56, 56, 56), 13: (112, 112, 112), 14: (36, 36, 36),
+    16: (36, 9, 36), 17: (36, 9, 36)}
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -957,12 +962,12 @@ class Engine:
         a = np.ascontiguousarray(a_words, dtype=np.uint32)
         b = np.ascontiguousarray(b_words, dtype=np.uint32)
         n = a.shape[0]
-        acc = {10: 36, 11: 36, 12: 56, 13: 112, 14: 36}
-        wa, wb = {2: (12, 12), 3: (28, 28), 4: (56, 56), 5: (18, 18), 6: (18, 18), 7: (27, 18), 16: (36, 9), 17: (36, 9),
-                  **{f: (w, w) for f, w in acc.items()}}.get(field, (9, 9))
+        if field not in FIELD_CHECK_WORDS:
+            raise ValueError("field_check: unknown field %d" % field)
+        wa, wb, wo = FIELD_CHECK_WORDS[field]
         if a.shape != (n, wa) or b.shape != (n, wb):   # the library reads n * wa and n * wb words
             raise ValueError("field_check: field %d takes a [n, %d] and b [n, %d]" % (field, wa, wb))
-        out = np.zeros((n, {2: 12, 3: 12, 4: 24, 5: 9, 6: 9, 7: 27, 8: 9, 9: 9, 16: 36, 17: 36, **acc}.get(field, 8)), dtype=np.uint32)
+        out = np.zeros((n, wo), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_field_check(self.h, field, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out

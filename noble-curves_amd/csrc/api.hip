@@ -14,6 +14,7 @@
 #include "host_api.hpp"
 #include "consts_gen.hpp"
 #include "msm.hpp"
+#include "selfcheck.hpp"
 
 namespace {
 std::mutex g_err_mu;
@@ -1906,25 +1907,18 @@ int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scala
   return hc.finish(ncg_ristretto_msm_dev(ctx, n, hc.dev(in), hc.dev(sc), out32, out_bad_index, ctx->stream));
 }
 
-// words per item (a / b / out): fe9 9 / 9 / 8; Fe29 from wire 12 / 12 / 12; Fe29 raw limbs [a, c] 28 / 28 / 12; lane-paired
-// Fp2 raw [a, c] 56 / 56 / 24; fused Fe9 [a, c] 18 / 18 / 9; secp256k1 ladder pieces 27 / 18 / 27; fr29 raw limbs 9 / 9 / 9;
-// bn254 Fe9 Montgomery raw limbs 9 / 9 / 9; the MSM groups (fields 10-14: secp256k1, ed25519, bls12-381 G1, lane-paired G2, bn254 G1):
-// one stored accumulator, 4 FW words, for each of a, b and out; the X25519 ladder pieces (field 16; 15 is unassigned) and the
-// ristretto255 pieces (field 17) 36 / 9 / 36
-static const size_t k_field_wa[18] = {9, 9, 12, 28, 56, 18, 18, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36, 36},
-                    k_field_wb[18] = {9, 9, 12, 28, 56, 18, 18, 18, 9, 9, 36, 36, 56, 112, 36, 0, 9, 9},
-                    k_field_wo[18] = {8, 8, 12, 12, 24, 9, 9, 27, 9, 9, 36, 36, 56, 112, 36, 0, 36, 36};
 static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {
   int rc = NCG_OK;
-  if (field < 0 || field > 17 || field == 15) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
+  if (!ncg::selfcheck_field(field)) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: field_check: unknown field %d", field);
   else if (n > (1u << 24)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: field_check: batch too large (max 2^24)");
   return {"field_check", rc};
 }
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out) {
   NCG_BEGIN(ctx, field_rule(ctx, field, n), n, a, b, out);
   HostCall hc(ctx);
-  const int da = hc.in(a, n * k_field_wa[field] * 4), db = hc.in(b, n * k_field_wb[field] * 4);
-  const int o = hc.out(out, n * k_field_wo[field] * 4, true);
+  const ncg::SelfCheckField& f = *ncg::selfcheck_field(field);  // selfcheck.hpp: words per row
+  const int da = hc.in(a, n * f.wa * 4), db = hc.in(b, n * f.wb * 4);
+  const int o = hc.out(out, n * f.wo * 4, true);
   if (int rc = hc.stage()) return rc;
   NCG_HIP(ctx, ncg::field_check_run(field, op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n,
                                     ctx->stream));

@@ -1,4 +1,4 @@
-// Self-check of the bn254 Montgomery form (fe9m.hpp) on RAW limbs, shared by the device (ncg_field_check field 9, ubench.hip)
+// Self-check of the bn254 Montgomery form (fe9m.hpp) on RAW limbs, shared by the device (ncg_field_check field 9, selfcheck.hip)
 // and the host twin (hosttest.hip).  a, b: 9 raw limbs at the bounds of `variant` (decimal digits A B); r: 9 raw limbs.
 //   op 0 a*b   1 a^2   2 a + b   3 a - b   4 -a   5 1/a   6 weak normalisation   7 to wire (plain canonical, 8 words)
 //   op 8 from wire (a = 8 LE words of a canonical residue)

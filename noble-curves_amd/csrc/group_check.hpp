@@ -1,4 +1,4 @@
-// Self-check of the group law the MSM runs on its buckets, on STORED words (ncg_field_check fields 10-14, ubench.hip) and of
+// Self-check of the group law the MSM runs on its buckets, on STORED words (ncg_field_check fields 10-14, selfcheck.hip) and of
 // the bls12-381 zero test under its branches (op 7 of fields 3 / 4); shared with the host twin (hosttest.hip ht_group_op /
 // ht_fe29_eqz).  Nothing is converted on the way in or out: a, b and out are MsmGroup<C>::ACC_WORDS raw words in the layout
 // acc_load / acc_store read and write (Montgomery form included); for ops 0 / 1 b holds AFF_WORDS words in aff_load's layout.

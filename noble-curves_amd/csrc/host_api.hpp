@@ -221,9 +221,11 @@ void ristretto_from_uniform_host(const uint32_t* bytes64, uint32_t* out, uint32_
 void ristretto_mul_host(const uint32_t* enc, const uint32_t* scalars, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
 int ristretto_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
-// field-level self-check (ubench.hip): out[i] = op(a[i], b[i]) on the device field code
+// field-level self-check (selfcheck.hip; the fields and their row widths: selfcheck.hpp): out[i] = op(a[i], b[i]) on the device
+// field code
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
                            hipStream_t st);
+// instruction-rate and field-multiply micro-benchmarks (ubench.hip)
 hipError_t ubench_run(int kind, int blocks, int threads, int iters, uint32_t* d_out, const uint32_t* d_in,
                       hipStream_t st, float* ms);
 

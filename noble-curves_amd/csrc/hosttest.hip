@@ -16,8 +16,12 @@
 #include "msm_shard.hpp"
 #include "msm_endo.hip"  // msm_make_plan_endo
 #include "msm_schedule.hpp"
+#include "fe9_check.hpp"
 #include "fe9m_check.hpp"
+#include "fr29_check.hpp"
 #include "group_check.hpp"
+#include "secp_ladder_check.hpp"
+#include "selfcheck.hpp"
 #include "x25519.hip"
 #include "ristretto.hip"
 
@@ -46,62 +50,6 @@ static void ht_field_t(int op, const uint32_t* a, const uint32_t* b, uint32_t* r
   }
   fp_store<PR>(r, fp_from_mont<PR>(z));
 }
-
-// Fe9 ops on RAW limb arrays (so tests can feed the loosest limbs each bound type admits).
-// variant picks the operand bounds (A, B); the result is written as the canonical wire value.
-template <class PR, int A, int B>
-static void ht_fe9_ab(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  Fe9<PR, A> x;
-  Fe9<PR, B> y;
-  for (int i = 0; i < 9; i++) {
-    x.v[i] = a[i];
-    y.v[i] = b[i];
-  }
-  switch (op) {
-    case 0: fe9_to_wire(r, x * y); break;
-    case 1: if constexpr (A <= 2) fe9_to_wire(r, f_sqr(x)); else fe9_to_wire(r, f_sqr(fe9_norm(x))); break;
-    case 2: if constexpr (A + B <= 7) fe9_to_wire(r, x + y); break;
-    case 3: if constexpr (A + B + 1 <= 7) fe9_to_wire(r, x - y); break;
-    case 4: if constexpr (A + 1 <= 7) fe9_to_wire(r, f_neg(x)); break;
-    case 5: fe9_to_wire(r, f_inv(x)); break;
-    case 6: fe9_to_wire(r, fe9_norm(x)); break;
-    case 7: r[0] = f_eqz(x) ? 1u : 0u; break;
-    case 8: {  // norm must leave limbs below U
-      auto n = fe9_norm(x);
-      uint32_t mx = 0;
-      for (int i = 0; i < 9; i++) mx = n.v[i] > mx ? n.v[i] : mx;
-      r[0] = mx;
-      break;
-    }
-    case 9: {  // product limbs (raw), to check the output bound
-      auto n = x * y;
-      for (int i = 0; i < 8; i++) r[i] = 0;
-      uint32_t mx = 0;
-      for (int i = 0; i < 9; i++) mx = n.v[i] > mx ? n.v[i] : mx;
-      r[0] = mx;
-      break;
-    }
-    case 10: if constexpr (2 * A <= 7) fe9_to_wire(r, f_dbl(x)); break;
-  }
-}
-template <class PR>
-static int ht_fe9_t(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  switch (variant) {
-    case 11: ht_fe9_ab<PR, 1, 1>(op, a, b, r); return 0;
-    case 12: ht_fe9_ab<PR, 1, 2>(op, a, b, r); return 0;
-    case 17: ht_fe9_ab<PR, 1, 7>(op, a, b, r); return 0;
-    case 71: ht_fe9_ab<PR, 7, 1>(op, a, b, r); return 0;
-    case 23: ht_fe9_ab<PR, 2, 3>(op, a, b, r); return 0;
-    case 32: ht_fe9_ab<PR, 3, 2>(op, a, b, r); return 0;
-    case 22: ht_fe9_ab<PR, 2, 2>(op, a, b, r); return 0;
-    case 15: ht_fe9_ab<PR, 1, 5>(op, a, b, r); return 0;
-    case 33: ht_fe9_ab<PR, 3, 3>(op, a, b, r); return 0;
-    case 77: ht_fe9_ab<PR, 7, 7>(op, a, b, r); return 0;
-    case 46: ht_fe9_ab<PR, 4, 6>(op, a, b, r); return 0;
-  }
-  return -1;
-}
-
 
 // ---- sharded MSM twin (tests/test_distributed_cpu.py): the per-shard grouped window sums computed naively with the
 // group-law templates, then the REAL slot format, header check, partial-sum order and finish of comm.hip / msm_finish.hpp
@@ -215,95 +163,6 @@ static int ht_shard_combine_t(int curve, int n_max, int nparts, const uint8_t* s
     default: return -1;                               \
   }
 
-// fused Fe9 expressions at fixed operand bounds (the loosest each admits)
-template <class PR, int A, int B, int C, int D>
-static void ht_fe9_fused_ab(int op, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* r) {
-  Fe9<PR, A> x;
-  Fe9<PR, B> y;
-  Fe9<PR, C> z;
-  Fe9<PR, D> w;
-  for (int i = 0; i < 9; i++) {
-    x.v[i] = a[i];
-    y.v[i] = b[i];
-    z.v[i] = c[i];
-    w.v[i] = d[i];
-  }
-  Fe9<PR, 1> o;
-  if constexpr (A * B + C * D <= 7) {
-    if (op == 0) o = f_mul_mul(x, y, z, w);
-  }
-  if constexpr (C <= 2 && A * B + C * C <= 7) {
-    if (op == 1) o = f_mul_sqr(x, y, z);
-  }
-  if constexpr (A * B <= 7) {
-    if (op == 2) o = f_mul_add(x, y, z);
-  }
-  if constexpr (A <= 2) {
-    if (op == 3) o = f_sqr_add(x, z);
-  }
-  if constexpr (A == 1) {
-    if (op == 4) {
-      const Fe9<PR, 2> h = f_half(x);
-      for (int i = 0; i < 9; i++) r[i] = h.v[i];
-      return;
-    }
-  }
-  for (int i = 0; i < 9; i++) r[i] = o.v[i];
-}
-template <class PR>
-static int ht_fe9_fused_t(int op, int variant, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d, uint32_t* r) {
-  switch (variant) {  // decimal digits A B C D
-    case 1111: ht_fe9_fused_ab<PR, 1, 1, 1, 1>(op, a, b, c, d, r); return 0;
-    case 1322: ht_fe9_fused_ab<PR, 1, 3, 2, 2>(op, a, b, c, d, r); return 0;
-    case 3211: ht_fe9_fused_ab<PR, 3, 2, 1, 1>(op, a, b, c, d, r); return 0;
-    case 2311: ht_fe9_fused_ab<PR, 2, 3, 1, 1>(op, a, b, c, d, r); return 0;
-    case 1123: ht_fe9_fused_ab<PR, 1, 1, 2, 3>(op, a, b, c, d, r); return 0;
-    case 3121: ht_fe9_fused_ab<PR, 3, 1, 2, 1>(op, a, b, c, d, r); return 0;
-    case 1327: ht_fe9_fused_ab<PR, 1, 3, 2, 7>(op, a, b, c, d, r); return 0;
-    case 7171: ht_fe9_fused_ab<PR, 7, 1, 7, 1>(op, a, b, c, d, r); return 0;
-    case 1771: ht_fe9_fused_ab<PR, 1, 7, 7, 1>(op, a, b, c, d, r); return 0;
-    case 2171: ht_fe9_fused_ab<PR, 2, 1, 7, 1>(op, a, b, c, d, r); return 0;
-    default: return -1;
-  }
-}
-
-// fr29.hpp on RAW limbs for one field (ht_fr29_op, ht_fr29_field_op below)
-template <class F>
-static int fr29_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  Fr29 x, y, z;
-  for (int i = 0; i < 9; i++) {
-    x.v[i] = a[i];
-    y.v[i] = b ? b[i] : 0;
-    z.v[i] = 0;
-  }
-  fr29_overflows() = 0;
-  switch (op) {
-    case 0: z = fr29_mont<F>(x, y); break;
-    case 1: z = fr29_add(x, y); break;
-    case 2: z = fr29_sub<F>(x, y); break;
-    case 3: z = fr29_weak(x); break;
-    case 4: z = fr29_reduce256<F>(x); break;
-    case 5: z = fr29_cond_sub<F>(x); break;
-    case 8: z = fr29_fold255<F>(x); break;  // one fold (only through ht_fr29_field_op)
-    case 6: {
-      uint32_t w[8];
-      for (int i = 0; i < 8; i++) w[i] = a[i];
-      z = fr29_from_words(w);
-      break;
-    }
-    case 7: {
-      uint32_t w[8];
-      fr29_to_words(w, x);
-      for (int i = 0; i < 8; i++) z.v[i] = w[i];
-      z.v[8] = 0;
-      break;
-    }
-    default: return -1;
-  }
-  for (int i = 0; i < 9; i++) r[i] = z.v[i];
-  return fr29_overflows();
-}
-
 // inversion of n operands of 9 raw limbs at the bound A (1, 2 or 7): which = 0 f_inv (division steps, fe9_inv.hpp), 1 the kept Fermat
 // chain; out: 8 canonical wire words per operand and, in raw[9 n] when given, the limbs f_inv returned
 template <class PR, int A>
@@ -320,10 +179,11 @@ static void ht_fe9_inv_batch_t(int which, const uint32_t* a, uint32_t* out, uint
 
 extern "C" {
 
-// field: 0 secp256k1 p, 1 ed25519 p (radix-2^29 lazy form, fe9.hpp); a, b: 9 raw limbs; r: 8 wire words
+// fe9_check (fe9_check.hpp, the code of ncg_field_check fields 0 / 1): field 0 secp256k1 p, 1 ed25519 p; a, b: 9 raw limbs;
+// r: 8 wire words; -1 for an unknown field or variant
 int ht_fe9_op(int field, int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  if (field == 0) return ht_fe9_t<Fe9SecpPR>(op, variant, a, b, r);
-  if (field == 1) return ht_fe9_t<Fe9EdPR>(op, variant, a, b, r);
+  if (field == 0) return fe9_check<Fe9SecpPR>(op, variant, a, b, r);
+  if (field == 1) return fe9_check<Fe9EdPR>(op, variant, a, b, r);
   return -1;
 }
 
@@ -358,107 +218,46 @@ int ht_field_op(int field, int op, const uint32_t* a, const uint32_t* b, uint32_
   return -1;
 }
 
-// fused Fe9 expressions (ht_fe9_fused_t): field 0 secp256k1 p, 1 ed25519 p; a, b, c, d, r: 9 raw limbs
+// fe9_fused_check (fe9_check.hpp, the code of ncg_field_check fields 5 / 6): field 0 secp256k1 p, 1 ed25519 p; a, b, c, d, r:
+// 9 raw limbs; -1 for an unknown field or variant
 int ht_fe9_fused(int field, int op, int variant, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* d,
                  uint32_t* r) {
-  if (field == 0) return ht_fe9_fused_t<Fe9SecpPR>(op, variant, a, b, c, d, r);
-  if (field == 1) return ht_fe9_fused_t<Fe9EdPR>(op, variant, a, b, c, d, r);
+  if (field == 0) return fe9_fused_check<Fe9SecpPR>(op, variant, a, b, c, d, r);
+  if (field == 1) return fe9_fused_check<Fe9EdPR>(op, variant, a, b, c, d, r);
   return -1;
 }
 
-// the negated ladder formulas of ec_sw.hpp on secp256k1 Jacobian points (27 limbs X, Y, Z at the storage bound 2):
-// op 0: out = jac_dbl_neg(P);  op 1: out = jac_madd_neg(P, qx, qy), qx at bound 2, qy at bound 3 (a negated table entry)
+// the pieces of the secp256k1 fused ladder on raw limbs: secp_ladder_check (secp_ladder_check.hpp, the code of ncg_field_check
+// field 7).  ht_jac_neg: its ops 0 (the negated doubling of p) and 1 (the negated mixed addition of p and (qx, qy)); p 27 limbs
+// X, Y, Z at the storage bound 2, qx at bound 2, qy at bound 3 (a negated table entry)
 int ht_jac_neg(int op, const uint32_t* p, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
-  Jac<FeSecp> P;
-  Fe9<Fe9SecpPR, 2> x;
-  Fe9<Fe9SecpPR, 3> y;
-  for (int i = 0; i < 9; i++) {
-    P.X.v[i] = p[i];
-    P.Y.v[i] = p[9 + i];
-    P.Z.v[i] = p[18 + i];
-    x.v[i] = qx[i];
-    y.v[i] = qy[i];
-  }
-  Jac<FeSecp> R;
-  if (op == 0) R = jac_dbl_neg(P);
-  else if (op == 1) R = jac_madd_neg(P, x, y);
-  else return -1;
-  for (int i = 0; i < 9; i++) {
-    out[i] = R.X.v[i];
-    out[9 + i] = R.Y.v[i];
-    out[18 + i] = R.Z.v[i];
-  }
-  return 0;
+  if (op != 0 && op != 1) return -1;
+  return secp_ladder_check(op, p, qx, qy, out);
 }
+// secp_glv_split followed by secp_glv_make_odd; layout of ht_glv_split
+int ht_glv_split_odd(const uint32_t* k, uint32_t* out) { return secp_ladder_check(2, k, nullptr, nullptr, out); }
+// secp_glv_split followed by secp_glv_make_k1_odd (the split of CurveSecpI's ladder); layout of ht_glv_split
+int ht_glv_split_k1_odd(const uint32_t* k, uint32_t* out) { return secp_ladder_check(3, k, nullptr, nullptr, out); }
 
 // the exception-free additions of the fused ladder (ec_sw.hpp) on the same raw limbs; out = X, Y, Z and the `degenerate` verdict
 // (28 words).  op 0: jac_madd_neg_nx(P, qx, qy);  op 1: aff_add_neg_nx((P.X, P.Y), (beta qx, qy)) - P.Z is not read
 int ht_jac_neg_nx(int op, const uint32_t* p, const uint32_t* qx, const uint32_t* qy, uint32_t* out) {
-  Jac<FeSecp> P;
-  Fe9<Fe9SecpPR, 2> x;
-  Fe9<Fe9SecpPR, 3> y;
-  for (int i = 0; i < 9; i++) {
-    P.X.v[i] = p[i];
-    P.Y.v[i] = p[9 + i];
-    P.Z.v[i] = p[18 + i];
-    x.v[i] = qx[i];
-    y.v[i] = qy[i];
-  }
+  const Jac<FeSecp> P = jac_load_limbs(p);
+  const Fe9<Fe9SecpPR, 2> x = fe9_load_limbs<2>(qx);
+  const Fe9<Fe9SecpPR, 3> y = fe9_load_limbs<3>(qy);
   Jac<FeSecp> R;
   bool degenerate = false;
   if (op == 0) R = jac_madd_neg_nx(P, x, y, degenerate);
   else if (op == 1) R = aff_add_neg_nx(P.X, Fe9<Fe9SecpPR, 3>(P.Y), x, CurveSecpI::beta(), y, degenerate);
   else return -1;
-  for (int i = 0; i < 9; i++) {
-    out[i] = R.X.v[i];
-    out[9 + i] = R.Y.v[i];
-    out[18 + i] = R.Z.v[i];
-  }
+  jac_store_limbs(out, R);
   out[27] = degenerate ? 1u : 0u;
-  return 0;
-}
-
-// secp_glv_split followed by secp_glv_make_odd; layout of ht_glv_split
-int ht_glv_split_odd(const uint32_t* k, uint32_t* out) {
-  uint32_t kk[8];
-  for (int i = 0; i < 8; i++) kk[i] = k[i];
-  GlvSplit s = secp_glv_split(kk);
-  secp_glv_make_odd(s);
-  for (int i = 0; i < 5; i++) {
-    out[i] = s.k1[i];
-    out[5 + i] = s.k2[i];
-  }
-  out[10] = s.k1neg;
-  out[11] = s.k2neg;
-  return 0;
-}
-
-// secp_glv_split followed by secp_glv_make_k1_odd (the split of CurveSecpI's ladder); layout of ht_glv_split
-int ht_glv_split_k1_odd(const uint32_t* k, uint32_t* out) {
-  uint32_t kk[8];
-  for (int i = 0; i < 8; i++) kk[i] = k[i];
-  GlvSplit s = secp_glv_split(kk);
-  secp_glv_make_k1_odd(s);
-  for (int i = 0; i < 5; i++) {
-    out[i] = s.k1[i];
-    out[5 + i] = s.k2[i];
-  }
-  out[10] = s.k1neg;
-  out[11] = s.k2neg;
   return 0;
 }
 
 // GLV split of a 256-bit scalar: out = k1[5] k2[5] k1neg k2neg (12 words)
 int ht_glv_split(const uint32_t* k, uint32_t* out) {
-  uint32_t kk[8];
-  for (int i = 0; i < 8; i++) kk[i] = k[i];
-  GlvSplit s = secp_glv_split(kk);
-  for (int i = 0; i < 5; i++) {
-    out[i] = s.k1[i];
-    out[5 + i] = s.k2[i];
-  }
-  out[10] = s.k1neg;
-  out[11] = s.k2neg;
+  glv_store(out, glv_split_words(k));
   return 0;
 }
 
@@ -562,18 +361,28 @@ int ht_ntt_field(int field, int n, const uint32_t* omega, const uint32_t* in, ui
   if (t0max < 1 || tmax < 1 || 1 + (n - (n < t0max ? n : t0max) + tmax - 1) / tmax > 8) return -1;
   return ntt_host(field, n, omega, in, out, flags, t0max, tmax);
 }
-// fr29.hpp on RAW limbs (9 words each).  op 0: mont(a, b) -> 9 limbs; 1: a + b; 2: a + 3r - b; 3: weak(a);
-// 4: reduce256(a); 5: cond_sub(a); 6: from_words(a[0..7]); 7: to_words(a) -> 8 words.
-// Returns the overflow count of the call.
+// fr29.hpp on RAW limbs (9 words each): fr29_check (fr29_check.hpp, the code of ncg_field_check field 8), `variant` numbered
+// as there: 0 bls12-381 Fr, 1 bn254 Fr.  op 0: mont(a, b) -> 9 limbs; 1: a + b; 2: a + 3r - b; 3: weak(a); 4: reduce256(a);
+// 5: cond_sub(a); 6: from_words(a[0..7]); 7: to_words(a) -> 8 words; 8: one fold.  b may be null.
+// Returns the overflow count of the call, or -1 for an unknown op / variant.
+int ht_fr29_field_op(int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
+  fr29_overflows() = 0;
+  const int rc = variant == 0 ? fr29_check<Fr29Bls>(op, a, b, r) : variant == 1 ? fr29_check<Fr29Bn>(op, a, b, r) : -1;
+  return rc ? -1 : fr29_overflows();
+}
+// bls12-381 Fr, ops 0..7
 int ht_fr29_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
   if (op < 0 || op > 7) return -1;
-  return fr29_op_host<Fr29Bls>(op, a, b, r);
+  return ht_fr29_field_op(0, op, a, b, r);
 }
-// the same for either field, numbered as ncg_field_check field 8's variant: 0 bls12-381 Fr, 1 bn254 Fr; ops 0..7 and 8 = one fold
-int ht_fr29_field_op(int variant, int op, const uint32_t* a, const uint32_t* b, uint32_t* r) {
-  if (variant == 0) return fr29_op_host<Fr29Bls>(op, a, b, r);
-  if (variant == 1) return fr29_op_host<Fr29Bn>(op, a, b, r);
-  return -1;
+// the row of ncg_field_check's field table (selfcheck.hpp): out = words per row of a, b and out; -1 for a field that is refused
+int ht_field_check_shape(int field, int out[3]) {
+  const SelfCheckField* f = selfcheck_field(field);
+  if (!f) return -1;
+  out[0] = f->wa;
+  out[1] = f->wb;
+  out[2] = f->wo;
+  return 0;
 }
 // fe9m.hpp (bn254 base field, Montgomery radix 2^29) on RAW limbs: fe9m_check (fe9m_check.hpp), the same code as
 // ncg_field_check field 9.  Returns the overflow count of the call, or -1 for an unknown op / variant.
