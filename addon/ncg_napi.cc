@@ -305,6 +305,46 @@ static napi_value Ristretto(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// bls12-381 pairings on packed rows.  bls(0, g1 rows (96 B), g2 rows (192 B), offsets (n_groups + 1 little-endian uint32), flags)
+// -> n_groups GT elements (576 B each) followed by n_groups is_one bytes (ncg_pairing_batch);
+// bls(1, pk rows, sig rows, u rows, scheme) -> n verdict bytes (ncg_bls_verify_batch; scheme 0: 48 / 96 / 192 B, scheme 1: 96 / 48 / 96 B).
+static napi_value Bls(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t mode, last;
+  uint8_t *a, *b, *c, *out;
+  size_t al, bl, cl;
+  if (argc < 5 || napi_get_value_int32(env, argv[0], &mode) != napi_ok || (mode != 0 && mode != 1) || !get_u8(env, argv[1], &a, &al) ||
+      !get_u8(env, argv[2], &b, &bl) || !get_u8(env, argv[3], &c, &cl) || napi_get_value_int32(env, argv[4], &last) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: bls(mode, rows, rows, rows, flags | scheme)");
+    return nullptr;
+  }
+  if (mode == 0) {
+    const size_t n = al / 96, ng = cl >= 4 ? cl / 4 - 1 : 0;
+    if (al % 96 || bl != n * 192 || cl % 4 || cl < 4) {
+      napi_throw_error(env, nullptr, "arrays of G1 points, G2 points and group offsets must have matching lengths");
+      return nullptr;
+    }
+    std::vector<uint32_t> off(ng + 1);
+    memcpy(off.data(), c, (ng + 1) * 4);
+    napi_value res = make_u8(env, ng * 577, &out);
+    if (!res) return nullptr;
+    if (ncg_pairing_batch(g_ctx, n, a, b, ng, off.data(), last, out, out + ng * 576, nullptr) != 0) return throw_native(env);
+    return res;
+  }
+  const size_t pw = last == 0 ? 48 : 96, sw = last == 0 ? 96 : 48, uw = last == 0 ? 192 : 96, n = al / pw;
+  if ((last != 0 && last != 1) || al % pw || bl != n * sw || cl != n * uw) {
+    napi_throw_error(env, nullptr, "arrays of keys, signatures and messages must have matching lengths");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n, &out);
+  if (!res) return nullptr;
+  if (n && ncg_bls_verify_batch(g_ctx, last, n, a, b, c, out) != 0) return throw_native(env);
+  return res;
+}
+
 // eddsa.verify from (sig, msg, pk): the challenge hash runs on the device too.  msgs = all messages back to
 // back, offs = Float64Array / BigUint64Array-free: a Uint8Array holding n + 1 little-endian uint64 offsets.
 static napi_value Ed25519VerifyMsgs(napi_env env, napi_callback_info info) {
@@ -949,7 +989,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ristretto", Ristretto}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ristretto", Ristretto}, {"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

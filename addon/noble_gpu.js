@@ -869,9 +869,79 @@ function hashToCurveBatch(c, msgs, DST) {
   return unmarshalPoints(c, id, out, n, n * pb);
 }
 
+// ---- bls12-381 pairings: bls.pairingBatch for many groups in one call (bls.ts:670-693) and verify per row from bytes (:795-818).
+// pairs: [{ g1, g2 }] of registered G1 / G2 points, or of affine wire rows (Uint8Array of 96 / 192 bytes); groups: sizes summing to
+// pairs.length (omitted: ONE product, one Fp12 returned; given: an array of Fp12).  The result has the reference's Fp12 object shape
+// ({ c0: { c0: { c0, c1 }, c1, c2 }, c1: .. } of bigint, frozen); with registerBls(bls12_381) it goes through fields.Fp12.create.
+let blsFields = null, blsG1 = null, blsG2 = null;
+function registerBls(bls) {
+  blsFields = bls.fields; blsG1 = bls.G1.Point; blsG2 = bls.G2.Point;
+  register(blsG1, CURVE.BLS12_381_G1); register(blsG2, CURVE.BLS12_381_G2);
+}
+const BLS_ERRORS = ['pairing is not available for ZERO point', 'bad point: equation left != right', 'bad point: not in prime-order subgroup'];
+function blsWire(p, c, bytes, title) {
+  if (p instanceof Uint8Array) {
+    if (p.length !== bytes) throw new TypeError('"' + title + '" expected ' + bytes + ' bytes');
+    return p;
+  }
+  if (c === null || !(p instanceof c)) throw new TypeError('"' + title + '" expected ' + (bytes === 96 ? 'G1' : 'G2') + ' point, got type=' + typeof p);
+  return marshalPoints(c, curveId(c), [p]).subarray(0, bytes);
+}
+function fp12FromWire(buf, off) {
+  const f2 = (k) => Object.freeze({ c0: leNumber(buf, off + 96 * k, 48), c1: leNumber(buf, off + 96 * k + 48, 48) });
+  const f6 = (k) => Object.freeze({ c0: f2(3 * k), c1: f2(3 * k + 1), c2: f2(3 * k + 2) });
+  const v = Object.freeze({ c0: f6(0), c1: f6(1) });
+  return blsFields ? blsFields.Fp12.create(v) : v;
+}
+function pairingBatch(pairs, groups, opts) {
+  if (!Array.isArray(pairs)) throw new TypeError('"pairs" expected array, got type=' + typeof pairs);
+  const n = pairs.length, sizes = groups === undefined ? [n] : Array.from(groups);
+  if (sizes.some((x) => !Number.isInteger(x) || x < 0) || sizes.reduce((a, b) => a + b, 0) !== n) throw new Error('group sizes must be non-negative and sum to the number of pairs');
+  const g1 = new Uint8Array(n * 96), g2 = new Uint8Array(n * 192), off = new Uint8Array((sizes.length + 1) * 4);
+  pairs.forEach((pr, i) => {
+    const a = blsWire(pr.g1, blsG1, 96, 'pairs[' + i + '].g1'), b = blsWire(pr.g2, blsG2, 192, 'pairs[' + i + '].g2');
+    if (a.every((x) => x === 0) || b.every((x) => x === 0)) throw new Error(BLS_ERRORS[0]);
+    g1.set(a, i * 96); g2.set(b, i * 192);
+  });
+  let acc = 0;
+  sizes.forEach((x, g) => { acc += x; new DataView(off.buffer).setUint32(4 * (g + 1), acc, true); });
+  if (sizes.length === 0) return [];
+  init();
+  let out;
+  try { out = native.bls(0, g1, g2, off, opts && opts.checkSubgroup ? 1 : 0); } catch (e) {
+    const m = BLS_ERRORS.find((t) => e.message.includes(t));
+    throw m ? new Error(m) : e;
+  }
+  const res = sizes.map((_, g) => fp12FromWire(out, g * 576));
+  return groups === undefined ? res[0] : res;
+}
+// items: [{ signature, message, publicKey }] of BYTES (message: the raw message); { short, DST } -> boolean[]; false where the reference's
+// verify returns false or its fromBytes throws
+function blsVerifyBatch(items, opts) {
+  const short = !!(opts && opts.short), pw = short ? 96 : 48, sw = short ? 48 : 96, m = short ? 1 : 2, L = 64, uw = 2 * m * 48;
+  const dst = Buffer.from((opts && opts.DST) || (short ? 'BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_' : 'BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_'));
+  const verdict = items.map(() => false);
+  const good = items.map((_, i) => i).filter((i) => items[i].signature.length === sw && items[i].publicKey.length === pw);
+  if (good.length === 0) return verdict;
+  const pk = new Uint8Array(good.length * pw), sig = new Uint8Array(good.length * sw), u = new Uint8Array(good.length * uw);
+  good.forEach((i, k) => {
+    pk.set(items[i].publicKey, k * pw); sig.set(items[i].signature, k * sw);
+    const prb = expandMessageXmd(Buffer.from(items[i].message), dst, 2 * m * L);
+    for (let e = 0; e < 2 * m; e++) {
+      let v = 0n;
+      for (let j = 0; j < L; j++) v = (v << 8n) | BigInt(prb[e * L + j]);
+      leBytes(v % BLS_P, 48, u, k * uw + e * 48);
+    }
+  });
+  init();
+  const ok = native.bls(1, pk, sig, u, short ? 1 : 0);
+  good.forEach((i, k) => { verdict[i] = ok[k] === 1; });
+  return verdict;
+}
+
 module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, DEFAULT_MIN_POINTS, setPointCache, clearPointCache, packPoints, packScalars, pippenger, multiplyUnsafeBatch, multiplyBaseBatch, ed25519VerifyBatch,
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
-                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch,
+                   fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, registerBls, pairingBatch, blsVerifyBatch,
                    x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,

@@ -27,7 +27,9 @@
  * owns its device workspaces (grown on demand, reused across calls, released by ncg_destroy): the
  * batch multiplies keep a Jacobian scratch plus a per-item window table (secp256k1 1.6 KB, ed25519
  * 1.1 KB, bls12-381 G1 1.5 KB / G2 3.0 KB per item), the MSM about 650 B per point at 2^20, the NTT
- * a twiddle table of N elements per transform size.  Because these buffers are shared, *_dev calls
+ * a twiddle table of N elements per transform size, the pairing 672 B per pair (its Miller value) plus 4 B per group, BLS verification
+ * about 1.1 KB per row on top of its two pairs.
+ * Because these buffers are shared, *_dev calls
  * on one context must be issued in stream order (same stream, or externally ordered); growing a
  * workspace synchronises the stream it was used on.
  */
@@ -652,6 +654,65 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch
  * and points_verify_subgroup. */
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
+/* ---- bls12-381 pairings: batch pairing products and GT arithmetic ------------------------------------------
+ * A GT (Fp12) element crosses as 576 bytes: the 12 Fp coefficients in tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..,
+ * c1.c2.c1 - the order of Fp12.toBytes - each 48 bytes little-endian and canonical like every field element here.
+ *
+ * ncg_pairing_batch: bls.pairingBatch (src/abstract/bls.ts:670-693) for n_groups groups at once.  g1_affine / g2_affine
+ * are n_pairs affine wire points (96 / 192 bytes); group_offsets is a HOST array (in both forms) of n_groups + 1
+ * ascending pair offsets, the first 0 and the last n_pairs; out_gt[g] = finalExponentiate(product of the Miller values
+ * of the pairs of group g) and out_is_one[g] = 1 where that is Fp12.ONE.  Groups of one give bls.pairing per row, one
+ * group gives one pairing check, an empty group gives ONE.  out_gt may be NULL when only the booleans are wanted.
+ * Like the reference the call refuses a ZERO operand ("pairing is not available for ZERO point", bls.ts:685) and an
+ * operand that fails assertValidity - a coordinate not below p or a point off its curve ("bad point: equation left !=
+ * right") - with NCG_ERR_INVALID_ARG: *out_bad_index (optional) is the first such pair, ncg_last_error carries the
+ * message, the outputs are untouched.  Membership of the prime-order subgroups - the last part of assertValidity, "bad
+ * point: not in prime-order subgroup" - is checked only under NCG_PAIRING_CHECK_SUBGROUP (the endomorphism tests of the
+ * decoders, about two more ladders per pair): points from ncg_decode_points_batch, ncg_map_to_curve_batch and the
+ * multiplies of subgroup points are members already.
+ * There is no un-exponentiated output: a Miller value is only defined up to factors the final exponentiation removes.
+ * Both forms return after the result is complete (the refusal needs the device's verdict); n_groups = 0 returns NCG_OK. */
+#define NCG_PAIRING_CHECK_SUBGROUP 1
+int ncg_pairing_batch(ncg_ctx* ctx, size_t n_pairs, const void* g1_affine, const void* g2_affine, size_t n_groups,
+                      const uint32_t* group_offsets, int flags, void* out_gt, uint8_t* out_is_one, int64_t* out_bad_index);
+int ncg_pairing_batch_dev(ncg_ctx* ctx, size_t n_pairs, const void* g1_affine_dev, const void* g2_affine_dev, size_t n_groups,
+                          const uint32_t* group_offsets, int flags, void* out_gt_dev, uint8_t* out_is_one_dev,
+                          int64_t* out_bad_index, void* stream);
+
+/* ncg_fp12_batch: bls12_381.fields.Fp12 for a batch, out[i] = op(a[i], b[i]) on GT wire elements (any Fp12 element,
+ * not only members of GT).  b is read by NCG_FP12_MUL (an Fp12) and NCG_FP12_MUL014 (o0 || o1 || o4, three Fp2 = 288
+ * bytes: the sparse product by o0 + o1 v + o4 v w of the line function, bls.ts:476-519) and may be NULL otherwise;
+ * out is n Fp12 elements, for NCG_FP12_IS_ONE n bytes (Fp12.eql(a, ONE)); out may be a (and b): a row is read before it is written.  NCG_FP12_CYCLOTOMIC_SQR is
+ * Fp12._cyclotomicSquare (the square only for members of the cyclotomic subgroup), NCG_FP12_INV of 0 gives 0. */
+enum ncg_fp12_op {
+  NCG_FP12_MUL = 0,
+  NCG_FP12_SQR = 1,
+  NCG_FP12_INV = 2,
+  NCG_FP12_CONJUGATE = 3,
+  NCG_FP12_FROBENIUS1 = 4,
+  NCG_FP12_FROBENIUS2 = 5,
+  NCG_FP12_FROBENIUS3 = 6,
+  NCG_FP12_CYCLOTOMIC_SQR = 7,
+  NCG_FP12_MUL014 = 8,
+  NCG_FP12_FINAL_EXP = 9,
+  NCG_FP12_IS_ONE = 10
+};
+int ncg_fp12_batch(ncg_ctx* ctx, int op, size_t n, const void* a, const void* b, void* out);
+int ncg_fp12_batch_dev(ncg_ctx* ctx, int op, size_t n, const void* a_dev, const void* b_dev, void* out_dev, void* stream);
+
+
+/* ncg_bls_verify_batch: verify of bls.longSignatures (scheme 0: pk 48 bytes in G1, sig 96 bytes in G2) or bls.shortSignatures
+ * (scheme 1: pk 96 bytes, sig 48 bytes) for n independent rows (src/abstract/bls.ts:795-818).  pk_enc / sig_enc are the compressed
+ * encodings, u the hash_to_field output of each message with count 2 as ncg_map_to_curve_batch takes it (scheme 0: 192 bytes,
+ * scheme 1: 96 bytes per row).  On the device, in order: both sets are decoded with the subgroup checks, the messages mapped,
+ * e(-pk, H(m)) e(G1, sig) - scheme 1: e(H(m), -pk) e(sig, G2) - formed and taken through the pairing path as groups of two,
+ * out_ok[i] = is_one.  out_ok[i] = 0 wherever the reference's verify returns false or its fromBytes throws: an undecodable, ZERO
+ * or out-of-subgroup key or signature included.  The call itself fails only on bad arguments.  Workspace: about 1.1 KB per row
+ * beside the pairing's 2 x 672 B.  Both forms return after the result is complete. */
+int ncg_bls_verify_batch(ncg_ctx* ctx, int scheme, size_t n, const void* pk_enc, const void* sig_enc, const void* u, uint8_t* out_ok);
+int ncg_bls_verify_batch_dev(ncg_ctx* ctx, int scheme, size_t n, const void* pk_enc_dev, const void* sig_enc_dev, const void* u_dev,
+                             uint8_t* out_ok_dev, void* stream);
 
 #ifdef __cplusplus
 }

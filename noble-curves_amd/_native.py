@@ -21,6 +21,12 @@ POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
 X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
 RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
+# ncg_fp12_batch ops (enum ncg_fp12_op); a GT element is GT_BYTES on the wire
+(FP12_MUL, FP12_SQR, FP12_INV, FP12_CONJUGATE, FP12_FROBENIUS1, FP12_FROBENIUS2, FP12_FROBENIUS3, FP12_CYCLOTOMIC_SQR, FP12_MUL014,
+ FP12_FINAL_EXP, FP12_IS_ONE) = range(11)
+GT_BYTES = 576
+PAIRING_CHECK_SUBGROUP = 1   # ncg_pairing_batch flag: the reference's isTorsionFree on every operand
+BLS_LONG_SIGNATURES, BLS_SHORT_SIGNATURES = 0, 1   # ncg_bls_verify_batch schemes
 # ncg_field_check: {field: words per row of (a, b, out)}, the table of csrc/selfcheck.hpp (15 is unassigned)
 FIELD_CHECK_WORDS = {
     0: (9, 9, 8), 1: (9, 9, 8), 2: (12, 12, 12), 3: (28, 28, 12), 4: (56, 56, 24), 5: (18, 18, 9), 6: (18, 18, 9), 7: (27, 18, 27),
@@ -155,6 +161,12 @@ _OPTIONAL_PROTOS = {
     "ncg_ristretto_mul_base_batch_dev": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ristretto_msm": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_ristretto_msm_dev": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
+    "ncg_pairing_batch": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
+    "ncg_pairing_batch_dev": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
+    "ncg_bls_verify_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
+    "ncg_bls_verify_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_fp12_batch": [_vp, _i32, _sz, _vp, _vp, _vp],
+    "ncg_fp12_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
     "ncg_points_upload": [_vp, _i32, _sz, _vp, ctypes.POINTER(_vp)],
     "ncg_points_from_encoded": [_vp, _i32, _sz, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)],
     "ncg_points_curve": [_vp],
@@ -699,6 +711,77 @@ class Engine:
             err.bad_index = int(bad.value)
             raise err
         return out
+
+    # ---- bls12-381 pairings: G1 / G2 affine wire points [n, 96] / [n, 192], GT elements uint8 [n, 576] ---------------------
+    def _pairing_error(self, rc, bad):
+        err = NativeError((self.lib.ncg_last_error(self.h) or b"").decode() or "noble-gpu: native call failed (%d)" % rc)
+        err.bad_index = int(bad.value)
+        return err
+
+    def pairing_batch(self, g1, g2, group_offsets, want_gt=True, flags=0):
+        """pairingBatch of every group -> (GT [n_groups, 576] or None, is_one bool [n_groups]); group_offsets: n_groups + 1
+        ascending pair offsets.  NativeError with the attribute bad_index for a ZERO or invalid operand."""
+        g1 = np.ascontiguousarray(g1, dtype=np.uint8).reshape(-1, 96)
+        g2 = np.ascontiguousarray(g2, dtype=np.uint8).reshape(-1, 192)
+        off = np.ascontiguousarray(group_offsets, dtype=np.uint32).reshape(-1)
+        n, ng = g1.shape[0], off.shape[0] - 1
+        if g2.shape[0] != n:
+            raise ValueError("arrays of G1 and G2 points must have equal length")
+        if ng < 0:
+            raise ValueError("group offsets must hold at least one entry")
+        gt = np.zeros((ng, 576), dtype=np.uint8) if want_gt else None
+        one, bad = np.zeros((ng,), dtype=np.uint8), ctypes.c_int64(-1)
+        rc = self.lib.ncg_pairing_batch(self.h, n, g1.ctypes.data if n else None, g2.ctypes.data if n else None, ng, off.ctypes.data, flags,
+                                        gt.ctypes.data if want_gt and ng else None, one.ctypes.data if ng else None, ctypes.byref(bad))
+        if rc:
+            raise self._pairing_error(rc, bad)
+        return gt, one.astype(bool)
+
+    def pairing_batch_dev(self, n_pairs, g1_ptr, g2_ptr, group_offsets, out_gt_ptr, out_is_one_ptr, stream=None, flags=0):
+        """device-resident variant; group_offsets stays a host array.  Returns after the result is complete."""
+        off = np.ascontiguousarray(group_offsets, dtype=np.uint32).reshape(-1)
+        bad = ctypes.c_int64(-1)
+        rc = self.lib.ncg_pairing_batch_dev(self.h, n_pairs, g1_ptr, g2_ptr, off.shape[0] - 1, off.ctypes.data, flags, out_gt_ptr, out_is_one_ptr,
+                                            ctypes.byref(bad), stream)
+        if rc:
+            raise self._pairing_error(rc, bad)
+
+    def bls_verify_batch(self, scheme, pk_enc, sig_enc, u):
+        """verify per row from bytes: scheme 0 pk [n, 48] / sig [n, 96] / u [n, 192], scheme 1 pk [n, 96] / sig [n, 48] / u [n, 96]
+        (u = hash_to_field of the message, count 2) -> bool [n]"""
+        if scheme not in (BLS_LONG_SIGNATURES, BLS_SHORT_SIGNATURES):    # the library's own refusal and message
+            self._check(self.lib.ncg_bls_verify_batch(self.h, scheme, 1, None, None, None, None))
+        pw, sw, uw = (48, 96, 192) if scheme == 0 else (96, 48, 96)
+        pk = np.ascontiguousarray(pk_enc, dtype=np.uint8).reshape(-1, pw)
+        sig = np.ascontiguousarray(sig_enc, dtype=np.uint8).reshape(-1, sw)
+        u = np.ascontiguousarray(u, dtype=np.uint8).reshape(-1, uw)
+        n = pk.shape[0]
+        if sig.shape[0] != n or u.shape[0] != n:
+            raise ValueError("arrays of keys, signatures and messages must have equal length")
+        ok = np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_bls_verify_batch(self.h, scheme, n, pk.ctypes.data, sig.ctypes.data, u.ctypes.data, ok.ctypes.data))
+        return ok.astype(bool)
+
+    def bls_verify_batch_dev(self, scheme, n, pk_ptr, sig_ptr, u_ptr, out_ok_ptr, stream=None):
+        self._check(self.lib.ncg_bls_verify_batch_dev(self.h, scheme, n, pk_ptr, sig_ptr, u_ptr, out_ok_ptr, stream))
+
+    def fp12_batch(self, op, a, b=None):
+        """bls12_381.fields.Fp12 per row: out[i] = op(a[i], b[i]) -> [n, 576], or bool [n] for FP12_IS_ONE"""
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 576)
+        n = a.shape[0]
+        bw = 576 if op == FP12_MUL else 288 if op == FP12_MUL014 else 0
+        if bw:
+            b = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, bw)
+            if b.shape[0] != n:
+                raise ValueError("arrays of operands must have equal length")
+        out = np.zeros((n,), dtype=np.uint8) if op == FP12_IS_ONE else np.zeros((n, 576), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_fp12_batch(self.h, op, n, a.ctypes.data, b.ctypes.data if bw else None, out.ctypes.data))
+        return out.astype(bool) if op == FP12_IS_ONE else out
+
+    def fp12_batch_dev(self, op, n, a_ptr, b_ptr, out_ptr, stream=None):
+        self._check(self.lib.ncg_fp12_batch_dev(self.h, op, n, a_ptr, b_ptr, out_ptr, stream))
 
     def ed25519_verify_batch_msgs(self, sigs, pks, msgs_blob, msg_off, zip215=True):
         """sigs uint8 [n,64], pks [n,32], msgs_blob uint8 [total], msg_off uint64 [n+1] -> bool array [n];

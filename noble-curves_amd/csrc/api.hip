@@ -375,6 +375,8 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->ntt_ws) (void)hipFree(ctx->ntt_ws);
   if (ctx->poly_ws) (void)hipFree(ctx->poly_ws);
   if (ctx->rist_ws) (void)hipFree(ctx->rist_ws);
+  if (ctx->pair_ws) (void)hipFree(ctx->pair_ws);
+  if (ctx->bls_ws) (void)hipFree(ctx->bls_ws);
   (void)ncg_comm_destroy(ctx);
   if (ctx->comm_buf) (void)hipFree(ctx->comm_buf);
   if (ctx->sync_land) (void)hipHostFree(ctx->sync_land);
@@ -1905,6 +1907,139 @@ int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scala
   const int in = hc.in(enc, n * 32), sc = hc.in(scalars, n * 32);
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ristretto_msm_dev(ctx, n, hc.dev(in), hc.dev(sc), out32, out_bad_index, ctx->stream));
+}
+
+// ---- bls12-381 pairings (pairing.hip).  The _dev form keeps the verdict word, the group offsets and the Miller values in
+// ctx->pair_ws, never in ctx->scratch.
+static Rule pairing_rule(ncg_ctx* ctx, size_t n_pairs, size_t n_groups, const uint32_t* off, int flags) {
+  int rc = NCG_OK;
+  if (flags & ~NCG_PAIRING_CHECK_SUBGROUP) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: unknown flag bits 0x%x", flags);
+  else if (n_pairs > 0x7fffffffu || n_groups > 0x7fffffffu) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: batch too large");
+  else if (n_groups && !off) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: NULL buffer");
+  else if (n_groups) {
+    bool ok = off[0] == 0 && off[n_groups] == n_pairs;
+    for (size_t g = 0; ok && g < n_groups; g++) ok = off[g] <= off[g + 1];
+    if (!ok)
+      rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: group offsets must ascend from 0 to the number of pairs");
+  } else if (n_pairs) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: pairs without a group");
+  return {"pairing_batch", rc};
+}
+// the reference's message for each refusal (bls.ts:685; weierstrass.ts:748-766 assertValidity)
+static const char* pairing_bad_message(uint32_t code) {
+  switch (code) {
+    case 1: return "pairing is not available for ZERO point";
+    case 3:
+    case 5: return "bad point: not in prime-order subgroup";
+    default: return "bad point: equation left != right";
+  }
+}
+int ncg_pairing_batch_dev(ncg_ctx* ctx, size_t n_pairs, const void* g1_affine_dev, const void* g2_affine_dev, size_t n_groups,
+                          const uint32_t* group_offsets, int flags, void* out_gt_dev, uint8_t* out_is_one_dev, int64_t* out_bad_index,
+                          void* stream) {
+  if (out_bad_index) *out_bad_index = -1;
+  NCG_BEGIN(ctx, pairing_rule(ctx, n_pairs, n_groups, group_offsets, flags), n_groups, out_is_one_dev);
+  if (n_pairs && (!g1_affine_dev || !g2_affine_dev)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: NULL buffer");
+  const hipStream_t st = stream_of(ctx, stream);
+  const size_t off_b = align256((n_groups + 1) * 4);
+  if (int rc = ncg_grow_buf(ctx, &ctx->pair_ws, &ctx->pair_ws_bytes, 256 + off_b + n_pairs * ncg::PAIRING_WS_WORDS * 4,
+                            256 + off_b + n_pairs * ncg::PAIRING_WS_WORDS * 4, GrowWait::stream, st))
+    return rc;
+  unsigned long long* d_bad = (unsigned long long*)ctx->pair_ws;
+  uint32_t* d_off = (uint32_t*)((char*)ctx->pair_ws + 256);
+  uint32_t* d_f = (uint32_t*)((char*)ctx->pair_ws + 256 + off_b);
+  NCG_HIP(ctx, hipMemcpyAsync(d_off, group_offsets, (n_groups + 1) * 4, hipMemcpyHostToDevice, st));
+  NCG_HIP(ctx, ncg::pairing_miller((const uint32_t*)g1_affine_dev, (const uint32_t*)g2_affine_dev, flags & NCG_PAIRING_CHECK_SUBGROUP, d_f, d_bad, (int)n_pairs, st));
+  unsigned long long bad = 0;
+  NCG_HIP(ctx, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+  NCG_HIP(ctx, hipStreamSynchronize(st));  // (also: group_offsets has been read)
+  if (bad != ~0ull) {
+    if (out_bad_index) *out_bad_index = (int64_t)(bad >> 8);
+    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: %s (%s operand) at index %llu", pairing_bad_message((uint32_t)(bad & 0xff)),
+                   (bad & 0xff) == 1 ? "G1 or G2" : (bad & 0xff) <= 3 ? "G1" : "G2", bad >> 8);
+  }
+  uint32_t largest = 0;
+  for (size_t g = 0; g < n_groups; g++) largest = std::max(largest, group_offsets[g + 1] - group_offsets[g]);
+  NCG_HIP(ctx, ncg::pairing_finish(d_f, d_off, (int)n_groups, (int)n_pairs, largest, (uint32_t*)out_gt_dev, out_is_one_dev, st));
+  NCG_HIP(ctx, hipStreamSynchronize(st));
+  return NCG_OK;
+}
+int ncg_pairing_batch(ncg_ctx* ctx, size_t n_pairs, const void* g1_affine, const void* g2_affine, size_t n_groups,
+                      const uint32_t* group_offsets, int flags, void* out_gt, uint8_t* out_is_one, int64_t* out_bad_index) {
+  if (out_bad_index) *out_bad_index = -1;
+  NCG_BEGIN(ctx, pairing_rule(ctx, n_pairs, n_groups, group_offsets, flags), n_groups, out_is_one);
+  if (n_pairs && (!g1_affine || !g2_affine)) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: pairing_batch: NULL buffer");
+  HostCall hc(ctx);
+  const int a = hc.in(g1_affine, n_pairs * 96), b = hc.in(g2_affine, n_pairs * 192);
+  const int gt = out_gt ? hc.out(out_gt, n_groups * 576) : -1, one = hc.out(out_is_one, n_groups);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_pairing_batch_dev(ctx, n_pairs, hc.dev(a), hc.dev(b), n_groups, group_offsets, flags, gt < 0 ? nullptr : hc.dev(gt),
+                                         hc.dev<uint8_t>(one), out_bad_index, ctx->stream));
+}
+
+// ---- BLS signature verification for a batch (pairing.hip k_bls_pairs): decode with the subgroup checks, map the messages, two
+// pairs per row through the pairing path, is_one - five device steps, only bytes cross.  Everything between them lives in ctx->bls_ws.
+static Rule bls_rule(ncg_ctx* ctx, int scheme, size_t n) {
+  int rc = NCG_OK;
+  if (scheme != 0 && scheme != 1) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: bls_verify_batch: scheme must be 0 (long) or 1 (short), got %d", scheme);
+  else if (n > 0x3fffffffu) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: bls_verify_batch: batch too large");
+  return {"bls_verify_batch", rc};
+}
+int ncg_bls_verify_batch_dev(ncg_ctx* ctx, int scheme, size_t n, const void* pk_enc_dev, const void* sig_enc_dev, const void* u_dev,
+                             uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, bls_rule(ctx, scheme, n), n, pk_enc_dev, sig_enc_dev, u_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  const int pk_curve = scheme == 0 ? NCG_BLS12_381_G1 : NCG_BLS12_381_G2, sig_curve = scheme == 0 ? NCG_BLS12_381_G2 : NCG_BLS12_381_G1;
+  const size_t pkb = align256(n * (size_t)ncg_point_bytes(pk_curve)), sgb = align256(n * (size_t)ncg_point_bytes(sig_curve)), fb = align256(n);
+  const size_t g1b = align256(2 * n * 96), g2b = align256(2 * n * 192);
+  const size_t total = pkb + 2 * sgb + 7 * fb + g1b + g2b;
+  if (int rc = ncg_grow_buf(ctx, &ctx->bls_ws, &ctx->bls_ws_bytes, total, total, GrowWait::stream, st)) return rc;
+  char* p = (char*)ctx->bls_ws;
+  uint32_t* d_pk = (uint32_t*)p;  p += pkb;
+  uint32_t* d_sig = (uint32_t*)p; p += sgb;
+  uint32_t* d_hm = (uint32_t*)p;  p += sgb;
+  uint8_t* fl[7];
+  for (int k = 0; k < 7; k++) { fl[k] = (uint8_t*)p; p += fb; }   // pk ok / inf, sig ok / inf, hm inf, bad, is_one
+  uint32_t* d_g1 = (uint32_t*)p;  p += g1b;
+  uint32_t* d_g2 = (uint32_t*)p;
+  if (int rc = ncg_decode_points_batch_dev(ctx, pk_curve, n, pk_enc_dev, 0, d_pk, fl[0], fl[1], st)) return rc;
+  if (int rc = ncg_decode_points_batch_dev(ctx, sig_curve, n, sig_enc_dev, 0, d_sig, fl[2], fl[3], st)) return rc;
+  if (int rc = ncg_map_to_curve_batch_dev(ctx, sig_curve, n, 2, u_dev, d_hm, fl[4], st)) return rc;
+  NCG_HIP(ctx, ncg::bls_build_pairs(scheme, d_pk, fl[0], fl[1], d_sig, fl[2], fl[3], d_hm, fl[4], d_g1, d_g2, fl[5], (int)n, st));
+  std::vector<uint32_t> off(n + 1);
+  for (size_t i = 0; i <= n; i++) off[i] = (uint32_t)(2 * i);
+  // (every point is a decoded or mapped subgroup member or a generator: the pairing refuses nothing here)
+  if (int rc = ncg_pairing_batch_dev(ctx, 2 * n, d_g1, d_g2, n, off.data(), 0, nullptr, fl[6], nullptr, st)) return rc;
+  NCG_HIP(ctx, ncg::bls_verdict(fl[6], fl[5], out_ok_dev, (int)n, st));
+  NCG_HIP(ctx, hipStreamSynchronize(st));
+  return NCG_OK;
+}
+int ncg_bls_verify_batch(ncg_ctx* ctx, int scheme, size_t n, const void* pk_enc, const void* sig_enc, const void* u, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, bls_rule(ctx, scheme, n), n, pk_enc, sig_enc, u, out_ok);
+  HostCall hc(ctx);
+  const int pk = hc.in(pk_enc, n * (scheme == 0 ? 48 : 96)), sg = hc.in(sig_enc, n * (scheme == 0 ? 96 : 48));
+  const int du = hc.in(u, n * (scheme == 0 ? 192 : 96)), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_bls_verify_batch_dev(ctx, scheme, n, hc.dev(pk), hc.dev(sg), hc.dev(du), hc.dev<uint8_t>(ok), ctx->stream));
+}
+
+static Rule fp12_rule(ncg_ctx* ctx, int op) {
+  return {"fp12_batch", op >= NCG_FP12_MUL && op <= NCG_FP12_IS_ONE ? NCG_OK : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: fp12_batch: unknown op %d", op)};
+}
+static size_t fp12_b_bytes(int op) { return op == NCG_FP12_MUL ? 576 : op == NCG_FP12_MUL014 ? 288 : 0; }
+int ncg_fp12_batch_dev(ncg_ctx* ctx, int op, size_t n, const void* a_dev, const void* b_dev, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, fp12_rule(ctx, op), n, a_dev, out_dev);
+  if (fp12_b_bytes(op) && !b_dev) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: fp12_batch: NULL buffer");
+  NCG_HIP(ctx, ncg::fp12_batch(op, (const uint32_t*)a_dev, (const uint32_t*)b_dev, out_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_fp12_batch(ncg_ctx* ctx, int op, size_t n, const void* a, const void* b, void* out) {
+  NCG_BEGIN(ctx, fp12_rule(ctx, op), n, a, out);
+  if (fp12_b_bytes(op) && !b) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: fp12_batch: NULL buffer");
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * 576), db = fp12_b_bytes(op) ? hc.in(b, n * fp12_b_bytes(op)) : -1;
+  const int o = hc.out(out, op == NCG_FP12_IS_ONE ? n : n * 576);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_fp12_batch_dev(ctx, op, n, hc.dev(da), db < 0 ? nullptr : hc.dev(db), hc.dev(o), ctx->stream));
 }
 
 static Rule field_rule(ncg_ctx* ctx, int field, size_t n) {

@@ -66,6 +66,12 @@ struct ncg_ctx {
   // the (X, Y, Z) rows of the fixed-base walk, a broadcast scalar; one call at a time
   void* rist_ws = nullptr;
   size_t rist_ws_bytes = 0;
+  // pairings (pairing.hip): the verdict word, the group offsets and one Miller value per pair; one call at a time
+  void* pair_ws = nullptr;
+  size_t pair_ws_bytes = 0;
+  // BLS verification (ncg_bls_verify_batch): decoded keys and signatures, mapped messages, their flags and the two pairs per row
+  void* bls_ws = nullptr;
+  size_t bls_ws_bytes = 0;
   // multi-GPU (comm.hip): RCCL communicator of this rank and the gather buffer of the sharded MSM
   void* comm = nullptr;  // ncclComm_t
   int comm_rank = 0, comm_size = 1;

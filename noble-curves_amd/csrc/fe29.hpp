@@ -402,6 +402,10 @@ NCG_DI Fe29x2<2> f_inv(const Fe29x2<A>& a) {  // tower.ts:458-475
 // count as Karatsuba: mul = 2 lanes x (2 products + 1 reduction), sqr = 2 lanes x 1 product.
 // Every data-dependent decision (is_zero, f_eqz) is made pair-uniform, so the two lanes of a
 // pair always follow the same control flow.  Device only.
+// CAUTION: do not SUBTRACT a swapped multi-limb value directly (`a.h - pair_swap(a.h)`).  In fp12.hpp that expression gave a wrong
+// lowest limb on the even lane on gfx950 where the difference fed a second subtraction (results right on the CPU twin and at every
+// other use); the cause is not established - possibly the DPP move being folded into the limb-0 subtract, the only limb without a
+// borrow-in.  Negate on the sending lane and ADD what arrives (f2_mul_nr), or select between own and swapped halves first (f_sqr).
 NCG_DI uint32_t pair_swap(uint32_t v) {
 #ifdef __HIP_DEVICE_COMPILE__
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);

@@ -221,6 +221,25 @@ void ristretto_from_uniform_host(const uint32_t* bytes64, uint32_t* out, uint32_
 void ristretto_mul_host(const uint32_t* enc, const uint32_t* scalars, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
 int ristretto_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// bls12-381 pairings (pairing.hip).  ws: PAIRING_WS_WORDS words per pair; off: n_groups + 1 ascending pair offsets (device);
+// first_bad: one 64-bit word, all ones or (index << 8 | PairingBad code) of the first refused pair after pairing_miller;
+// pairing_finish multiplies each group's Miller values (largest_group decides the number of passes), exponentiates and stores
+// 144 canonical wire words per group (out_gt may be null) and the is_one bytes.  fp12_batch: the Fp12 ops of ncg_fp12_batch.
+constexpr size_t PAIRING_WS_WORDS = 168;
+hipError_t pairing_miller(const uint32_t* g1, const uint32_t* g2, int subgroup, uint32_t* ws, unsigned long long* first_bad, int n, hipStream_t st);
+hipError_t pairing_finish(uint32_t* ws, const uint32_t* off, int n_groups, int n, uint32_t largest_group, uint32_t* out_gt,
+                          uint8_t* out_is_one, hipStream_t st);
+hipError_t fp12_batch(int op, const uint32_t* a, const uint32_t* b, void* out, int n, hipStream_t st);
+void fp12_op_host(int op, const uint32_t* a, const uint32_t* b, void* out, int n, bool raw = false);  // raw: a as 168 stored words
+int64_t pairing_host(const uint32_t* g1, const uint32_t* g2, int n, const uint32_t* off, int n_groups, int subgroup, uint32_t* out_gt,
+                     uint8_t* out_is_one, uint32_t* bad_code);
+// BLS verification rows (pairing.hip): two pairs per row from decoded keys / signatures and mapped messages; bad[i] = 1 and generator
+// pairs where a key or signature did not decode or any of the three points is ZERO; out_ok = is_one && !bad
+hipError_t bls_build_pairs(int scheme, const uint32_t* pk, const uint8_t* pk_ok, const uint8_t* pk_inf, const uint32_t* sig,
+                           const uint8_t* sig_ok, const uint8_t* sig_inf, const uint32_t* hm, const uint8_t* hm_inf, uint32_t* g1,
+                           uint32_t* g2, uint8_t* bad, int n, hipStream_t st);
+hipError_t bls_verdict(const uint8_t* is_one, const uint8_t* bad, uint8_t* out_ok, int n, hipStream_t st);
+
 // field-level self-check (selfcheck.hip; the fields and their row widths: selfcheck.hpp): out[i] = op(a[i], b[i]) on the device
 // field code
 hipError_t field_check_run(int field, int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,

@@ -24,6 +24,7 @@
 #include "selfcheck.hpp"
 #include "x25519.hip"
 #include "ristretto.hip"
+#include "pairing.hip"
 
 using namespace ncg;
 
@@ -680,6 +681,27 @@ int ht_msm_plan_top(int curve, int n, int c_override, uint32_t* out16) {
   out16[4] = msm_plan_top_vmax(pl);
   out16[5] = (uint32_t)pl.nb;
   for (int i = 0; i < 10; i++) out16[6 + i] = pl.hconst[i];
+  return 0;
+}
+
+// bls12-381 pairing twins (tests/pairing_helpers.py): the templates of fp12.hpp / pairing.hpp on the unpaired Fp2.
+// ht_fp12_op: the ops of ncg_fp12_batch on wire rows; raw != 0 reads `a` as 168 stored words (Montgomery limbs below 256 p).
+// ht_pairing: ncg_pairing_batch (flags as there); returns -1 or the first refused pair with its code in *bad_code.
+int ht_fp12_op(int op, const uint32_t* a, const uint32_t* b, void* out, int n, int raw) {
+  if (op < 0 || op > 10) return -1;
+  fp12_op_host(op, a, b, out, n, raw != 0);
+  return 0;
+}
+long long ht_pairing(const uint32_t* g1, const uint32_t* g2, int n, const uint32_t* off, int n_groups, int flags, uint32_t* out_gt,
+                     uint8_t* out_is_one, uint32_t* bad_code) {
+  return (long long)pairing_host(g1, g2, n, off, n_groups, flags & NCG_PAIRING_CHECK_SUBGROUP, out_gt, out_is_one, bad_code);
+}
+// Frobenius coefficients as the lane code holds them: 3 tables x 4 powers x (c0, c1) as 12 canonical wire words each
+int ht_tower_consts(uint32_t* out) {
+  const uint32_t (*tabs[3])[2][14] = {BlsTower::FROB6_C1, BlsTower::FROB6_C2, BlsTower::FROB12};
+  for (int t = 0; t < 3; t++)
+    for (int k = 0; k < 4; k++)
+      for (int c = 0; c < 2; c++) fe29_to_wire(out + ((t * 4 + k) * 2 + c) * 12, fe29_const(tabs[t][k][c]));
   return 0;
 }
 

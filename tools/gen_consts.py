@@ -205,6 +205,19 @@ def main():
     assert psi2_x[1] == 0 and f2pow(base, (bp * bp - 1) // 2) == (bp - 1, 0)
     out += "  static constexpr uint32_t PSI2_X[14] = %s;  // in Fp\n" % m29(psi2_x[0])
     out += "};\n\n"
+    # Frobenius coefficients of the Fp6 / Fp12 tower over v^3 = u + 1, w^2 = v (src/abstract/tower.ts:136-179
+    # calcFrobeniusCoefficients, used at :587-602 and :865-875): rows k = 0..3 of
+    #   FROB6_C1[k] = (u+1)^((p^k - 1)/3), FROB6_C2[k] = (u+1)^((2 p^k - 2)/3), FROB12[k] = (u+1)^((p^k - 1)/6)
+    out += "// Frobenius coefficients of Fp6 / Fp12 (powers 0..3), radix-2^29 Montgomery form, [k][c0 | c1][limb]\nstruct BlsTower {\n"
+    for name, mul, div in (("FROB6_C1", 1, 3), ("FROB6_C2", 2, 3), ("FROB12", 1, 6)):
+        rows = []
+        for k in range(4):
+            num = mul * bp ** k - mul
+            assert num % div == 0
+            rows.append(f2pow((1, 1), num // div))
+        out += "  static constexpr uint32_t %s[4][2][14] = {\n%s\n  };\n" % (
+            name, ",\n".join("    {%s, %s}" % (m29(a), m29(b)) for a, b in rows))
+    out += "};\n\n"
     out += "// exponents / thresholds for bls12-381 Fp square roots and the compressed-point sort bit\nstruct BlsFpConsts {\n"
     out += arr("SQRT_EXP", (bp + 1) // 4, 12)          # p = 3 mod 4: sqrt(a) = a^((p+1)/4)
     out += arr("SQRT_EXP_M1", (bp - 3) // 4, 12)       # a^((p-3)/4): sqrt candidate and its inverse at once
