@@ -9,7 +9,10 @@
 //   ed25519VerifyBatch(sigs, pks, ks, zip215: bool)  -> Uint8Array n (0 / 1)
 //   x25519(kind, scalars | null, rows)               -> Uint8Array n * 33 (32-byte results, then ok flags); kind 0 scalarMult
 //                                                       (scalars: n rows, or ONE row used for every u), 1 getPublicKey, 2 toMontgomery
-//   ristretto(mode, a, b | null)                     -> ristretto255 on packed rows; mode 0 decode (a: n x 32) -> n x 64 points + n ok flags,
+//   ed448(kind, a | null, b, c)                      -> kind 0 x448.scalarMult (a scalars: n rows or ONE, b u rows), 1 x448.getPublicKey (b):
+//                                                       Uint8Array n * 57 (56-byte results, then ok flags); 2 ed448 verify (a signatures,
+//                                                       b public keys, c challenges) -> Uint8Array n (0 / 1)
+//   ristretto(mode, a, b | null)                   -> ristretto255 on packed rows; mode 0 decode (a: n x 32) -> n x 64 points + n ok flags,
 //                                                       1 encode (a: n x 64) -> n x 32, 2 equals (a, b: n x 64) -> n flags,
 //                                                       3 deriveToCurve (a: n x 64) -> n x 32, 4 multiply (a: n x 32 encodings, b: n or ONE
 //                                                       scalar row) -> n x 32 + n ok flags, 5 BASE.multiply (a: n x 32 scalars) -> n x 32,
@@ -264,6 +267,37 @@ static napi_value X25519(napi_env env, napi_callback_info info) {
   if (n && kind == 0) rc = ncg_x25519_batch(g_ctx, n, sc, rows, sl != rl ? NCG_X25519_ONE_SCALAR : 0, out, out + n * 32);
   else if (n && kind == 1) rc = ncg_x25519_base_batch(g_ctx, n, rows, out, out + n * 32);
   else if (n) rc = ncg_ed25519_to_montgomery_batch(g_ctx, n, rows, out, out + n * 32);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
+// X448 and Ed448 on packed rows (ncg_x448_batch, ncg_x448_base_batch, ncg_ed448_verify_batch): kind 0 (scalars, us) - one 56-byte scalar
+// row against n > 1 rows of u selects NCG_X448_ONE_SCALAR - and kind 1 (null, secret keys): n x 56 bytes, then n ok flags (a refused row
+// is zero); kind 2 (signatures n x 114, public keys n x 57, challenges n x 56) -> n verdicts (0 / 1).
+static napi_value Ed448(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind;
+  uint8_t *a = nullptr, *b = nullptr, *c = nullptr, *out;
+  size_t al = 0, bl = 0, cl = 0;
+  bool good = argc >= 3 && napi_get_value_int32(env, argv[0], &kind) == napi_ok && kind >= 0 && kind <= 2 && get_u8(env, argv[2], &b, &bl);
+  if (good && kind == 0) good = bl % 56 == 0 && get_u8(env, argv[1], &a, &al) && (al == bl || al == 56);
+  if (good && kind == 1) good = bl % 56 == 0;
+  if (good && kind == 2)
+    good = argc >= 4 && get_u8(env, argv[1], &a, &al) && get_u8(env, argv[3], &c, &cl) && al % 114 == 0 && bl == al / 114 * 57 && cl == al / 114 * 56;
+  if (!good) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: ed448(kind, scalars | signatures | null, rows, challenges)");
+    return nullptr;
+  }
+  const size_t n = kind == 2 ? al / 114 : bl / 56;
+  napi_value res = make_u8(env, kind == 2 ? n : n * 57, &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (n && kind == 0) rc = ncg_x448_batch(g_ctx, n, a, b, al != bl ? NCG_X448_ONE_SCALAR : 0, out, out + n * 56);
+  else if (n && kind == 1) rc = ncg_x448_base_batch(g_ctx, n, b, out, out + n * 56);
+  else if (n) rc = ncg_ed448_verify_batch(g_ctx, n, a, b, c, out);
   if (rc != 0) return throw_native(env);
   return res;
 }
@@ -989,7 +1023,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ristretto", Ristretto}, {"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

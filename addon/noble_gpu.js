@@ -8,6 +8,8 @@
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
 //   x25519ScalarMultBatch(items)           - array form of x25519.scalarMult / getSharedSecret (abstract/montgomery.ts:314-331);
 //   x25519GetPublicKeyBatch(secretKeys)      x25519.getPublicKey; ed25519ToMontgomeryBatch(publicKeys): ed25519.utils.toMontgomery
+//   x448ScalarMultBatch(items), x448GetPublicKeyBatch(secretKeys) - x448.scalarMult / getPublicKey (ed448.ts:284-311);
+//   ed448VerifyBatch(items, { context, prehash }) - ed448 / ed448ph verify, the SHAKE256 challenge hashed here on the host
 //   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
 //                                            BASE.multiply, an MSM from encodings and ristretto255_hasher.deriveToCurve
 //                                            (src/ed25519.ts:443-668), with single-item forms that throw the reference's messages
@@ -534,6 +536,91 @@ function ed25519ToMontgomeryBatch(publicKeys) {
   init();
   return x25519Rows(native.x25519(2, null, K), n);
 }
+// ---- X448 and Ed448 verification (ed448.ts; abstract/montgomery.ts:247-420, abstract/edwards.ts:942-989) ----------------------
+// The same buffers-in / buffers-out convention as the X25519 calls.  Hashing stays on the host: the challenge
+// k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114) mod n and the ed448ph prehash use crypto.createHash('shake256').
+function abytesT(b, len, title) {               // utils abytes(value, length | undefined, title)
+  const bytes = b instanceof Uint8Array;
+  if (!bytes || (len !== undefined && b.length !== len))
+    throw new Error(`"${title}" expected Uint8Array` + (len !== undefined ? ' of length ' + len : '') + ', got ' +
+                    (bytes ? `length=${b.length}` : `type=${typeof b}`));
+  return b;
+}
+function x448Rows(packed, n) {
+  const out = new Array(n);
+  for (let i = 0; i < n; i++) out[i] = packed[56 * n + i] === 1 ? packed.slice(56 * i, 56 * i + 56) : null;
+  return out;
+}
+// items: [{scalar, u}] - or {scalar, us}: ONE secret against many peer keys.  The u coordinate of a row is checked before its scalar.
+function x448ScalarMultBatch(items) {
+  const one = !Array.isArray(items);
+  const us = one ? items.us : items.map((it) => it.u);
+  const n = us.length;
+  const U = new Uint8Array(56 * n), S = new Uint8Array(one ? 56 : 56 * n);
+  for (let i = 0; i < n; i++) {
+    U.set(abytesT(us[i], 56, 'uCoordinate'), 56 * i);
+    if (!one) S.set(abytesT(items[i].scalar, 56, 'scalar'), 56 * i);
+  }
+  if (one) S.set(abytesT(items.scalar, 56, 'scalar'), 0);
+  if (n === 0) return [];
+  init();
+  return x448Rows(native.ed448(0, S, U), n);
+}
+function x448GetPublicKeyBatch(secretKeys) {
+  const n = secretKeys.length, S = new Uint8Array(56 * n);
+  secretKeys.forEach((k, i) => S.set(abytesT(k, 56, 'scalar'), 56 * i));
+  if (n === 0) return [];
+  init();
+  return x448Rows(native.ed448(1, null, S), n);
+}
+const ED448_N = (1n << 446n) - 13818066809895115352007386748515426880336692474882178609894547503885n;
+const ED448_P = (1n << 448n) - (1n << 224n) - 1n;
+function ed448Decodes(enc) {                    // whether Point.fromBytes (strict) accepts the 57 bytes
+  if (enc[56] & 0x7f) return false;
+  const P = ED448_P, y = leNumber(enc, 0, 56);
+  if (y >= P) return false;
+  const y2 = y * y % P, x2 = (y2 - 1n + P) % P * powMod(((P - 39081n) * y2 - 1n + P) % P, P - 2n, P) % P;
+  if (x2 !== 0n && powMod(x2, (P - 1n) / 2n, P) !== 1n) return false;
+  return !(x2 === 0n && (enc[56] & 0x80));
+}
+function ed448SmallOrder(enc) {                 // a canonical encoding of one of the four points of order 1, 2, 4 (ed448.ts:738-743)
+  const y = leNumber(enc, 0, 56);
+  return y === 1n || y === ED448_P - 1n || y === 0n;
+}
+function shake256(len, ...parts) {
+  const h = crypto.createHash('shake256', { outputLength: len });
+  for (const p of parts) h.update(p);
+  return h.digest();
+}
+// items: [{sig, msg, publicKey}] -> array of booleans; opts.context (Uint8Array, at most 255 bytes) and opts.prehash (true: ed448ph)
+// hold for the whole batch
+function ed448VerifyBatch(items, opts = {}) {
+  const context = opts.context === undefined ? new Uint8Array(0) : abytesT(opts.context, undefined, 'context');
+  const prehash = !!opts.prehash, n = items.length;
+  const S = new Uint8Array(114 * n), A = new Uint8Array(57 * n), K = new Uint8Array(56 * n);
+  for (let i = 0; i < n; i++) {
+    const sig = abytesT(items[i].sig, 114, 'signature');
+    let msg = abytesT(items[i].msg, undefined, 'message');
+    const pk = abytesT(items[i].publicKey, 57, 'publicKey');
+    if (context.length > 255) {
+      // edwards.ts:964-984: dom4 refuses the context only for a row that got past the decoding of A and R, s < n and the small-order
+      // test; every other row is false without the context being looked at (rare path: host integers)
+      if (ed448Decodes(pk) && ed448Decodes(sig.subarray(0, 57)) && leNumber(sig, 57, 57) < ED448_N && !ed448SmallOrder(pk))
+        throw new Error('context must be smaller than 255, got: ' + context.length);
+      continue;
+    }
+    if (prehash) msg = shake256(64, msg);
+    const dom = Buffer.concat([Buffer.from('SigEd448'), Buffer.from([prehash ? 1 : 0, context.length]), context]);
+    S.set(sig, 114 * i);
+    A.set(pk, 57 * i);
+    leBytes(leNumber(shake256(114, dom, sig.subarray(0, 57), pk, msg), 0, 114) % ED448_N, 56, K, 56 * i);
+  }
+  if (n === 0) return [];
+  if (context.length > 255) return new Array(n).fill(false);
+  init();
+  return Array.from(native.ed448(2, S, A, K), (v) => v === 1);
+}
+
 const X25519_P = (1n << 255n) - 19n;
 const X25519_LOW = [0n, 1n, X25519_P - 1n, 325606250916557431795983626356110631294008115727848805560023387167927233504n,
                     39382357235489614581723060781553021112529911719440698176882885853963445705823n];
@@ -943,6 +1030,7 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
                    fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, registerBls, pairingBatch, blsVerifyBatch,
                    x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery,
+                   x448ScalarMultBatch, x448GetPublicKeyBatch, ed448VerifyBatch,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
                    ristrettoDeriveToCurve, native };

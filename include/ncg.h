@@ -533,6 +533,69 @@ int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scala
 int ncg_ristretto_msm_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, void* out32,
                           int64_t* out_bad_index, void* stream);
 
+/* ---- X448 (RFC 7748) and Ed448-Goldilocks (RFC 8032): the reference's src/ed448.ts -------------------------------
+ * The curve has no ncg_curve id and no ncg_field_check field: these are dedicated entry points, bytes in and bytes out.
+ * Field elements and scalars are 56 bytes little-endian, read as 14 words: a DEVICE pointer to such rows (scalars56, u56, out56,
+ * k56, the affine points x || y of 112 bytes) must be 4-byte aligned and is refused, not dereferenced, otherwise.  Encoded
+ * points (57 bytes) and signatures (114 bytes) are packed rows and may sit at any address.  Host pointers may sit at any address.
+ * Rejected rows come back as zero rows with out_ok[i] = 0.  n = 0 returns NCG_OK and touches nothing; n >= 2^31 is refused
+ * ("too large") before any buffer is read; unknown flag bits return NCG_ERR_INVALID_ARG.
+ *
+ * ncg_x448_batch: out56[i] = x448.scalarMult(scalars56[i], u56[i]) = getSharedSecret (src/abstract/montgomery.ts:314-331 with
+ * the ladder of :352-393, a24 = 39081, 448 steps).  The scalar bytes are RAW: the call clamps them (ed448.ts:122-130:
+ * b[0] &= 252, b[55] |= 128).  u has no masked bit (montgomery.ts:277-287) and is reduced mod p = 2^448 - 2^224 - 1, so the
+ * encodings p .. 2^448 - 1 are accepted.  The low-order u 0, 1, p - 1 in any encoding (p and p + 1 included) give out_ok = 0
+ * ('invalid private or public key received', :303-325), as does a zero result (:329).  flags: NCG_X448_ONE_SCALAR =
+ * `scalars56` holds ONE secret used for every row.
+ * ncg_x448_base_batch: out56[i] = x448.getPublicKey(scalars56[i]) = scalarMult(scalars56[i], 5); the reference's Edwards hook
+ * (ed448.ts:299-309) gives the same bytes.
+ *
+ * ncg_ed448_decode_batch: Point.fromBytes(enc57[i]) under the strict rules (src/abstract/edwards.ts:405-436, zip215 = false,
+ * uvRatio of ed448.ts:135-153) -> x || y, 56 bytes each, canonical.  Refused: y >= p (any bit of byte 56 but bit 7), a y with
+ * no x, x = 0 with the sign bit.
+ * ncg_ed448_encode_batch: Point.toBytes (edwards.ts:620-628) of affine points: y, then the parity of x in bit 7 of byte 56.
+ * ncg_ed448_add_pairs_batch: Point.add (subtract != 0: Point.subtract) of affine points by the complete a = 1 formulas: the
+ * identity, the points of order 2 and 4, P = Q and P = -Q need no care by the caller.  The inputs are not validated.
+ * ncg_ed448_mul_batch: out57[i] = fromBytes(enc57[i]).multiplyUnsafe(k56[i]).toBytes(), k any value below 2^448 (the exact
+ * integer multiple, k = 0 gives the identity).  flags: NCG_ED448_ONE_SCALAR = one k for every row.
+ * ncg_ed448_mul_base_batch: out57[i] = BASE.multiplyUnsafe(k56[i]).toBytes().
+ * ncg_ed448_to_montgomery_batch: ed448.utils.toMontgomery (ed448.ts:171-179): u = y^2 / x^2 of the strictly decoded key;
+ * out_ok = 0 where decoding fails and for x = 0.
+ * ncg_ed448_verify_batch: eddsa.verify (edwards.ts:942-989) per row with the challenge given: sig114 = R || s, pk57 = A,
+ * k56 = the challenge (any value below 2^448; the caller hashes: k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114)
+ * mod n, ed448.ts:190-201).  A and R are decoded strictly, s >= n is refused, a small-order A (the four points of order 1, 2, 4)
+ * is refused even where the equation holds, and the row is accepted iff [4]([s]B - [k]A - R) is the identity - cofactored: an R
+ * with a torsion component is accepted when the equation holds.
+ *
+ * Nothing in the ladder branches or indexes on a scalar bit, but the library makes no constant-time claim; the Edwards
+ * multiplications are multiplyUnsafe and the verification works on public data. */
+#define NCG_X448_ONE_SCALAR 1
+#define NCG_ED448_ONE_SCALAR 1
+int ncg_x448_batch(ncg_ctx* ctx, size_t n, const void* scalars56, const void* u56, int flags, void* out56, uint8_t* out_ok);
+int ncg_x448_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars56_dev, const void* u56_dev, int flags, void* out56_dev,
+                       uint8_t* out_ok_dev, void* stream);
+int ncg_x448_base_batch(ncg_ctx* ctx, size_t n, const void* scalars56, void* out56, uint8_t* out_ok);
+int ncg_x448_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars56_dev, void* out56_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_ed448_decode_batch(ncg_ctx* ctx, size_t n, const void* enc57, void* out_affine112, uint8_t* out_ok);
+int ncg_ed448_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc57_dev, void* out_affine112_dev, uint8_t* out_ok_dev,
+                               void* stream);
+int ncg_ed448_encode_batch(ncg_ctx* ctx, size_t n, const void* affine112, void* out57);
+int ncg_ed448_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine112_dev, void* out57_dev, void* stream);
+int ncg_ed448_add_pairs_batch(ncg_ctx* ctx, size_t n, const void* a112, const void* b112, int subtract, void* out112);
+int ncg_ed448_add_pairs_batch_dev(ncg_ctx* ctx, size_t n, const void* a112_dev, const void* b112_dev, int subtract,
+                                  void* out112_dev, void* stream);
+int ncg_ed448_mul_batch(ncg_ctx* ctx, size_t n, const void* enc57, const void* k56, int flags, void* out57, uint8_t* out_ok);
+int ncg_ed448_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc57_dev, const void* k56_dev, int flags, void* out57_dev,
+                            uint8_t* out_ok_dev, void* stream);
+int ncg_ed448_mul_base_batch(ncg_ctx* ctx, size_t n, const void* k56, void* out57);
+int ncg_ed448_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* k56_dev, void* out57_dev, void* stream);
+int ncg_ed448_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk57, void* out56, uint8_t* out_ok);
+int ncg_ed448_to_montgomery_batch_dev(ncg_ctx* ctx, size_t n, const void* pk57_dev, void* out56_dev, uint8_t* out_ok_dev,
+                                      void* stream);
+int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const void* pk57, const void* k56, uint8_t* out_ok);
+int ncg_ed448_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, const void* k56_dev,
+                               uint8_t* out_ok_dev, void* stream);
+
 /* ---- measurement helpers (not on the product path) ------------------------------------ */
 /* ---- secp256k1 ECDSA batch verification --------------------------------------------------------
  * out_ok[i] = ecdsa.verify(sig[i], msgHash[i], publicKey[i], { prehash: false, format: 'compact', lowS })
@@ -654,6 +717,24 @@ int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float
  * encode / points_from_encoded / aggregate_encoded return NCG_ERR_UNSUPPORTED, as do mul_base_batch, map_to_curve_batch
  * and points_verify_subgroup. */
 int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
+/* The lane code of csrc/fe448.hpp and csrc/ed448.hpp (GF(2^448 - 2^224 - 1), X448, Ed448) on n rows of RAW uint32 words.  It is
+ * an entry point of its own because the table of ncg_field_check is closed.  A field element is 16 limbs in radix 2^28; "at
+ * bound B" means every limb below B * (2^28 + 2^10).  Words per row (a, b, out) and the input bounds, per op:
+ *   0  a * b                       (16, 16, 16)   a at 3, b at 2; out at 1
+ *   1  a^2                         (16,  0, 16)   a at 2; out at 1
+ *   2  a + b, a - b, -a            (16, 16, 48)   both at 1; out at 2, 3, 1
+ *   3  a + 39081 b                 (16, 16, 16)   a at 3, b at 2; out at 1
+ *   4  the canonical store         (16,  0, 14)   a at 8; out = the 14 LE words of the residue
+ *   5  the 56-byte load            (14,  0, 16)   a = 14 LE words of any value below 2^448; out at 1, the same integer
+ *   6  a^((p - 3) / 4)             (16,  0, 16)   a at 1; out at 1
+ *   7  1 / a                       (16,  0, 16)   a at 1; out at 1 (0 -> 0)
+ *   8  one X448 ladder step        (64, 16, 64)   a = x2 z2 x3 z3, b = x1, all at 1, swap bit = variant & 1; out at 1
+ *   9  one Edwards addition        (48, 48, 48)   a, b = X Y Z projective, all at 1; out at 1
+ *  10  one Edwards doubling        (48,  0, 48)   a = X Y Z; out at 1
+ * b is required (non-NULL) even where its width is 0.  An op nobody defines reads nothing and leaves out zero (rows of 16
+ * words).  n above 2^24 is refused. */
+int ncg_fe448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
 /* ---- bls12-381 pairings: batch pairing products and GT arithmetic ------------------------------------------
  * A GT (Fp12) element crosses as 576 bytes: the 12 Fp coefficients in tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..,

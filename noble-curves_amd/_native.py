@@ -32,6 +32,11 @@ FIELD_CHECK_WORDS = {
     0: (9, 9, 8), 1: (9, 9, 8), 2: (12, 12, 12), 3: (28, 28, 12), 4: (56, 56, 24), 5: (18, 18, 9), 6: (18, 18, 9), 7: (27, 18, 27),
     8: (9, 9, 9), 9: (9, 9, 9), 10: (36, 36, 36), 11: (36, 36, 36), 12: (56, 56, 56), 13: (112, 112, 112), 14: (36, 36, 36),
     16: (36, 9, 36), 17: (36, 9, 36)}
+X448_ONE_SCALAR = 1     # ncg_x448_batch flag: one secret for every row
+ED448_ONE_SCALAR = 1    # ncg_ed448_mul_batch flag: one scalar for every row
+# ncg_fe448_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/ed448.hpp)
+FE448_CHECK_WORDS = {0: (16, 16, 16), 1: (16, 0, 16), 2: (16, 16, 48), 3: (16, 16, 16), 4: (16, 0, 14), 5: (14, 0, 16), 6: (16, 0, 16),
+                     7: (16, 0, 16), 8: (64, 16, 64), 9: (48, 48, 48), 10: (48, 0, 48)}
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -147,6 +152,25 @@ _OPTIONAL_PROTOS = {
     "ncg_x25519_base_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ed25519_to_montgomery_batch": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ed25519_to_montgomery_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_x448_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_x448_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_x448_base_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_x448_base_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_decode_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_encode_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed448_encode_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_add_pairs_batch": [_vp, _sz, _vp, _vp, _i32, _vp],
+    "ncg_ed448_add_pairs_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_ed448_mul_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_ed448_mul_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_ed448_mul_base_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed448_mul_base_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_to_montgomery_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_to_montgomery_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_verify_batch": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_verify_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_fe448_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
     "ncg_ristretto_decode_batch": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ristretto_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ristretto_encode_batch": [_vp, _sz, _vp, _vp],
@@ -633,6 +657,116 @@ class Engine:
         if n:
             self._check(self.lib.ncg_ed25519_to_montgomery_batch(self.h, n, pks.ctypes.data, out.ctypes.data, ok.ctypes.data))
         return out, ok.astype(bool)
+
+    # ---- X448 / Ed448: field elements and scalars uint8 [n, 56], encodings [n, 57], signatures [n, 114], affine points [n, 112];
+    # a refused row is zero with ok False -------------------------------------------------------------------------------------
+    def _rows(self, a, width):
+        return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, width)
+
+    def x448_batch(self, scalars, us, one_scalar=False):
+        """x448.scalarMult per row: scalars [n, 56] raw (clamped by the library), or ONE row with one_scalar; us [n, 56]."""
+        us, scalars = self._rows(us, 56), self._rows(scalars, 56)
+        n = us.shape[0]
+        if scalars.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of scalars and u coordinates must have equal length")
+        out, ok = np.zeros((n, 56), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_x448_batch(self.h, n, scalars.ctypes.data, us.ctypes.data, X448_ONE_SCALAR if one_scalar else 0,
+                                                out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def x448_base_batch(self, scalars):
+        """x448.getPublicKey per row"""
+        scalars = self._rows(scalars, 56)
+        n = scalars.shape[0]
+        out, ok = np.zeros((n, 56), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_x448_base_batch(self.h, n, scalars.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ed448_decode_batch(self, enc):
+        """ed448 Point.fromBytes (strict) per row -> (x || y [n, 112], ok bool [n])"""
+        enc = self._rows(enc, 57)
+        n = enc.shape[0]
+        out, ok = np.zeros((n, 112), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_decode_batch(self.h, n, enc.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ed448_encode_batch(self, affine):
+        """Point.toBytes of affine points [n, 112] -> [n, 57]"""
+        affine = self._rows(affine, 112)
+        n = affine.shape[0]
+        out = np.zeros((n, 57), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_encode_batch(self.h, n, affine.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed448_add_pairs_batch(self, a, b, subtract=False):
+        """Point.add / Point.subtract of affine points [n, 112] -> [n, 112]"""
+        a, b = self._rows(a, 112), self._rows(b, 112)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("arrays of points must have equal length")
+        out = np.zeros((n, 112), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_add_pairs_batch(self.h, n, a.ctypes.data, b.ctypes.data, 1 if subtract else 0, out.ctypes.data))
+        return out
+
+    def ed448_mul_batch(self, enc, ks, one_scalar=False):
+        """fromBytes(enc).multiplyUnsafe(k).toBytes() per row: enc [n, 57], ks [n, 56] (or ONE row) -> ([n, 57], ok bool [n])"""
+        enc, ks = self._rows(enc, 57), self._rows(ks, 56)
+        n = enc.shape[0]
+        if ks.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of points and scalars must have equal length")
+        out, ok = np.zeros((n, 57), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_mul_batch(self.h, n, enc.ctypes.data, ks.ctypes.data, ED448_ONE_SCALAR if one_scalar else 0,
+                                                     out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ed448_mul_base_batch(self, ks):
+        """BASE.multiplyUnsafe(k).toBytes() per row: ks [n, 56] -> [n, 57]"""
+        ks = self._rows(ks, 56)
+        n = ks.shape[0]
+        out = np.zeros((n, 57), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_mul_base_batch(self.h, n, ks.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed448_to_montgomery_batch(self, pks):
+        """ed448.utils.toMontgomery per row: [n, 57] -> ([n, 56], ok bool [n])"""
+        pks = self._rows(pks, 57)
+        n = pks.shape[0]
+        out, ok = np.zeros((n, 56), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_to_montgomery_batch(self.h, n, pks.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ed448_verify_batch(self, sigs, pks, ks):
+        """ed448 verify (strict, cofactored) with the challenges given: sigs [n, 114], pks [n, 57], ks [n, 56] -> bool [n]"""
+        sigs, pks, ks = self._rows(sigs, 114), self._rows(pks, 57), self._rows(ks, 56)
+        n = sigs.shape[0]
+        if pks.shape[0] != n or ks.shape[0] != n:
+            raise ValueError("arrays of signatures, public keys and challenges must have equal length")
+        ok = np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_verify_batch(self.h, n, sigs.ctypes.data, pks.ctypes.data, ks.ctypes.data, ok.ctypes.data))
+        return ok.astype(bool)
+
+    def fe448_check(self, op, variant, a_words, b_words):
+        """The lane code of GF(2^448 - 2^224 - 1), X448 and Ed448 on raw uint32 rows (ncg_fe448_check; FE448_CHECK_WORDS has the
+        widths): a [n, wa], b [n, wb] (any array where wb = 0) -> [n, wo]; an unknown op gives [n, 16] zeros."""
+        wa, wb, wo = FE448_CHECK_WORDS.get(op, (0, 0, 16))
+        a = np.ascontiguousarray(a_words, dtype=np.uint32)
+        b = np.ascontiguousarray(b_words, dtype=np.uint32)
+        n = a.shape[0]
+        if (wa and a.shape[1] != wa) or (wb and (b.shape[0] != n or b.shape[1] != wb)):
+            raise ValueError("fe448_check: op %d takes rows of %d and %d words" % (op, wa, wb))
+        out = np.zeros((n, wo), dtype=np.uint32)
+        if n:
+            self._check(self.lib.ncg_fe448_check(self.h, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
 
     # ---- ristretto255: encodings and scalars uint8 [n, 32], Edwards representatives (ed25519 wire points) [n, 64] ------------
     def ristretto_decode_batch(self, enc):

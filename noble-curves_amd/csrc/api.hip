@@ -1760,6 +1760,139 @@ int ncg_ed25519_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk32, vo
   return hc.finish(ncg_ed25519_to_montgomery_batch_dev(ctx, n, hc.dev(pk), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
+// ---- X448 and Ed448 (ed448.hip).  56-byte rows (scalars, u coordinates, the halves of an affine point) are read as 14 LE words: a
+// device pointer to them must be 4-byte aligned and is refused otherwise; encodings (57 bytes) and signatures (114) are packed and
+// read byte by byte.  The host forms stage every buffer at a 256-byte boundary, so host memory may sit at any address.
+static Rule ed448_rule(ncg_ctx* ctx, const char* op, int flags, int known_flags, std::initializer_list<const void*> word_rows) {
+  int rc = NCG_OK;
+  if (flags & ~known_flags) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
+  else
+    for (const void* p : word_rows)
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: 56-byte rows must be 4-byte aligned", op);
+  return {op, rc};
+}
+static Rule ed448_flags_rule(ncg_ctx* ctx, const char* op, int flags, int known_flags) { return ed448_rule(ctx, op, flags, known_flags, {}); }
+
+int ncg_x448_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, const void* u_dev, int flags, void* out56_dev, uint8_t* out_ok_dev,
+                       void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "x448_batch", flags, NCG_X448_ONE_SCALAR, {scalars_dev, u_dev, out56_dev}), n, scalars_dev, u_dev, out56_dev,
+            out_ok_dev);
+  NCG_HIP(ctx, ncg::x448_batch((const uint32_t*)scalars_dev, (const uint32_t*)u_dev, flags & NCG_X448_ONE_SCALAR, (uint32_t*)out56_dev, out_ok_dev,
+                               (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_x448_batch(ncg_ctx* ctx, size_t n, const void* scalars, const void* u, int flags, void* out56, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed448_flags_rule(ctx, "x448_batch", flags, NCG_X448_ONE_SCALAR), n, scalars, u, out56, out_ok);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, (flags & NCG_X448_ONE_SCALAR) ? 56 : n * 56), du = hc.in(u, n * 56);
+  const int o = hc.out(out56, n * 56), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_x448_batch_dev(ctx, n, hc.dev(sc), hc.dev(du), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_x448_base_batch_dev(ncg_ctx* ctx, size_t n, const void* scalars_dev, void* out56_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "x448_base_batch", 0, 0, {scalars_dev, out56_dev}), n, scalars_dev, out56_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::x448_batch((const uint32_t*)scalars_dev, nullptr, 0, (uint32_t*)out56_dev, out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_x448_base_batch(ncg_ctx* ctx, size_t n, const void* scalars, void* out56, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("x448_base_batch"), n, scalars, out56, out_ok);
+  HostCall hc(ctx);
+  const int sc = hc.in(scalars, n * 56), o = hc.out(out56, n * 56), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_x448_base_batch_dev(ctx, n, hc.dev(sc), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ed448_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc57_dev, void* out_affine112_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_decode_batch", 0, 0, {out_affine112_dev}), n, enc57_dev, out_affine112_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ed448_decode_batch((const uint8_t*)enc57_dev, (uint32_t*)out_affine112_dev, out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_decode_batch(ncg_ctx* ctx, size_t n, const void* enc57, void* out_affine112, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("ed448_decode_batch"), n, enc57, out_affine112, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc57, n * 57), o = hc.out(out_affine112, n * 112), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_decode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ed448_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine112_dev, void* out57_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_encode_batch", 0, 0, {affine112_dev}), n, affine112_dev, out57_dev);
+  NCG_HIP(ctx, ncg::ed448_encode_batch((const uint32_t*)affine112_dev, (uint8_t*)out57_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_encode_batch(ncg_ctx* ctx, size_t n, const void* affine112, void* out57) {
+  NCG_BEGIN(ctx, no_rule("ed448_encode_batch"), n, affine112, out57);
+  HostCall hc(ctx);
+  const int in = hc.in(affine112, n * 112), o = hc.out(out57, n * 57);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_encode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), ctx->stream));
+}
+int ncg_ed448_add_pairs_batch_dev(ncg_ctx* ctx, size_t n, const void* a112_dev, const void* b112_dev, int subtract, void* out112_dev,
+                                  void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_add_pairs_batch", 0, 0, {a112_dev, b112_dev, out112_dev}), n, a112_dev, b112_dev, out112_dev);
+  NCG_HIP(ctx, ncg::ed448_add_pairs_batch((const uint32_t*)a112_dev, (const uint32_t*)b112_dev, subtract != 0, (uint32_t*)out112_dev, (int)n,
+                                          stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_add_pairs_batch(ncg_ctx* ctx, size_t n, const void* a112, const void* b112, int subtract, void* out112) {
+  NCG_BEGIN(ctx, no_rule("ed448_add_pairs_batch"), n, a112, b112, out112);
+  HostCall hc(ctx);
+  const int da = hc.in(a112, n * 112), db = hc.in(b112, n * 112), o = hc.out(out112, n * 112);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_add_pairs_batch_dev(ctx, n, hc.dev(da), hc.dev(db), subtract, hc.dev(o), ctx->stream));
+}
+int ncg_ed448_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc57_dev, const void* k56_dev, int flags, void* out57_dev, uint8_t* out_ok_dev,
+                            void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_mul_batch", flags, NCG_ED448_ONE_SCALAR, {k56_dev}), n, enc57_dev, k56_dev, out57_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ed448_mul_batch((const uint8_t*)enc57_dev, (const uint32_t*)k56_dev, flags & NCG_ED448_ONE_SCALAR, (uint8_t*)out57_dev,
+                                    out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_mul_batch(ncg_ctx* ctx, size_t n, const void* enc57, const void* k56, int flags, void* out57, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed448_flags_rule(ctx, "ed448_mul_batch", flags, NCG_ED448_ONE_SCALAR), n, enc57, k56, out57, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc57, n * 57), k = hc.in(k56, (flags & NCG_ED448_ONE_SCALAR) ? 56 : n * 56);
+  const int o = hc.out(out57, n * 57), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_mul_batch_dev(ctx, n, hc.dev(in), hc.dev(k), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ed448_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* k56_dev, void* out57_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_mul_base_batch", 0, 0, {k56_dev}), n, k56_dev, out57_dev);
+  NCG_HIP(ctx, ncg::ed448_mul_batch(nullptr, (const uint32_t*)k56_dev, 0, (uint8_t*)out57_dev, nullptr, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_mul_base_batch(ncg_ctx* ctx, size_t n, const void* k56, void* out57) {
+  NCG_BEGIN(ctx, no_rule("ed448_mul_base_batch"), n, k56, out57);
+  HostCall hc(ctx);
+  const int k = hc.in(k56, n * 56), o = hc.out(out57, n * 57);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_mul_base_batch_dev(ctx, n, hc.dev(k), hc.dev(o), ctx->stream));
+}
+int ncg_ed448_to_montgomery_batch_dev(ncg_ctx* ctx, size_t n, const void* pk57_dev, void* out56_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_to_montgomery_batch", 0, 0, {out56_dev}), n, pk57_dev, out56_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ed448_to_montgomery_batch((const uint8_t*)pk57_dev, (uint32_t*)out56_dev, out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_to_montgomery_batch(ncg_ctx* ctx, size_t n, const void* pk57, void* out56, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("ed448_to_montgomery_batch"), n, pk57, out56, out_ok);
+  HostCall hc(ctx);
+  const int pk = hc.in(pk57, n * 57), o = hc.out(out56, n * 56), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_to_montgomery_batch_dev(ctx, n, hc.dev(pk), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_ed448_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, const void* k56_dev, uint8_t* out_ok_dev,
+                               void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "ed448_verify_batch", 0, 0, {k56_dev}), n, sig114_dev, pk57_dev, k56_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::ed448_verify_batch((const uint8_t*)sig114_dev, (const uint8_t*)pk57_dev, (const uint32_t*)k56_dev, out_ok_dev, (int)n,
+                                       stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const void* pk57, const void* k56, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("ed448_verify_batch"), n, sig114, pk57, k56, out_ok);
+  HostCall hc(ctx);
+  const int sig = hc.in(sig114, n * 114), pk = hc.in(pk57, n * 57), k = hc.in(k56, n * 56), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_verify_batch_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(k), hc.dev<uint8_t>(ok), ctx->stream));
+}
+
 // ---- ristretto255 (ristretto.hip).  Encodings and scalars are rows of 32 bytes read as 8 LE words, Edwards representatives are
 // ed25519 wire points.  The _dev forms keep what lies between their kernels in ctx->rist_ws, never in ctx->scratch.
 static int ensure_rist_ws(ncg_ctx* ctx, size_t bytes, hipStream_t st) {
@@ -2057,6 +2190,23 @@ int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, cons
   if (int rc = hc.stage()) return rc;
   NCG_HIP(ctx, ncg::field_check_run(field, op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n,
                                     ctx->stream));
+  return hc.finish(NCG_OK);
+}
+
+// The pieces of fe448.hpp / ed448.hpp on raw limbs.  Its own entry point: the table of ncg_field_check is closed.  An op nobody
+// defines reads nothing and leaves rows of 16 zero words.
+int ncg_fe448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out) {
+  const Rule rule = {"fe448_check", !ctx || n <= (1u << 24) ? NCG_OK
+                                        : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: fe448_check: batch too large (max 2^24)")};
+  NCG_BEGIN(ctx, rule, n, a, b, out);
+  int wa, wb, wo;
+  ncg::fe448_check_row_words(op, &wa, &wb, &wo);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * wa * 4), db = hc.in(b, n * wb * 4);
+  const int o = hc.out(out, n * (wo ? wo : 16) * 4, true);
+  if (int rc = hc.stage()) return rc;
+  if (wo)
+    NCG_HIP(ctx, ncg::fe448_check(op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, ctx->stream));
   return hc.finish(NCG_OK);
 }
 

@@ -200,6 +200,28 @@ void x25519_base_host(const uint32_t* scalars, uint32_t* out, uint8_t* out_ok, i
 void ed25519_to_montgomery_host(const uint32_t* pk, uint32_t* out, uint8_t* out_ok, int n);
 int x25519_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// X448 and Ed448 (ed448.hip).  56-byte rows are 14 LE words; encodings (57 bytes), signatures (114) are packed bytes; affine points
+// are x || y, 28 words.  out_ok = 0 and a zero row where the reference throws.  u = NULL (x448_batch) / enc = NULL (ed448_mul_batch):
+// the base point.  one_scalar: one row of `scalars` / `k` for every item.
+hipError_t x448_batch(const uint32_t* scalars, const uint32_t* u, int one_scalar, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+hipError_t ed448_decode_batch(const uint8_t* enc, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+hipError_t ed448_encode_batch(const uint32_t* affine, uint8_t* out, int n, hipStream_t st);
+hipError_t ed448_add_pairs_batch(const uint32_t* a, const uint32_t* b, int subtract, uint32_t* out, int n, hipStream_t st);
+hipError_t ed448_mul_batch(const uint8_t* enc, const uint32_t* k, int one_scalar, uint8_t* out, uint8_t* out_ok, int n, hipStream_t st);
+hipError_t ed448_to_montgomery_batch(const uint8_t* pk, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+hipError_t ed448_verify_batch(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, uint8_t* out_ok, int n, hipStream_t st);
+// the pieces of fe448.hpp / ed448.hpp on raw limbs (ncg_fe448_check); words per row of each op: fe448_check_row_words (0 = unknown op)
+void fe448_check_row_words(int op, int* wa, int* wb, int* wo);
+hipError_t fe448_check(int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st);
+void x448_host(const uint32_t* scalars, const uint32_t* u, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
+void ed448_decode_host(const uint8_t* enc, uint32_t* out, uint8_t* out_ok, int n);
+void ed448_encode_host(const uint32_t* affine, uint8_t* out, int n);
+void ed448_add_pairs_host(const uint32_t* a, const uint32_t* b, int subtract, uint32_t* out, int n);
+void ed448_mul_host(const uint8_t* enc, const uint32_t* k, int one_scalar, uint8_t* out, uint8_t* out_ok, int n);
+void ed448_to_montgomery_host(const uint8_t* pk, uint32_t* out, uint8_t* out_ok, int n);
+void ed448_verify_host(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, uint8_t* out_ok, int n);
+int fe448_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 // ristretto255 (ristretto.hip): encodings and scalars are rows of 8 LE words, Edwards representatives ed25519 wire points (16
 // words), uniform input 16 words.  A rejected encoding gives out_ok = 0 and a zero row - or the identity (0, 1) with
 // identity_on_reject, for a caller that multiplies what comes out.  ristretto_encode_proj_batch takes the (X, Y, Z) rows of

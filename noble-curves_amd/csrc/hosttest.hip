@@ -25,6 +25,7 @@
 #include "x25519.hip"
 #include "ristretto.hip"
 #include "pairing.hip"
+#include "ed448.hip"
 
 using namespace ncg;
 
@@ -283,6 +284,42 @@ int ht_ed25519_to_montgomery(const uint32_t* pk, uint32_t* out, uint8_t* ok, int
   return 0;
 }
 int ht_x25519_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return x25519_check_host(op, variant, a, b, out); }
+
+// X448 and Ed448 on the CPU twins of ed448.hip: 56-byte rows as 14 LE words, encodings 57 packed bytes, signatures 114, affine
+// points 28 words; flags as ncg_x448_batch / ncg_ed448_mul_batch.  u = NULL / enc = NULL: the base point.  ht_fe448_op: one row of
+// ncg_fe448_check, -1 for an unknown op; ht_fe448_widths: its words per row.
+int ht_x448(const uint32_t* scalars, const uint32_t* u, int flags, uint32_t* out, uint8_t* ok, int n) {
+  if (flags & ~1) return -1;
+  x448_host(scalars, u, flags & 1, out, ok, n);
+  return 0;
+}
+int ht_ed448_decode(const uint8_t* enc, uint32_t* out, uint8_t* ok, int n) {
+  ed448_decode_host(enc, out, ok, n);
+  return 0;
+}
+int ht_ed448_encode(const uint32_t* affine, uint8_t* out, int n) {
+  ed448_encode_host(affine, out, n);
+  return 0;
+}
+int ht_ed448_add_pairs(const uint32_t* a, const uint32_t* b, int subtract, uint32_t* out, int n) {
+  ed448_add_pairs_host(a, b, subtract, out, n);
+  return 0;
+}
+int ht_ed448_mul(const uint8_t* enc, const uint32_t* k, int flags, uint8_t* out, uint8_t* ok, int n) {
+  if (flags & ~1) return -1;
+  ed448_mul_host(enc, k, flags & 1, out, ok, n);
+  return 0;
+}
+int ht_ed448_to_montgomery(const uint8_t* pk, uint32_t* out, uint8_t* ok, int n) {
+  ed448_to_montgomery_host(pk, out, ok, n);
+  return 0;
+}
+int ht_ed448_verify(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, uint8_t* ok, int n) {
+  ed448_verify_host(sig, pk, k, ok, n);
+  return 0;
+}
+int ht_fe448_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return fe448_check_host(op, variant, a, b, out); }
+void ht_fe448_widths(int op, int* wa, int* wb, int* wo) { fe448_check_row_words(op, wa, wb, wo); }
 
 // ristretto255 on the CPU twins of ristretto.hip: encodings and scalars 8 LE words per row, Edwards representatives 16, uniform
 // bytes 16; flags as ncg_ristretto_mul_batch.  ht_ristretto_encode_proj: X Y Z as wire words (24 per row).  ht_ristretto_op: the

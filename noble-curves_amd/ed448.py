@@ -1,0 +1,296 @@
+"""Ed448 / X448 host shim with the reference's call shapes, checks, check order and messages (src/ed448.ts over
+src/abstract/montgomery.ts and src/abstract/edwards.ts).
+
+`x448`: scalarMult / getSharedSecret / getPublicKey and their `_batch` forms (`ncg_x448_batch`, `ncg_x448_base_batch`): the
+u coordinate (the peer's key) is checked before the scalar (montgomery.ts:324-326); clamping, the reduction of u mod p, the
+low-order test and the 448-step ladder run in HIP kernels.  `_batch` forms return (list of bytes-or-None, list of bool), None
+where the reference throws 'invalid private or public key received'; `scalars` may be ONE bytes value against many peers.
+
+`ed448` / `ed448ph`: verify / verify_batch (`ncg_ed448_verify_batch`), getPublicKey[_batch], utils.toMontgomery[_batch] and
+utils.toMontgomerySecret.  HASHING STAYS ON THE HOST: the challenge k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114)
+mod n, the prehash of ed448ph and the SHAKE256 of getPublicKey are hashlib.shake_256 here; the decoding of A and R, the
+small-order test, s < n and the cofactored equation run on the device.  `zip215=True` is not supported.
+
+`ed448_Point`: fromBytes_batch / toBytes_batch / multiplyUnsafe_batch / multiplyBase_batch / add_batch on encodings, with the
+range errors of multiply / multiplyUnsafe raised here.
+
+Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), decaf448 and its hasher,
+`ed448_hasher` (hash-to-curve), FROST and OPRF suites, signing, an MSM over Ed448, and a fixed-base table (multiplyBase runs the
+variable-base kernel on the base point).
+"""
+import hashlib
+
+import numpy as np
+
+from ._native import get_engine
+
+P = 2**448 - 2**224 - 1
+N = 2**446 - 13818066809895115352007386748515426880336692474882178609894547503885
+_D = P - 39081
+INVALID = "invalid private or public key received"
+LOW_ORDER_U = frozenset((0, 1, P - 1))                   # montgomery.ts:303-313
+# ED448_TORSION_SUBGROUP (ed448.ts:738-743): the hex encodings of the four points of order 1, 2, 4, 4
+ED448_TORSION_SUBGROUP = tuple(b.hex() for b in ((1).to_bytes(57, "little"), (P - 1).to_bytes(57, "little"), bytes(57), bytes(56) + b"\x80"))
+
+
+def _abytes(b, length, title):
+    """utils abytes(value, length, title) with the reference's wording, the type named as JavaScript's typeof names it"""
+    if not isinstance(b, (bytes, bytearray, memoryview, np.ndarray)):
+        kind = "string" if isinstance(b, str) else "boolean" if isinstance(b, bool) else "number" if isinstance(b, (int, float)) else "object"
+        raise TypeError('"%s" expected Uint8Array%s, got type=%s' % (title, "" if length is None else " of length %d" % length, kind))
+    b = bytes(b)
+    if length is not None and len(b) != length:
+        raise ValueError('"%s" expected Uint8Array of length %d, got length=%d' % (title, length, len(b)))
+    return b
+
+
+def _result(out, ok):
+    ok = [bool(x) for x in ok]
+    return [out[i].tobytes() if ok[i] else None for i in range(len(ok))], ok
+
+
+def _rows(items, width, title):
+    out = np.zeros((len(items), width), np.uint8)
+    for i, b in enumerate(items):
+        out[i] = np.frombuffer(_abytes(b, width, title), np.uint8)
+    return out
+
+
+def _adjust(b):
+    """adjustScalarBytes (ed448.ts:122-130) on 56 or 57 bytes"""
+    b = bytearray(b)
+    b[0] &= 252
+    b[55] |= 128
+    if len(b) > 56:
+        b[56] = 0
+    return bytes(b)
+
+
+class x448:
+    """x448 of src/ed448.ts:284-311"""
+    GuBytes = (5).to_bytes(56, "little")
+
+    @staticmethod
+    def scalarMult_batch(scalars, us, engine=None):
+        """x448.scalarMult for every (scalar, u) pair.  `scalars` may be ONE bytes value: that secret against every u."""
+        one = isinstance(scalars, (bytes, bytearray, memoryview))
+        if not one and len(scalars) != len(us):
+            raise ValueError("arrays of scalars and u coordinates must have equal length")
+        U = np.zeros((len(us), 56), np.uint8)
+        S = np.zeros((1 if one else len(us), 56), np.uint8)
+        for i in range(len(us)):   # row by row, the u coordinate first (montgomery.ts:324-326)
+            U[i] = np.frombuffer(_abytes(us[i], 56, "uCoordinate"), np.uint8)
+            if not one:
+                S[i] = np.frombuffer(_abytes(scalars[i], 56, "scalar"), np.uint8)
+        if one:
+            S[0] = np.frombuffer(_abytes(scalars, 56, "scalar"), np.uint8)
+        return _result(*(engine or get_engine()).x448_batch(S, U, one_scalar=one))
+
+    @staticmethod
+    def getSharedSecret_batch(secretKeys, publicKeys, engine=None):
+        return x448.scalarMult_batch(secretKeys, publicKeys, engine)
+
+    @staticmethod
+    def getPublicKey_batch(secretKeys, engine=None):
+        return _result(*(engine or get_engine()).x448_base_batch(_rows(secretKeys, 56, "scalar")))
+
+    @staticmethod
+    def scalarMult(scalar, u, engine=None):
+        """a batch of one, with the reference's errors in the reference's order"""
+        u = _abytes(u, 56, "uCoordinate")
+        if int.from_bytes(u, "little") % P in LOW_ORDER_U:
+            raise ValueError(INVALID)
+        out, ok = x448.scalarMult_batch([_abytes(scalar, 56, "scalar")], [u], engine)
+        if not ok[0]:
+            raise ValueError(INVALID)
+        return out[0]
+
+    @staticmethod
+    def getSharedSecret(secretKey, publicKey, engine=None):
+        return x448.scalarMult(secretKey, publicKey, engine)
+
+    @staticmethod
+    def getPublicKey(secretKey, engine=None):
+        out, ok = x448.getPublicKey_batch([secretKey], engine)
+        if not ok[0]:
+            raise ValueError(INVALID)
+        return out[0]
+
+
+def _dom4(data, ctx, phflag):
+    """ed448.ts:190-201"""
+    if len(ctx) > 255:
+        raise ValueError("context must be smaller than 255, got: %d" % len(ctx))
+    return b"SigEd448" + bytes([1 if phflag else 0, len(ctx)]) + ctx + data
+
+
+def _decode_error(enc):
+    """the message of the error Point.fromBytes throws for an encoding the device refused (rare path: host integers), or None"""
+    y = int.from_bytes(enc[:56] + bytes([enc[56] & 0x7f]), "little")
+    if y >= P:
+        return "expected valid point.y: 0 <= n < %d, got %d" % (P, y)
+    u, v = (y * y - 1) % P, (_D * y * y - 1) % P
+    x2 = u * pow(v, P - 2, P) % P
+    if x2 and pow(x2, (P - 1) // 2, P) != 1:
+        return "bad point: invalid y coordinate"
+    if x2 == 0 and enc[56] & 0x80:
+        return "bad point: x=0 and x_0=1"
+    return None
+
+
+class _Utils:
+    @staticmethod
+    def toMontgomery_batch(publicKeys, engine=None):
+        """u = y^2 / x^2 of Point.fromBytes(publicKey) for every key (`ncg_ed448_to_montgomery_batch`)"""
+        return _result(*(engine or get_engine()).ed448_to_montgomery_batch(_rows(publicKeys, 57, "point")))
+
+    @staticmethod
+    def toMontgomery(publicKey, engine=None):
+        out, ok = _Utils.toMontgomery_batch([publicKey], engine)
+        if not ok[0]:
+            raise ValueError(_decode_error(_abytes(publicKey, 57, "point")) or "invert: expected non-zero number")
+        return out[0]
+
+    @staticmethod
+    def toMontgomerySecret(secretKey):
+        """ed448.ts:181-188: the clamped first 56 bytes of SHAKE256(secretKey, 114), on the host"""
+        if not isinstance(secretKey, (bytes, bytearray, memoryview, np.ndarray)):
+            raise TypeError("expected Uint8Array of length 57, got type=%s" % type(secretKey).__name__)
+        if len(bytes(secretKey)) != 57:
+            raise ValueError("expected Uint8Array of length 57, got length=%d" % len(bytes(secretKey)))
+        return _adjust(hashlib.shake_256(bytes(secretKey)).digest(114)[:57])[:56]
+
+
+class _EdDSA:
+    """ed4(opts) of ed448.ts:206-215: `prehash` False = ed448, True = ed448ph"""
+    utils = _Utils
+
+    def __init__(self, prehash):
+        self.prehash = prehash
+
+    def challenge(self, r_bytes, pk_bytes, msg, context=b""):
+        """hashDomainToScalar (edwards.ts:900-906) of an already prehashed message, reduced mod n"""
+        return int.from_bytes(hashlib.shake_256(_dom4(bytes(r_bytes) + bytes(pk_bytes) + bytes(msg), context, self.prehash)).digest(114),
+                              "little") % N
+
+    def verify_batch(self, sigs, msgs, publicKeys, context=b"", zip215=False, engine=None):
+        """list of bool, one per (signature, message, publicKey) triple, all under one context"""
+        n = len(sigs)
+        if len(msgs) != n or len(publicKeys) != n:
+            raise ValueError("arrays of signatures, messages and public keys must have equal length")
+        if not isinstance(zip215, bool):
+            raise TypeError('"zip215" expected boolean')
+        if zip215:
+            raise ValueError("ed448: zip215 is not supported")
+        context = _abytes(context, None, "context")
+        long_context = len(context) > 255
+        S, A, K = np.zeros((n, 114), np.uint8), np.zeros((n, 57), np.uint8), np.zeros((n, 56), np.uint8)
+        for i in range(n):
+            sig = _abytes(sigs[i], 114, "signature")
+            msg = _abytes(msgs[i], None, "message")
+            pk = _abytes(publicKeys[i], 57, "publicKey")
+            if self.prehash:
+                msg = hashlib.shake_256(msg).digest(64)
+            S[i], A[i] = np.frombuffer(sig, np.uint8), np.frombuffer(pk, np.uint8)
+            if long_context:
+                # edwards.ts:964-984: dom4 refuses the context only for a row that got past the decoding of A and R, s < n and the
+                # small-order test; every other row is False without the context being looked at (rare path: host integers)
+                if (_decode_error(pk) is None and _decode_error(sig[:57]) is None and int.from_bytes(sig[57:], "little") < N
+                        and pk.hex() not in ED448_TORSION_SUBGROUP):
+                    _dom4(b"", context, self.prehash)
+                continue
+            K[i] = np.frombuffer(self.challenge(sig[:57], pk, msg, context).to_bytes(56, "little"), np.uint8)
+        if long_context:
+            return [False] * n
+        return [bool(x) for x in (engine or get_engine()).ed448_verify_batch(S, A, K)]
+
+    def verify(self, sig, msg, publicKey, context=b"", zip215=False, engine=None):
+        """eddsa.verify (edwards.ts:942): one signature = a batch of one"""
+        return self.verify_batch([sig], [msg], [publicKey], context, zip215, engine)[0]
+
+    def getPublicKey_batch(self, secretKeys, engine=None):
+        """getExtendedPublicKey(secretKey).pointBytes (edwards.ts:871-897): SHAKE256 on the host, [scalar]B on the device"""
+        K = np.zeros((len(secretKeys), 56), np.uint8)
+        for i, sk in enumerate(secretKeys):
+            head = _adjust(hashlib.shake_256(_abytes(sk, 57, "secretKey")).digest(114)[:57])
+            K[i] = np.frombuffer(head[:56], np.uint8)
+        out = (engine or get_engine()).ed448_mul_base_batch(K)
+        return [out[i].tobytes() for i in range(len(secretKeys))]
+
+    def getPublicKey(self, secretKey, engine=None):
+        return self.getPublicKey_batch([secretKey], engine)[0]
+
+
+ed448 = _EdDSA(False)
+ed448ph = _EdDSA(True)
+
+
+class ed448_Point:
+    """batch forms of the reference's ed448.Point on ENCODINGS (57 bytes)"""
+
+    @staticmethod
+    def fromBytes_batch(encodings, engine=None):
+        """Point.fromBytes (strict) per row -> (list of (x, y) or None, list of bool)"""
+        out, ok = (engine or get_engine()).ed448_decode_batch(_rows(encodings, 57, "point"))
+        pts = [(int.from_bytes(out[i, :56].tobytes(), "little"), int.from_bytes(out[i, 56:].tobytes(), "little")) if ok[i] else None
+               for i in range(len(ok))]
+        return pts, [bool(x) for x in ok]
+
+    @staticmethod
+    def fromBytes(encoding, engine=None):
+        pts, ok = ed448_Point.fromBytes_batch([encoding], engine)
+        if not ok[0]:
+            raise ValueError(_decode_error(bytes(encoding)))
+        return pts[0]
+
+    @staticmethod
+    def toBytes_batch(points, engine=None):
+        """Point.toBytes of affine (x, y) pairs"""
+        A = np.zeros((len(points), 112), np.uint8)
+        for i, (x, y) in enumerate(points):
+            A[i] = np.frombuffer(int(x).to_bytes(56, "little") + int(y).to_bytes(56, "little"), np.uint8)
+        out = (engine or get_engine()).ed448_encode_batch(A)
+        return [out[i].tobytes() for i in range(len(points))]
+
+    @staticmethod
+    def _scalars(scalars, lo, what):
+        K = np.zeros((len(scalars), 56), np.uint8)
+        for i, k in enumerate(scalars):
+            if not isinstance(k, int) or isinstance(k, bool) or not lo <= k < N:
+                raise ValueError("invalid scalar: expected %s" % what)
+            K[i] = np.frombuffer(k.to_bytes(56, "little"), np.uint8)
+        return K
+
+    @staticmethod
+    def multiplyUnsafe_batch(encodings, scalars, engine=None):
+        """fromBytes(enc).multiplyUnsafe(k).toBytes() per row; `scalars` a list, or ONE int for every row"""
+        one = isinstance(scalars, int)
+        if not one and len(scalars) != len(encodings):
+            raise ValueError("arrays of points and scalars must have equal length")
+        K = ed448_Point._scalars([scalars] if one else scalars, 0, "0 <= sc < curve.n")
+        return _result(*(engine or get_engine()).ed448_mul_batch(_rows(encodings, 57, "point"), K, one_scalar=one))
+
+    @staticmethod
+    def multiply_batch(encodings, scalars, engine=None):
+        """Point.multiply: the same products, the scalar range 1 <= sc < curve.n"""
+        ed448_Point._scalars([scalars] if isinstance(scalars, int) else scalars, 1, "1 <= sc < curve.n")
+        return ed448_Point.multiplyUnsafe_batch(encodings, scalars, engine)
+
+    @staticmethod
+    def multiplyBase_batch(scalars, engine=None):
+        """BASE.multiply(k).toBytes() per row"""
+        out = (engine or get_engine()).ed448_mul_base_batch(ed448_Point._scalars(scalars, 1, "1 <= sc < curve.n"))
+        return [out[i].tobytes() for i in range(len(scalars))]
+
+    @staticmethod
+    def add_batch(a_encodings, b_encodings, subtract=False, engine=None):
+        """fromBytes(a).add(fromBytes(b)).toBytes() per row (subtract: .subtract); None where either encoding is refused"""
+        if len(a_encodings) != len(b_encodings):
+            raise ValueError("arrays of points must have equal length")
+        eng = engine or get_engine()
+        pa, oka = eng.ed448_decode_batch(_rows(a_encodings, 57, "point"))
+        pb, okb = eng.ed448_decode_batch(_rows(b_encodings, 57, "point"))
+        pb[~np.asarray(okb, bool), 56] = 1        # a refused row becomes the identity (0, 1) so that the addition stays on the curve
+        pa[~np.asarray(oka, bool), 56] = 1
+        out = eng.ed448_encode_batch(eng.ed448_add_pairs_batch(pa, pb, subtract))
+        return _result(out, np.asarray(oka, bool) & np.asarray(okb, bool))
