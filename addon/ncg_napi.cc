@@ -17,6 +17,10 @@
 //                                                       3 deriveToCurve (a: n x 64) -> n x 32, 4 multiply (a: n x 32 encodings, b: n or ONE
 //                                                       scalar row) -> n x 32 + n ok flags, 5 BASE.multiply (a: n x 32 scalars) -> n x 32,
 //                                                       6 msm (a: encodings, b: scalars) -> 32 bytes; throws naming a bad index
+//   decaf448(mode, a, b | null)                    -> decaf448 on packed rows; mode 0 decode (a: n x 56) -> n x 112 points + n ok flags,
+//                                                       1 encode (a: n x 112) -> n x 56, 2 equals (a, b: n x 112) -> n flags,
+//                                                       3 deriveToCurve (a: n x 112) -> n x 56, 4 multiply (a: n x 56 encodings, b: n or ONE
+//                                                       scalar row) -> n x 56 + n ok flags, 5 BASE.multiply (a: n x 56 scalars) -> n x 56
 //   decodePoints(curveId, encoded, zip215: bool)     -> Uint8Array n * (PB + 2)  (points, ok flags, inf flags)
 //   encodePoints(curveId, points)                    -> Uint8Array n * (EB + 1)  (encodings, ok flags)
 //   aggregateEncoded(curveId, encoded, zip215)       -> Uint8Array PB + 1 (flag); throws naming a bad index
@@ -335,6 +339,41 @@ static napi_value Ristretto(napi_env env, napi_callback_info info) {
   else if (mode == 3) rc = ncg_ristretto_from_uniform_batch(g_ctx, n, a, out, nullptr);
   else if (mode == 4) rc = ncg_ristretto_mul_batch(g_ctx, n, a, b, bl != al ? NCG_RISTRETTO_ONE_SCALAR : 0, out, out + n * 32);
   else rc = ncg_ristretto_mul_base_batch(g_ctx, n, a, out);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
+// decaf448 on packed rows (ncg_decaf448_*): one entry, the operation chosen by `mode` (see the list at the top of this file).
+static napi_value Decaf448(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  static const size_t in_row[6] = {56, 112, 112, 112, 56, 56}, out_row[6] = {113, 56, 1, 56, 57, 56};
+  int32_t mode;
+  uint8_t *a, *b = nullptr, *out;
+  size_t al, bl = 0;
+  bool ok = argc >= 3 && napi_get_value_int32(env, argv[0], &mode) == napi_ok && mode >= 0 && mode <= 5 && get_u8(env, argv[1], &a, &al) &&
+            al % in_row[mode] == 0;
+  const bool two = ok && (mode == 2 || mode == 4);
+  if (two) ok = get_u8(env, argv[2], &b, &bl);
+  const size_t n = ok ? al / in_row[mode] : 0;
+  if (ok && mode == 2) ok = bl == al;
+  if (ok && mode == 4) ok = bl == al || bl == 56;
+  if (!ok) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: decaf448(mode, rows, rows | null)");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n * out_row[mode], &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (n == 0) rc = 0;
+  else if (mode == 0) rc = ncg_decaf448_decode_batch(g_ctx, n, a, out, out + n * 112);
+  else if (mode == 1) rc = ncg_decaf448_encode_batch(g_ctx, n, a, out);
+  else if (mode == 2) rc = ncg_decaf448_equals_batch(g_ctx, n, a, b, out);
+  else if (mode == 3) rc = ncg_decaf448_from_uniform_batch(g_ctx, n, a, out);
+  else if (mode == 4) rc = ncg_decaf448_mul_batch(g_ctx, n, a, b, bl != al ? NCG_DECAF448_ONE_SCALAR : 0, out, out + n * 56);
+  else rc = ncg_decaf448_mul_base_batch(g_ctx, n, a, out);
   if (rc != 0) return throw_native(env);
   return res;
 }
@@ -1023,7 +1062,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -13,6 +13,8 @@
 //   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
 //                                            BASE.multiply, an MSM from encodings and ristretto255_hasher.deriveToCurve
 //                                            (src/ed25519.ts:443-668), with single-item forms that throw the reference's messages
+//   decaf448FromBytesBatch(encodings) ...   - array forms of decaf448.Point.fromBytes / toBytes / equals / multiply / BASE.multiply
+//                                            and decaf448_hasher.deriveToCurve (src/ed448.ts:462-701)
 //   fftFr(values, opts)                    - FFT(roots, Fr).direct / .inverse (abstract/fft.ts:518-577)
 //   polyFr(opts)                           - poly(Fr, roots, ...) on arrays of bigint (abstract/fft.ts:583-926): add, sub, dot,
 //                                            mul, convolve, shift, eval, monomial.eval, lagrange.basis / eval
@@ -746,6 +748,58 @@ function ristrettoMultiply(encoding, k) {
 function ristrettoMultiplyBase(k) { return ristrettoMultiplyBaseBatch([k])[0]; }
 function ristrettoDeriveToCurve(bytes64) { return ristrettoDeriveToCurveBatch([bytes64])[0]; }
 
+// ---- decaf448 (src/ed448.ts:462-701, RFC 9496 section 5), with the argument conventions of the ristretto255 exports.  An element is
+// its 56-byte encoding on this side; fromBytes hands back the Edwards representative as a 112-byte Ed448 affine point (x || y).
+// Batch forms return null where the reference throws.
+function decafScalars(ks) {                       // Point.multiply: 1 <= k < n
+  const out = new Uint8Array(56 * ks.length);
+  ks.forEach((k, i) => {
+    if (typeof k !== 'bigint' || k < 1n || k >= ED448_N) throw new Error('invalid scalar: expected 1 <= sc < curve.n');
+    leBytes(k, 56, out, 56 * i);
+  });
+  return out;
+}
+function decaf448FromBytesBatch(encodings) {      // -> 112-byte affine representatives (x || y) or null
+  const n = encodings.length, E = ristrettoPack(encodings, 56);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.decaf448(0, E, null), n, 112, true);
+}
+function decaf448ToBytesBatch(points) {           // 112-byte affine points -> encodings
+  const n = points.length, A = ristrettoPack(points, 112);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.decaf448(1, A, null), n, 56, false);
+}
+function decaf448EqualsBatch(as, bs) {
+  if (as.length !== bs.length) throw new Error('arrays of points must have equal length');
+  const A = ristrettoPack(as, 112), B = ristrettoPack(bs, 112);
+  if (as.length === 0) return [];
+  init();
+  return Array.from(native.decaf448(2, A, B)).map((x) => x === 1);
+}
+function decaf448DeriveToCurveBatch(rows112) {
+  const n = rows112.length, A = ristrettoPack(rows112, 112);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.decaf448(3, A, null), n, 56, false);
+}
+// encodings x scalars (bigint[]), or ONE bigint against every row -> encodings of the products, null where a row does not decode
+function decaf448MultiplyBatch(encodings, scalars) {
+  const one = typeof scalars === 'bigint';
+  if (!one && scalars.length !== encodings.length) throw new Error('arrays of points and scalars must have equal length');
+  const n = encodings.length, E = ristrettoPack(encodings, 56), K = decafScalars(one ? [scalars] : scalars);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.decaf448(4, E, K), n, 56, true);
+}
+function decaf448MultiplyBaseBatch(scalars) {
+  const n = scalars.length, K = decafScalars(scalars);
+  if (n === 0) return [];
+  init();
+  return ristrettoSplit(native.decaf448(5, K, null), n, 56, false);
+}
+
 
 // ---- codecs: array forms of Point.fromBytes / toBytes (compressed) --------------------------------
 //   weierstrass.ts:541-605, bls12-381.ts:377-459 (+ subgroup checks :567-577, :599-601), edwards.ts:405-436,620-628
@@ -1033,4 +1087,6 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    x448ScalarMultBatch, x448GetPublicKeyBatch, ed448VerifyBatch,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
-                   ristrettoDeriveToCurve, native };
+                   ristrettoDeriveToCurve,
+                   decaf448FromBytesBatch, decaf448ToBytesBatch, decaf448EqualsBatch, decaf448MultiplyBatch, decaf448MultiplyBaseBatch,
+                   decaf448DeriveToCurveBatch, native };

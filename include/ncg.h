@@ -596,6 +596,43 @@ int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const voi
 int ncg_ed448_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, const void* k56_dev,
                                uint8_t* out_ok_dev, void* stream);
 
+/* ---- decaf448 (RFC 9496 section 5): _DecafPoint and decaf448_hasher of the reference's src/ed448.ts ---------------------
+ * The prime-order group over edwards448.  An element is handled through an Edwards representative: an Ed448 affine point x || y,
+ * 56 canonical little-endian bytes each, the format ncg_ed448_add_pairs_batch and ncg_ed448_encode_batch take.  Encodings, scalars,
+ * representatives and uniform input are all made of 56-byte values read as 14 words: a DEVICE pointer to any of them must be
+ * 4-byte aligned and is refused, not dereferenced, otherwise; host pointers may sit at any address.  n = 0 returns NCG_OK and
+ * touches nothing; n >= 2^31 is refused; unknown flag bits return NCG_ERR_INVALID_ARG.
+ *
+ * ncg_decaf448_decode_batch: DecafPoint.fromBytes (ed448.ts:569-595) -> the affine representative of steps 5-7.  out_ok = 0 and a
+ * zero row where the reference throws: s >= p or s odd ('invalid decaf448 encoding 1'), the ratio not a square ('encoding 2').
+ * ncg_decaf448_encode_batch: toBytes (:610-621) of ANY point of the curve given affine: P and P + (0, -1) give the same 56 bytes
+ * (as in the reference, a translate by a point of order 4 does not: the identity and (0, -1) encode to zero, (+-1, 0) to p - 1).
+ * The input is not validated.
+ * ncg_decaf448_equals_batch: equals (:627-633): out_eq[i] = (x1 y2 == y1 x2).
+ * ncg_decaf448_from_uniform_batch: decaf448_hasher.deriveToCurve (:689-700) of 112 uniform bytes, ENCODED: each 56-byte half is
+ * reduced mod p (no bit is masked, p .. 2^448 - 1 are accepted), mapped (calcElligatorDecafMap, :474-510), and the two points added.
+ * ncg_decaf448_mul_batch: out56[i] = fromBytes(enc56[i]).multiplyUnsafe(k56[i]).toBytes(), k any value below 2^448: the exact
+ * integer multiple of the decoded representative, k = 0 gives 56 zero bytes.  Decode, multiply and encode run in one kernel.
+ * flags: NCG_DECAF448_ONE_SCALAR = one k for every row.  A refused encoding gives a zero row and out_ok = 0.
+ * ncg_decaf448_mul_base_batch: out56[i] = DecafPoint.BASE.multiplyUnsafe(k56[i]).toBytes(); BASE is twice the Ed448 base (:515-520).
+ * The multiplications are multiplyUnsafe; the library makes no constant-time claim. */
+#define NCG_DECAF448_ONE_SCALAR 1
+int ncg_decaf448_decode_batch(ncg_ctx* ctx, size_t n, const void* enc56, void* out_affine112, uint8_t* out_ok);
+int ncg_decaf448_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc56_dev, void* out_affine112_dev, uint8_t* out_ok_dev,
+                                  void* stream);
+int ncg_decaf448_encode_batch(ncg_ctx* ctx, size_t n, const void* affine112, void* out56);
+int ncg_decaf448_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine112_dev, void* out56_dev, void* stream);
+int ncg_decaf448_equals_batch(ncg_ctx* ctx, size_t n, const void* a112, const void* b112, uint8_t* out_eq);
+int ncg_decaf448_equals_batch_dev(ncg_ctx* ctx, size_t n, const void* a112_dev, const void* b112_dev, uint8_t* out_eq_dev,
+                                  void* stream);
+int ncg_decaf448_from_uniform_batch(ncg_ctx* ctx, size_t n, const void* uniform112, void* out56);
+int ncg_decaf448_from_uniform_batch_dev(ncg_ctx* ctx, size_t n, const void* uniform112_dev, void* out56_dev, void* stream);
+int ncg_decaf448_mul_batch(ncg_ctx* ctx, size_t n, const void* enc56, const void* k56, int flags, void* out56, uint8_t* out_ok);
+int ncg_decaf448_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc56_dev, const void* k56_dev, int flags, void* out56_dev,
+                               uint8_t* out_ok_dev, void* stream);
+int ncg_decaf448_mul_base_batch(ncg_ctx* ctx, size_t n, const void* k56, void* out56);
+int ncg_decaf448_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* k56_dev, void* out56_dev, void* stream);
+
 /* ---- measurement helpers (not on the product path) ------------------------------------ */
 /* ---- secp256k1 ECDSA batch verification --------------------------------------------------------
  * out_ok[i] = ecdsa.verify(sig[i], msgHash[i], publicKey[i], { prehash: false, format: 'compact', lowS })
@@ -735,6 +772,16 @@ int ncg_field_check(ncg_ctx* ctx, int field, int op, int variant, size_t n, cons
  * b is required (non-NULL) even where its width is 0.  An op nobody defines reads nothing and leaves out zero (rows of 16
  * words).  n above 2^24 is refused. */
 int ncg_fe448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
+/* The lane code of csrc/decaf448.hpp on n rows of RAW uint32 words, in the style of ncg_fe448_check (whose op table is closed as
+ * well).  Field elements are 16 limbs in radix 2^28; every input element is at bound 1 (every limb below 2^28 + 2^10, the value
+ * any representative), every output element at bound 1.  Words per row (a, b, out), per op:
+ *   0  SQRT_RATIO_M1(u, v)         (16, 16, 17)   a = u, b = v; out[0..16) = the value, non-negative; out[16] = 1 iff v value^2 = u
+ *   1  encode_ext                  (64,  0, 14)   a = X Y Z T; out = the 14 LE words of the encoding
+ *   2  the Elligator map           (16,  0, 64)   a = r0; out = X Y Z T of the extended representative
+ * `variant` is not read.  b is required (non-NULL) even where its width is 0.  An op nobody defines reads nothing and leaves out
+ * zero (rows of 16 words).  n above 2^24 is refused. */
+int ncg_decaf448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
 /* ---- bls12-381 pairings: batch pairing products and GT arithmetic ------------------------------------------
  * A GT (Fp12) element crosses as 576 bytes: the 12 Fp coefficients in tower order c0.c0.c0, c0.c0.c1, c0.c1.c0, ..,

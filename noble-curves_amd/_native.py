@@ -37,6 +37,9 @@ ED448_ONE_SCALAR = 1    # ncg_ed448_mul_batch flag: one scalar for every row
 # ncg_fe448_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/ed448.hpp)
 FE448_CHECK_WORDS = {0: (16, 16, 16), 1: (16, 0, 16), 2: (16, 16, 48), 3: (16, 16, 16), 4: (16, 0, 14), 5: (14, 0, 16), 6: (16, 0, 16),
                      7: (16, 0, 16), 8: (64, 16, 64), 9: (48, 48, 48), 10: (48, 0, 48)}
+DECAF448_ONE_SCALAR = 1  # ncg_decaf448_mul_batch flag: one scalar for every row
+# ncg_decaf448_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/decaf448.hpp)
+DECAF448_CHECK_WORDS = {0: (16, 16, 17), 1: (64, 0, 14), 2: (16, 0, 64)}
 ENCODED_BYTES = {SECP256K1: 33, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 96}   # compressed toBytes
 
 
@@ -171,6 +174,19 @@ _OPTIONAL_PROTOS = {
     "ncg_ed448_verify_batch": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ed448_verify_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "ncg_fe448_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_decode_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_decaf448_encode_batch": [_vp, _sz, _vp, _vp],
+    "ncg_decaf448_encode_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_equals_batch": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_equals_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_decaf448_from_uniform_batch": [_vp, _sz, _vp, _vp],
+    "ncg_decaf448_from_uniform_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_mul_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_decaf448_mul_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_decaf448_mul_base_batch": [_vp, _sz, _vp, _vp],
+    "ncg_decaf448_mul_base_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_decaf448_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
     "ncg_ristretto_decode_batch": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ristretto_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ristretto_encode_batch": [_vp, _sz, _vp, _vp],
@@ -766,6 +782,80 @@ class Engine:
         out = np.zeros((n, wo), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_fe448_check(self.h, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
+
+    # ---- decaf448: encodings and scalars uint8 [n, 56], Edwards representatives (Ed448 affine points) and uniform bytes [n, 112] ----
+    def decaf448_decode_batch(self, enc):
+        """DecafPoint.fromBytes per row -> (representatives x || y [n, 112], ok bool [n]); a refused row is zero"""
+        enc = self._rows(enc, 56)
+        n = enc.shape[0]
+        out, ok = np.zeros((n, 112), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_decode_batch(self.h, n, enc.ctypes.data, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def decaf448_encode_batch(self, affine):
+        """DecafPoint.toBytes of any points of the curve [n, 112] -> [n, 56]"""
+        affine = self._rows(affine, 112)
+        n = affine.shape[0]
+        out = np.zeros((n, 56), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_encode_batch(self.h, n, affine.ctypes.data, out.ctypes.data))
+        return out
+
+    def decaf448_equals_batch(self, a, b):
+        """DecafPoint.equals per row of representatives [n, 112] -> bool [n]"""
+        a, b = self._rows(a, 112), self._rows(b, 112)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("arrays of points must have equal length")
+        out = np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_equals_batch(self.h, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out.astype(bool)
+
+    def decaf448_from_uniform_batch(self, bytes112):
+        """decaf448_hasher.deriveToCurve(row).toBytes() per row of 112 uniform bytes -> [n, 56]"""
+        b = self._rows(bytes112, 112)
+        n = b.shape[0]
+        out = np.zeros((n, 56), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_from_uniform_batch(self.h, n, b.ctypes.data, out.ctypes.data))
+        return out
+
+    def decaf448_mul_batch(self, enc, ks, one_scalar=False):
+        """fromBytes(enc).multiplyUnsafe(k).toBytes() per row: enc [n, 56], ks [n, 56] (or ONE row) -> ([n, 56], ok bool [n])"""
+        enc, ks = self._rows(enc, 56), self._rows(ks, 56)
+        n = enc.shape[0]
+        if ks.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of points and scalars must have equal length")
+        out, ok = np.zeros((n, 56), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_mul_batch(self.h, n, enc.ctypes.data, ks.ctypes.data, DECAF448_ONE_SCALAR if one_scalar else 0,
+                                                        out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def decaf448_mul_base_batch(self, ks):
+        """DecafPoint.BASE.multiplyUnsafe(k).toBytes() per row: ks [n, 56] -> [n, 56]"""
+        ks = self._rows(ks, 56)
+        n = ks.shape[0]
+        out = np.zeros((n, 56), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_decaf448_mul_base_batch(self.h, n, ks.ctypes.data, out.ctypes.data))
+        return out
+
+    def decaf448_check(self, op, a_words, b_words):
+        """The lane code of decaf448 on raw uint32 rows (ncg_decaf448_check; DECAF448_CHECK_WORDS has the widths): a [n, wa],
+        b [n, wb] (any array where wb = 0) -> [n, wo]; an unknown op gives [n, 16] zeros."""
+        wa, wb, wo = DECAF448_CHECK_WORDS.get(op, (0, 0, 16))
+        a = np.ascontiguousarray(a_words, dtype=np.uint32)
+        b = np.ascontiguousarray(b_words, dtype=np.uint32)
+        n = a.shape[0]
+        if (wa and a.shape[1] != wa) or (wb and (b.shape[0] != n or b.shape[1] != wb)):
+            raise ValueError("decaf448_check: op %d takes rows of %d and %d words" % (op, wa, wb))
+        out = np.zeros((n, wo), dtype=np.uint32)
+        if n:
+            self._check(self.lib.ncg_decaf448_check(self.h, op, 0, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out
 
     # ---- ristretto255: encodings and scalars uint8 [n, 32], Edwards representatives (ed25519 wire points) [n, 64] ------------

@@ -1893,6 +1893,85 @@ int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const voi
   return hc.finish(ncg_ed448_verify_batch_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(k), hc.dev<uint8_t>(ok), ctx->stream));
 }
 
+// ---- decaf448 (decaf448.hip).  Every buffer but the flag bytes is made of 56-byte rows read as 14 LE words: the alignment rule of
+// the Ed448 family holds for all of them.  Edwards representatives are Ed448 affine points (x || y, 112 bytes).
+int ncg_decaf448_decode_batch_dev(ncg_ctx* ctx, size_t n, const void* enc56_dev, void* out_affine112_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_decode_batch", 0, 0, {enc56_dev, out_affine112_dev}), n, enc56_dev, out_affine112_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::decaf448_decode_batch((const uint32_t*)enc56_dev, (uint32_t*)out_affine112_dev, out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_decode_batch(ncg_ctx* ctx, size_t n, const void* enc56, void* out_affine112, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, no_rule("decaf448_decode_batch"), n, enc56, out_affine112, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc56, n * 56), o = hc.out(out_affine112, n * 112), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_decode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_decaf448_encode_batch_dev(ncg_ctx* ctx, size_t n, const void* affine112_dev, void* out56_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_encode_batch", 0, 0, {affine112_dev, out56_dev}), n, affine112_dev, out56_dev);
+  NCG_HIP(ctx, ncg::decaf448_encode_batch((const uint32_t*)affine112_dev, (uint32_t*)out56_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_encode_batch(ncg_ctx* ctx, size_t n, const void* affine112, void* out56) {
+  NCG_BEGIN(ctx, no_rule("decaf448_encode_batch"), n, affine112, out56);
+  HostCall hc(ctx);
+  const int in = hc.in(affine112, n * 112), o = hc.out(out56, n * 56);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_encode_batch_dev(ctx, n, hc.dev(in), hc.dev(o), ctx->stream));
+}
+int ncg_decaf448_equals_batch_dev(ncg_ctx* ctx, size_t n, const void* a112_dev, const void* b112_dev, uint8_t* out_eq_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_equals_batch", 0, 0, {a112_dev, b112_dev}), n, a112_dev, b112_dev, out_eq_dev);
+  NCG_HIP(ctx, ncg::decaf448_equals_batch((const uint32_t*)a112_dev, (const uint32_t*)b112_dev, out_eq_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_equals_batch(ncg_ctx* ctx, size_t n, const void* a112, const void* b112, uint8_t* out_eq) {
+  NCG_BEGIN(ctx, no_rule("decaf448_equals_batch"), n, a112, b112, out_eq);
+  HostCall hc(ctx);
+  const int da = hc.in(a112, n * 112), db = hc.in(b112, n * 112), o = hc.out(out_eq, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_equals_batch_dev(ctx, n, hc.dev(da), hc.dev(db), hc.dev<uint8_t>(o), ctx->stream));
+}
+int ncg_decaf448_from_uniform_batch_dev(ncg_ctx* ctx, size_t n, const void* uniform112_dev, void* out56_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_from_uniform_batch", 0, 0, {uniform112_dev, out56_dev}), n, uniform112_dev, out56_dev);
+  NCG_HIP(ctx, ncg::decaf448_from_uniform_batch((const uint32_t*)uniform112_dev, (uint32_t*)out56_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_from_uniform_batch(ncg_ctx* ctx, size_t n, const void* uniform112, void* out56) {
+  NCG_BEGIN(ctx, no_rule("decaf448_from_uniform_batch"), n, uniform112, out56);
+  HostCall hc(ctx);
+  const int in = hc.in(uniform112, n * 112), o = hc.out(out56, n * 56);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_from_uniform_batch_dev(ctx, n, hc.dev(in), hc.dev(o), ctx->stream));
+}
+int ncg_decaf448_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc56_dev, const void* k56_dev, int flags, void* out56_dev,
+                               uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_mul_batch", flags, NCG_DECAF448_ONE_SCALAR, {enc56_dev, k56_dev, out56_dev}), n, enc56_dev, k56_dev,
+            out56_dev, out_ok_dev);
+  NCG_HIP(ctx, ncg::decaf448_mul_batch((const uint32_t*)enc56_dev, (const uint32_t*)k56_dev, flags & NCG_DECAF448_ONE_SCALAR, (uint32_t*)out56_dev,
+                                       out_ok_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_mul_batch(ncg_ctx* ctx, size_t n, const void* enc56, const void* k56, int flags, void* out56, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed448_flags_rule(ctx, "decaf448_mul_batch", flags, NCG_DECAF448_ONE_SCALAR), n, enc56, k56, out56, out_ok);
+  HostCall hc(ctx);
+  const int in = hc.in(enc56, n * 56), k = hc.in(k56, (flags & NCG_DECAF448_ONE_SCALAR) ? 56 : n * 56);
+  const int o = hc.out(out56, n * 56), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_mul_batch_dev(ctx, n, hc.dev(in), hc.dev(k), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream));
+}
+int ncg_decaf448_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* k56_dev, void* out56_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_rule(ctx, "decaf448_mul_base_batch", 0, 0, {k56_dev, out56_dev}), n, k56_dev, out56_dev);
+  NCG_HIP(ctx, ncg::decaf448_mul_batch(nullptr, (const uint32_t*)k56_dev, 0, (uint32_t*)out56_dev, nullptr, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_decaf448_mul_base_batch(ncg_ctx* ctx, size_t n, const void* k56, void* out56) {
+  NCG_BEGIN(ctx, no_rule("decaf448_mul_base_batch"), n, k56, out56);
+  HostCall hc(ctx);
+  const int k = hc.in(k56, n * 56), o = hc.out(out56, n * 56);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_decaf448_mul_base_batch_dev(ctx, n, hc.dev(k), hc.dev(o), ctx->stream));
+}
+
 // ---- ristretto255 (ristretto.hip).  Encodings and scalars are rows of 32 bytes read as 8 LE words, Edwards representatives are
 // ed25519 wire points.  The _dev forms keep what lies between their kernels in ctx->rist_ws, never in ctx->scratch.
 static int ensure_rist_ws(ncg_ctx* ctx, size_t bytes, hipStream_t st) {
@@ -2207,6 +2286,22 @@ int ncg_fe448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, 
   if (int rc = hc.stage()) return rc;
   if (wo)
     NCG_HIP(ctx, ncg::fe448_check(op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, ctx->stream));
+  return hc.finish(NCG_OK);
+}
+
+// The pieces of decaf448.hpp on raw limbs, in the same style: an op nobody defines reads nothing and leaves rows of 16 zero words.
+int ncg_decaf448_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out) {
+  (void)variant;  // no op has variants yet
+  const Rule rule = {"decaf448_check", !ctx || n <= (1u << 24) ? NCG_OK
+                                           : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: decaf448_check: batch too large (max 2^24)")};
+  NCG_BEGIN(ctx, rule, n, a, b, out);
+  int wa, wb, wo;
+  ncg::decaf448_check_row_words(op, &wa, &wb, &wo);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * wa * 4), db = hc.in(b, n * wb * 4);
+  const int o = hc.out(out, n * (wo ? wo : 16) * 4, true);
+  if (int rc = hc.stage()) return rc;
+  if (wo) NCG_HIP(ctx, ncg::decaf448_check(op, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, ctx->stream));
   return hc.finish(NCG_OK);
 }
 

@@ -222,6 +222,24 @@ void ed448_to_montgomery_host(const uint8_t* pk, uint32_t* out, uint8_t* out_ok,
 void ed448_verify_host(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, uint8_t* out_ok, int n);
 int fe448_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// decaf448 (decaf448.hip): every row is made of 56-byte values read as 14 LE words: encodings and scalars 14 words, Edwards
+// representatives (Ed448 affine points x || y) and uniform input 28.  A refused encoding gives out_ok = 0 and a zero row.
+// enc = NULL (decaf448_mul_batch): the decaf base point, out_ok is not written.  one_scalar: one row of `k` for every item.
+hipError_t decaf448_decode_batch(const uint32_t* enc, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+hipError_t decaf448_encode_batch(const uint32_t* affine, uint32_t* out, int n, hipStream_t st);
+hipError_t decaf448_equals_batch(const uint32_t* a, const uint32_t* b, uint8_t* out_eq, int n, hipStream_t st);
+hipError_t decaf448_from_uniform_batch(const uint32_t* uniform, uint32_t* out, int n, hipStream_t st);
+hipError_t decaf448_mul_batch(const uint32_t* enc, const uint32_t* k, int one_scalar, uint32_t* out, uint8_t* out_ok, int n, hipStream_t st);
+// the pieces of decaf448.hpp on raw limbs (ncg_decaf448_check); words per row of each op: decaf448_check_row_words (0 = unknown op)
+void decaf448_check_row_words(int op, int* wa, int* wb, int* wo);
+hipError_t decaf448_check(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st);
+void decaf448_decode_host(const uint32_t* enc, uint32_t* out, uint8_t* out_ok, int n);
+void decaf448_encode_host(const uint32_t* affine, uint32_t* out, int n);
+void decaf448_equals_host(const uint32_t* a, const uint32_t* b, uint8_t* out_eq, int n);
+void decaf448_from_uniform_host(const uint32_t* uniform, uint32_t* out, int n);
+void decaf448_mul_host(const uint32_t* enc, const uint32_t* k, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
+int decaf448_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 // ristretto255 (ristretto.hip): encodings and scalars are rows of 8 LE words, Edwards representatives ed25519 wire points (16
 // words), uniform input 16 words.  A rejected encoding gives out_ok = 0 and a zero row - or the identity (0, 1) with
 // identity_on_reject, for a caller that multiplies what comes out.  ristretto_encode_proj_batch takes the (X, Y, Z) rows of

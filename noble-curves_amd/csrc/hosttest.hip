@@ -26,6 +26,7 @@
 #include "ristretto.hip"
 #include "pairing.hip"
 #include "ed448.hip"
+#include "decaf448.hip"
 
 using namespace ncg;
 
@@ -320,6 +321,53 @@ int ht_ed448_verify(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, ui
 }
 int ht_fe448_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return fe448_check_host(op, variant, a, b, out); }
 void ht_fe448_widths(int op, int* wa, int* wb, int* wo) { fe448_check_row_words(op, wa, wb, wo); }
+
+// decaf448 on the CPU twins of decaf448.hip: encodings and scalars 14 LE words per row, Edwards representatives and uniform bytes
+// 28; flags as ncg_decaf448_mul_batch, enc = NULL: the decaf base.  ht_decaf448_encode_proj: X Y Z as wire words (42 per row).
+// ht_decaf448_op: one row of ncg_decaf448_check, -1 for an unknown op; ht_decaf448_widths: its words per row.
+// ht_decaf448_consts: 1 - d, 1 - 2 d, sqrt(-d), 1 / sqrt(-d) and the base point x, y as the lane code holds them, 14 words each.
+int ht_decaf448_decode(const uint32_t* enc, uint32_t* out, uint8_t* ok, int n) {
+  decaf448_decode_host(enc, out, ok, n);
+  return 0;
+}
+int ht_decaf448_encode(const uint32_t* affine, uint32_t* out, int n) {
+  decaf448_encode_host(affine, out, n);
+  return 0;
+}
+int ht_decaf448_encode_proj(const uint32_t* xyz, uint32_t* out, int n) {
+  for (int i = 0; i < n; i++) {
+    uint32_t c[3][14], w[14];
+    for (int j = 0; j < 3; j++)
+      for (int l = 0; l < 14; l++) c[j][l] = xyz[(size_t)i * 42 + j * 14 + l];
+    decaf_encode_proj(Ed448Pt{fe448_from_words(c[0]), fe448_from_words(c[1]), fe448_from_words(c[2])}, w);
+    for (int l = 0; l < 14; l++) out[(size_t)i * 14 + l] = w[l];
+  }
+  return 0;
+}
+int ht_decaf448_equals(const uint32_t* a, const uint32_t* b, uint8_t* eq, int n) {
+  decaf448_equals_host(a, b, eq, n);
+  return 0;
+}
+int ht_decaf448_from_uniform(const uint32_t* uniform, uint32_t* out, int n) {
+  decaf448_from_uniform_host(uniform, out, n);
+  return 0;
+}
+int ht_decaf448_mul(const uint32_t* enc, const uint32_t* k, int flags, uint32_t* out, uint8_t* ok, int n) {
+  if (flags & ~1) return -1;
+  decaf448_mul_host(enc, k, flags & 1, out, ok, n);
+  return 0;
+}
+int ht_decaf448_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) { return decaf448_check_host(op, a, b, out); }
+void ht_decaf448_widths(int op, int* wa, int* wb, int* wo) { decaf448_check_row_words(op, wa, wb, wo); }
+void ht_decaf448_consts(uint32_t* out) {
+  const F448 c[6] = {DecafConsts::one_minus_d(), DecafConsts::one_minus_two_d(), DecafConsts::sqrt_minus_d(), DecafConsts::invsqrt_minus_d(),
+                     decaf_base().X, decaf_base().Y};
+  for (int j = 0; j < 6; j++) {
+    uint32_t w[14];
+    fe448_to_words(w, c[j]);
+    for (int l = 0; l < 14; l++) out[j * 14 + l] = w[l];
+  }
+}
 
 // ristretto255 on the CPU twins of ristretto.hip: encodings and scalars 8 LE words per row, Edwards representatives 16, uniform
 // bytes 16; flags as ncg_ristretto_mul_batch.  ht_ristretto_encode_proj: X Y Z as wire words (24 per row).  ht_ristretto_op: the

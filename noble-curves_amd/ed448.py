@@ -14,9 +14,11 @@ small-order test, s < n and the cofactored equation run on the device.  `zip215=
 `ed448_Point`: fromBytes_batch / toBytes_batch / multiplyUnsafe_batch / multiplyBase_batch / add_batch on encodings, with the
 range errors of multiply / multiplyUnsafe raised here.
 
-Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), decaf448 and its hasher,
-`ed448_hasher` (hash-to-curve), FROST and OPRF suites, signing, an MSM over Ed448, and a fixed-base table (multiplyBase runs the
-variable-base kernel on the base point).
+decaf448 and its hasher, the prime-order group of this curve, live in `noble_curves_amd.decaf448`.
+
+Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), `ed448_hasher` (hash-to-curve), FROST
+and OPRF suites, signing, an MSM over Ed448, and a fixed-base table (multiplyBase runs the variable-base kernel on the base
+point).
 """
 import hashlib
 

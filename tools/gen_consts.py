@@ -317,6 +317,33 @@ def main():
     out += arr("K261", (1 << 261) % bn_r, 8)
     out += arr29("ONE", (1 << 261) % bn_r, 9)
     out += "};\n\n"
+    # decaf448 (src/ed448.ts:446-457, 515-520; RFC 9496 section 5.1) in the radix-2^28 form of fe448.hpp: 16 limbs, plain residues.
+    # p = 3 (mod 4): the square root of a residue v is v^((p + 1) / 4).  -d = 39081; the reference's sqrt(-d) is the EVEN root and
+    # 1 / sqrt(-d) its inverse (the host test compares both with the decimals of src/ed448.ts).  The base
+    # point is twice the Ed448 base (Gx, Gy), computed here by the affine doubling for a = 1.
+    gp = (1 << 448) - (1 << 224) - 1
+    gd = gp - 39081
+    root = pow(39081, (gp + 1) // 4, gp)
+    assert root * root % gp == 39081
+    sqrt_minus_d = root if root % 2 == 0 else gp - root
+    invsqrt_minus_d = pow(sqrt_minus_d, -1, gp)
+    assert invsqrt_minus_d ** 2 * 39081 % gp == 1
+    ggx = 0x4f1970c66bed0ded221d15a622bf36da9e146570470f1767ea6de324a3d3a46412ae1af72ab66511433b80e18b00938e2626a82bc70cc05e
+    ggy = 0x693f46716eb6bc248876203756c9c7624bea73736ca3984087789c1e05a0c2d73ad3ff1ce67c39c4fdbd132c4ed7c8ad9808795bf230fa14
+    assert (ggx * ggx + ggy * ggy - 1 - gd * ggx * ggx * ggy * ggy) % gp == 0
+    gt = gd * ggx * ggx * ggy * ggy % gp
+    dbx = 2 * ggx * ggy * pow(1 + gt, -1, gp) % gp
+    dby = (ggy * ggy - ggx * ggx) * pow(1 - gt, -1, gp) % gp
+    assert (dbx * dbx + dby * dby - 1 - gd * dbx * dbx * dby * dby) % gp == 0
+
+    def arr28(name, x):
+        return "  static constexpr uint32_t %s[16] = {%s};\n" % (
+            name, ", ".join("0x%08xu" % ((x >> (28 * i)) & ((1 << 28) - 1)) for i in range(16)))
+    out += "// decaf448 over GF(2^448 - 2^224 - 1): 16 limbs in radix 2^28 (fe448.hpp)\nstruct Decaf448Consts {\n"
+    out += arr28("ONE_MINUS_D", (1 - gd) % gp) + arr28("ONE_MINUS_TWO_D", (1 - 2 * gd) % gp)
+    out += arr28("SQRT_MINUS_D", sqrt_minus_d) + arr28("INVSQRT_MINUS_D", invsqrt_minus_d)
+    out += arr28("BASE_X", dbx) + arr28("BASE_Y", dby)
+    out += "};\n\n"
     out += "}  // namespace ncg\n"
     with open(OUT, "w") as f:
         f.write(out)

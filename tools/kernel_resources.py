@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / spill / scratch figures of the kernels in a HIP library or object: unpacks the clang offload bundles
+"""VGPR / AGPR / spill / scratch figures of the kernels in a HIP library or object: unpacks the clang offload bundles
 of the file and reads the code-object metadata with llvm-readelf.
     python tools/kernel_resources.py noble-curves_amd/libncg.so [substring ...]"""
 import re
@@ -45,8 +45,10 @@ def main():
             if pats and not any(p in dem for p in pats):
                 continue
             g = lambda k: (re.search(r"\.%s:\s+(\d+)" % k, blk) or [None, "?"])[1]  # noqa: E731
-            print("%-90s vgpr %3s spill %3s scratch %4s sgpr %3s" % (dem.split("(")[0][-90:], g("vgpr_count"), g("vgpr_spill_count"),
-                                                                      g("private_segment_fixed_size"), g("sgpr_count")))
+            agpr = (re.match(r"\s*(\d+)", blk) or [None, "?"])[1]   # the block starts right after "- .agpr_count:"
+            print("%-90s vgpr %3s agpr %3s spill %3s scratch %4s sgpr %3s" % (dem.split("(")[0][-90:], g("vgpr_count"), agpr,
+                                                                               g("vgpr_spill_count"), g("private_segment_fixed_size"),
+                                                                               g("sgpr_count")))
 
 
 if __name__ == "__main__":
