@@ -5,7 +5,7 @@
 #include <vector>
 
 #include "../../include/ncg.h"  // NCG_NTT_MAX_LOG2N
-#include "mulvar.hpp"
+#include "mulvar_pairsum.hpp"
 #include "ed25519.hip"  // single-TU inclusion: lane function + host table builder
 #include "decode.hip"
 #include "ntt.hip"
@@ -37,6 +37,48 @@ static void ht_mul_var_t(const uint32_t* pts, const uint32_t* scalars, uint32_t*
   for (int i = 0; i < n; i++)
     mul_var_lane<C, W>(pts + (size_t)i * 2 * WW, scalars + (size_t)i * 8, out + (size_t)i * 2 * WW, out_inf + i, true,
                        tab.data(), 1);
+}
+
+// The pair-sum path of the secp256k1 batch multiply (mulvar_pairsum.hpp) with its four kernels' lane routines run in the
+// kernels' order: prepare, inverse over groups of K, ladder, affine step over groups of K.  flags[i]: bit 0 the prepare lane's
+// flag, bit 1 the lane went through mul_var_slow.  dbg (or null): of item 0 the slot, the prefixes, acc and 1 / acc.
+template <class C, int W, int K>
+static void ht_mul_var_pairsum_t(const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, uint8_t* flags,
+                                 uint32_t* dbg, int n) {
+  using PS = PairSumCfg<C, W>;
+  using F = typename C::F;
+  constexpr int FW = PS::FW, WW = PS::Cfg::WW;
+  std::vector<uint32_t> jac((size_t)n * 3 * FW), slots((size_t)n * PS::SLOT_WORDS), pre((size_t)n * PS::PRE_WORDS);
+  auto acc = [&](int i) { return jac.data() + (size_t)i * PS::ACC_STRIDE + PS::ACC_OFF; };
+  for (int i = 0; i < n; i++)
+    flags[i] = pairsum_prepare_lane<C, W>(pts + (size_t)i * 2 * WW, scalars + (size_t)i * 8, slots.data() + (size_t)i * PS::SLOT_WORDS,
+                                          pre.data() + (size_t)i * PS::PRE_WORDS, 1, acc(i)) ? 1 : 0;
+  if (dbg && n > 0) {
+    memcpy(dbg, slots.data(), PS::SLOT_WORDS * 4);
+    memcpy(dbg + PS::SLOT_WORDS, pre.data(), PS::PRE_WORDS * 4);
+    memcpy(dbg + PS::SLOT_WORDS + PS::PRE_WORDS, acc(0), FW * 4);
+  }
+  for (int i0 = 0; i0 < n; i0 += K)
+    batch_inverse_lane<F, K, false>((uint32_t*)nullptr, n - i0, [&](int j) -> F { return FieldIO<F>::load(acc(i0 + j)); },
+                                    [&](int j, bool zero, const F& zi) { if (!zero) FieldIO<F>::store(acc(i0 + j), zi); });
+  if (dbg && n > 0) memcpy(dbg + PS::SLOT_WORDS + PS::PRE_WORDS + FW, acc(0), FW * 4);
+  for (int i = 0; i < n; i++)
+    if (pairsum_ladder_lane<C, W>(pts + (size_t)i * 2 * WW, scalars + (size_t)i * 8, jac.data() + (size_t)i * 3 * FW,
+                                  slots.data() + (size_t)i * PS::SLOT_WORDS, pre.data() + (size_t)i * PS::PRE_WORDS, 1, acc(i)))
+      flags[i] |= 2;
+  for (int i0 = 0; i0 < n; i0 += K)
+    batch_inverse_lane<F, K, false>(
+        (uint32_t*)nullptr, n - i0, [&](int j) -> F { return FieldIO<F>::load(jac.data() + ((size_t)(i0 + j) * 3 + 2) * FW); },
+        [&](int j, bool inf, const F& zi) {
+          const uint32_t* p = jac.data() + (size_t)(i0 + j) * 3 * FW;
+          Affine<F> A{F::zero(), F::zero()};
+          if (!inf) {
+            auto zi2 = f_sqr(zi);
+            A = {FieldIO<F>::load(p) * zi2, FieldIO<F>::load(p + FW) * zi2 * zi};
+          }
+          store_affine_wire<F>(out + (size_t)(i0 + j) * 2 * WW, A);
+          out_inf[i0 + j] = inf ? 1 : 0;
+        });
 }
 
 template <class PR>
@@ -209,6 +251,18 @@ int ht_mul_var(int curve, const uint32_t* pts, const uint32_t* scalars, uint32_t
     case CURVE_BN254_G1: ht_mul_var_t<CurveBn254, 4>(pts, scalars, out, out_inf, n); return 0;
   }
   return -1;
+}
+
+// the pair-sum path of mul_var_secp_inline (mulvar_pairsum.hpp) on the CPU: see ht_mul_var_pairsum_t.  ht_pairsum_min_n: the
+// item count from which the device takes that path; ht_pairsum_dbg_words: the size of `dbg`
+int ht_mul_var_pairsum(const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, uint8_t* flags, uint32_t* dbg, int n) {
+  ht_mul_var_pairsum_t<CurveSecpI, 4, 16>(pts, scalars, out, out_inf, flags, dbg, n);
+  return 0;
+}
+int ht_pairsum_min_n() { return PAIRSUM_MIN_N; }
+int ht_pairsum_dbg_words() {
+  using PS = PairSumCfg<CurveSecpI, 4>;
+  return PS::SLOT_WORDS + PS::PRE_WORDS + 2 * PS::FW;
 }
 
 // field: 0 secp256k1 p, 1 ed25519 p, 2 bls12-381 p; canonical LE limbs in and out

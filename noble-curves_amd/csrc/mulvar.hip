@@ -1,6 +1,6 @@
 // Launchers for the batch variable-base multiply kernels (see mulvar.hpp).
 #include <algorithm>
-#include "mulvar.hpp"
+#include "mulvar_pairsum.hpp"
 #include "host_api.hpp"
 
 namespace ncg {
@@ -128,7 +128,8 @@ hipError_t normalize_batch(int curve, const uint32_t* proj_wire, uint32_t* out_w
 size_t mul_var_tmp_bytes(int curve, int n) {
   switch (curve) {
     // Jacobian scratch + a per-item window table (k_mul_var_gtab), sized for 5-bit windows (the kernels use 4)
-    case CURVE_SECP256K1: return pad64(n) * (3 * FieldIO<CurveSecp::F>::WORDS + gtab_words_per_item<CurveSecp, 5>()) * 4;
+    case CURVE_SECP256K1:   // or the table and the prefix products of the pair-sum path (mulvar_pairsum.hpp)
+      return pad64(n) * (3 * FieldIO<CurveSecp::F>::WORDS + std::max(gtab_words_per_item<CurveSecp, 5>(), pairsum_words_per_item<CurveSecpI, 4>())) * 4;
     case CURVE_BLS12_381_G1: return pad64(n) * (3 * FieldIO<CurveG1::F>::WORDS + gtab_words_per_item<CurveG1, 5>()) * 4;
     case CURVE_BN254_G1: return pad64(n) * (3 * FieldIO<CurveBn254::F>::WORDS + gtab_words_per_item<CurveBn254, 5>()) * 4;
     case CURVE_BLS12_381_G2:  // the verified-set ladder (mulvar_endo.hip) keeps a second table per lane

@@ -111,6 +111,108 @@ struct MulVarCfg {
   static constexpr int LDS_WORDS = TS * 2 * TW * 64;      // per 64-lane block
 };
 
+// The per-lane table of odd multiples [1, 3, .., 2^W - 1] P of mul_var_lane, built and brought to one Z; returns that Z (`Zg`:
+// the table holds affine points of the curve isomorphic by it).  Entry e, word w at tab[(e*2*TW + w)*stride]; with ZR_IN_TAB the TS
+// Z-ratios of the build sit behind the table while it runs and are dead afterwards.  `degenerate`: see coz_addu.
+// STAGED: `stg` (same layout, words `sstride` apart) is where the entries wait for the rescale, which reads them there and writes
+// `tab` - a place that is cheaper to write and read back than the table.  The rescaled x of every entry is left there as well.
+template <class C, int W, bool ZR_IN_TAB, bool STAGED, class TABPTR, class STGPTR>
+NCG_DI typename C::F mul_var_build_table(const Affine<typename C::F>& P, TABPTR tab, const int stride, STGPTR stg, const int sstride,
+                                         bool& degenerate) {
+  using Cfg = MulVarCfg<C, W>;
+  using F = typename C::F;
+  constexpr int TW = Cfg::TW, TS = Cfg::TS;
+  Jac<F> D = jac_dbl(Jac<F>{P.x, P.y, F::one()});
+  auto dz2 = f_sqr(D.Z);
+  auto dz3 = dz2 * D.Z;
+  Affine<F> Dc{D.X, D.Y};                 // 2P and P on the isomorphic curve, both at Z = 1: co-Z from the start
+  Affine<F> T{P.x * dz2, P.y * dz3};
+  F zr[ZR_IN_TAB ? 1 : TS];
+  auto zr_put = [&](int j, const F& v) {
+    if constexpr (ZR_IN_TAB) FieldIO<F>::store_strided(stg + (TS * 2 * TW + j * TW) * sstride, sstride, v);
+    else zr[j] = v;
+  };
+  auto zr_get = [&](int j) -> F {
+    if constexpr (ZR_IN_TAB) return FieldIO<F>::load_strided(stg + (TS * 2 * TW + j * TW) * sstride, sstride);
+    else return zr[j];
+  };
+  FieldIO<F>::store_strided(stg, sstride, T.x);
+  FieldIO<F>::store_strided(stg + TW * sstride, sstride, T.y);
+  // with the Z-ratios in memory nothing here indexes a register array: keep the loops rolled (the
+  // unrolled build is 15 mixed additions of straight-line code in front of the ladder)
+#pragma unroll(ZR_IN_TAB ? 1 : TS)
+  for (int j = 1; j < TS; j++) {
+    F zj;
+    coz_addu(Dc, T, zj, degenerate);
+    zr_put(j, zj);
+    FieldIO<F>::store_strided(stg + (j * 2 * TW) * sstride, sstride, T.x);
+    FieldIO<F>::store_strided(stg + (j * 2 * TW + TW) * sstride, sstride, T.y);
+    if (STAGED && j == TS - 1) {   // the last entry is at the table's Z already
+      FieldIO<F>::store_strided(tab + (j * 2 * TW) * stride, stride, T.x);
+      FieldIO<F>::store_strided(tab + (j * 2 * TW + TW) * stride, stride, T.y);
+    }
+  }
+  // bring every entry to the last entry's Z
+  F s = F::one();
+#pragma unroll(ZR_IN_TAB ? 1 : TS)
+  for (int j = TS - 2; j >= 0; j--) {
+    if (j == TS - 2) s = zr_get(j + 1);
+    else s = s * zr_get(j + 1);
+    auto s2 = f_sqr(s);
+    auto s3 = s2 * s;
+    F x = FieldIO<F>::load_strided(stg + (j * 2 * TW) * sstride, sstride);
+    F y = FieldIO<F>::load_strided(stg + (j * 2 * TW + TW) * sstride, sstride);
+    const auto xs = x * s2;
+    FieldIO<F>::store_strided(tab + (j * 2 * TW) * stride, stride, xs);
+    if constexpr (STAGED) FieldIO<F>::store_strided(stg + (j * 2 * TW) * sstride, sstride, xs);
+    FieldIO<F>::store_strided(tab + (j * 2 * TW + TW) * stride, stride, y * s3);
+  }
+  return D.Z * s;   // s = the product of all the ratios = the Z the last entry was built at
+}
+template <class C, int W, bool ZR_IN_TAB, class TABPTR>
+NCG_DI typename C::F mul_var_build_table(const Affine<typename C::F>& P, TABPTR tab, const int stride, bool& degenerate) {
+  return mul_var_build_table<C, W, ZR_IN_TAB, false>(P, tab, stride, tab, stride, degenerate);
+}
+
+// The end of a ladder lane: R on the isomorphic curve of the table (Z = Zg), negated when `negated` (the fused ladder's sign);
+// back to the curve, flagged lanes redone by mul_var_slow, then the Jacobian (JAC_OUT) or affine result written.  Returns whether
+// the lane went through mul_var_slow.
+template <class C, bool JAC_OUT>
+NCG_DI bool mul_var_finish(Jac<typename C::F> R, const typename C::F& Zg, bool negated, bool degenerate, bool trivial_zero,
+                           const uint32_t* __restrict__ pt_wire, const uint32_t* __restrict__ k_wire,
+                           uint32_t* __restrict__ out_wire, uint8_t* __restrict__ out_inf, bool active) {
+  using F = typename C::F;
+  constexpr int FW = FieldIO<F>::WORDS;
+  if constexpr (FusedLadder<C>::value) {
+    if (negated) R.Y = f_neg(R.Y);   // the one fix-up of the negated forms (f_neg keeps a literal zero literal)
+    // a lane whose result is known beforehand (P = O, where the table build sets the flag, or k = 0, whose last addition is
+    // R = -Q) must not send its wave through the complete ladder
+    degenerate = degenerate && !trivial_zero;
+  }
+  // back from the isomorphic curve, then to affine (weierstrass.ts:951-969 toAffine)
+  const bool ladder_inf = R.is_inf();  // tested before the product: not every field keeps 0 * Zg literal
+  R.Z = R.Z * Zg;
+  if (ladder_inf) R = Jac<F>::inf();
+  if (degenerate) R = mul_var_slow<C>(pt_wire, k_wire);  // small-order P, or an exceptional addition in the fused ladder: complete ladder instead
+  bool inf = trivial_zero || R.is_inf();
+  if constexpr (JAC_OUT) {
+    if (inf) R = Jac<F>::inf();
+    if (active) {
+      FieldIO<F>::store(out_wire, R.X);
+      FieldIO<F>::store(out_wire + FW, R.Y);
+      FieldIO<F>::store(out_wire + 2 * FW, R.Z);
+    }
+    return degenerate;
+  }
+  Affine<F> A = jac_to_affine(R, f_inv(R.Z));
+  if (inf) A = {F::zero(), F::zero()};
+  if (active) {
+    store_affine_wire<F>(out_wire, A);
+    *out_inf = inf ? 1 : 0;
+  }
+  return degenerate;
+}
+
 // Per-lane body.  `tab` is this lane's table base, consecutive words `stride` apart
 // (LDS: lds + lane, stride 64;  host unit test: a plain array, stride 1).
 // JAC_OUT: write the Jacobian result (X, Y, Z in storage format, Z = 0 for infinity) to
@@ -124,7 +226,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
                          TABPTR tab, const int stride) {
   using Cfg = MulVarCfg<C, W>;
   using F = typename C::F;
-  constexpr int FW = Cfg::FW, TW = Cfg::TW, TS = Cfg::TS, M = Cfg::M, NL = Cfg::NL;
+  constexpr int TW = Cfg::TW, M = Cfg::M, NL = Cfg::NL;
 
   Affine<F> P = load_affine_wire<F>(pt_wire);
   uint32_t k[8];
@@ -133,51 +235,8 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
   const bool trivial_zero = P.is_inf() || mp_is_zero<8>(k);
 
   // ---- table of odd multiples on the isomorphic curve ------------------------------------
-  // entry e, word w at tab[(e*2*FW + w)*stride]
-  F Zg;
   bool degenerate = false;
-  {
-    Jac<F> D = jac_dbl(Jac<F>{P.x, P.y, F::one()});
-    auto dz2 = f_sqr(D.Z);
-    auto dz3 = dz2 * D.Z;
-    Affine<F> Dc{D.X, D.Y};                 // 2P and P on the isomorphic curve, both at Z = 1: co-Z from the start
-    Affine<F> T{P.x * dz2, P.y * dz3};
-    F zr[ZR_IN_TAB ? 1 : TS];
-    auto zr_put = [&](int j, const F& v) {
-      if constexpr (ZR_IN_TAB) FieldIO<F>::store_strided(tab + (TS * 2 * TW + j * TW) * stride, stride, v);
-      else zr[j] = v;
-    };
-    auto zr_get = [&](int j) -> F {
-      if constexpr (ZR_IN_TAB) return FieldIO<F>::load_strided(tab + (TS * 2 * TW + j * TW) * stride, stride);
-      else return zr[j];
-    };
-    FieldIO<F>::store_strided(tab, stride, T.x);
-    FieldIO<F>::store_strided(tab + TW * stride, stride, T.y);
-    // with the Z-ratios in memory nothing here indexes a register array: keep the loops rolled (the
-    // unrolled build is 15 mixed additions of straight-line code in front of the ladder)
-#pragma unroll(ZR_IN_TAB ? 1 : TS)
-    for (int j = 1; j < TS; j++) {
-      F zj;
-      coz_addu(Dc, T, zj, degenerate);
-      zr_put(j, zj);
-      FieldIO<F>::store_strided(tab + (j * 2 * TW) * stride, stride, T.x);
-      FieldIO<F>::store_strided(tab + (j * 2 * TW + TW) * stride, stride, T.y);
-    }
-    // bring every entry to the last entry's Z
-    F s = F::one();
-#pragma unroll(ZR_IN_TAB ? 1 : TS)
-    for (int j = TS - 2; j >= 0; j--) {
-      if (j == TS - 2) s = zr_get(j + 1);
-      else s = s * zr_get(j + 1);
-      auto s2 = f_sqr(s);
-      auto s3 = s2 * s;
-      F x = FieldIO<F>::load_strided(tab + (j * 2 * TW) * stride, stride);
-      F y = FieldIO<F>::load_strided(tab + (j * 2 * TW + TW) * stride, stride);
-      FieldIO<F>::store_strided(tab + (j * 2 * TW) * stride, stride, x * s2);
-      FieldIO<F>::store_strided(tab + (j * 2 * TW + TW) * stride, stride, y * s3);
-    }
-    Zg = D.Z * s;   // s = the product of all the ratios = the Z the last entry was built at
-  }
+  const F Zg = mul_var_build_table<C, W, ZR_IN_TAB>(P, tab, stride, degenerate);
 
   // ---- scalar recoding ---------------------------------------------------------------------
   SignedOddWindows<NL, W, M> w1, w2;
@@ -288,33 +347,7 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
       if (w2.was_even) R = madd(R, qx * beta, qy, !neg2);
     }
   }
-  if constexpr (FUSED) {
-    if (sg) R.Y = f_neg(R.Y);   // the one fix-up of the negated forms (f_neg keeps a literal zero literal)
-    // a lane whose result is known beforehand (P = O, where the table build sets the flag, or k = 0, whose last addition is
-    // R = -Q) must not send its wave through the complete ladder
-    degenerate = degenerate && !trivial_zero;
-  }
-  // back from the isomorphic curve, then to affine (weierstrass.ts:951-969 toAffine)
-  const bool ladder_inf = R.is_inf();  // tested before the product: not every field keeps 0 * Zg literal
-  R.Z = R.Z * Zg;
-  if (ladder_inf) R = Jac<F>::inf();
-  if (degenerate) R = mul_var_slow<C>(pt_wire, k_wire);  // small-order P, or an exceptional addition in the fused ladder: complete ladder instead
-  bool inf = trivial_zero || R.is_inf();
-  if constexpr (JAC_OUT) {
-    if (inf) R = Jac<F>::inf();
-    if (active) {
-      FieldIO<F>::store(out_wire, R.X);
-      FieldIO<F>::store(out_wire + FW, R.Y);
-      FieldIO<F>::store(out_wire + 2 * FW, R.Z);
-    }
-    return;
-  }
-  Affine<F> A = jac_to_affine(R, f_inv(R.Z));
-  if (inf) A = {F::zero(), F::zero()};
-  if (active) {
-    store_affine_wire<F>(out_wire, A);
-    *out_inf = inf ? 1 : 0;
-  }
+  mul_var_finish<C, JAC_OUT>(R, Zg, FusedLadder<C>::value && sg, degenerate, trivial_zero, pt_wire, k_wire, out_wire, out_inf, active);
 }
 
 // Batched Jacobian -> affine (the reference's normalizeZ / FpInvertBatch, src/abstract/curve.ts:
@@ -324,52 +357,82 @@ NCG_DI void mul_var_lane(const uint32_t* __restrict__ pt_wire, const uint32_t* _
 // In the translation units that inline the field multiply the array is not promoted to registers and ends up in
 // scratch memory (592 bytes per lane for secp256k1, K = 16) - global-memory round trips in a dependent chain, which cost
 // this kernel 0.22 ms per 2^20 on most boxes and 0.42 ms on the boxes of the pool with a slow memory path.
-template <class C, int K, bool PRE_LDS = false>
-__global__ void __launch_bounds__(PRE_LDS ? 64 : 256) k_jac_batch_affine(const uint32_t* __restrict__ jac,
-                                                                         uint32_t* __restrict__ out_wire,
-                                                                         uint8_t* __restrict__ out_inf, int n) {
-  using F = typename C::F;
-  constexpr int FW = FieldIO<F>::WORDS, WW = FieldWire<F>::WORDS, TW = FieldIO<F>::LANE_WORDS;
-  extern __shared__ __attribute__((aligned(16))) uint32_t pre_lds[];
-  const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> LaneShift<C>::value;
-  const int i0 = t * K;
-  if (i0 >= n) return;
-  F pre[PRE_LDS ? 1 : K];   // pre[j] = product of the non-zero Z of points i0..i0+j-1
+// batch_inverse_lane is the lane routine: z(j) is element i0 + j (read twice), emit(j, zero, zi) takes its inverse; an element
+// that is the literal zero is left out of the products and reported as `zero` (zi is then not meaningful), so one such element
+// does not spoil the K - 1 around it.
+template <class F, int K, bool PRE_LDS, class PREPTR, class LOADZ, class EMIT>
+NCG_DI void batch_inverse_lane(PREPTR pre_lds, const int cnt, LOADZ z, EMIT emit) {
+  constexpr int TW = FieldIO<F>::LANE_WORDS;
+  F pre[PRE_LDS ? 1 : K];   // pre[j] = product of the non-zero elements 0..j-1
   auto pre_put = [&](int j, const F& v) {
-    if constexpr (PRE_LDS) FieldIO<F>::store_strided(pre_lds + threadIdx.x + (size_t)j * TW * 64, 64, v);
+    if constexpr (PRE_LDS) FieldIO<F>::store_strided(pre_lds + (size_t)j * TW * 64, 64, v);
     else pre[j] = v;
   };
   auto pre_get = [&](int j) -> F {
-    if constexpr (PRE_LDS) return FieldIO<F>::load_strided(pre_lds + threadIdx.x + (size_t)j * TW * 64, 64);
+    if constexpr (PRE_LDS) return FieldIO<F>::load_strided(pre_lds + (size_t)j * TW * 64, 64);
     else return pre[j];
   };
   F acc = F::one();
 #pragma unroll
   for (int j = 0; j < K; j++) {
     pre_put(j, acc);
-    if (i0 + j < n) {
-      F z = FieldIO<F>::load(jac + ((size_t)(i0 + j) * 3 + 2) * FW);
-      if (!z.is_zero()) acc = acc * z;
+    if (j < cnt) {
+      F zj = z(j);
+      if (!zj.is_zero()) acc = acc * zj;
     }
   }
   F inv = f_inv(acc);
 #pragma unroll
   for (int j = K - 1; j >= 0; j--) {
-    if (i0 + j < n) {
-      const uint32_t* p = jac + (size_t)(i0 + j) * 3 * FW;
-      F z = FieldIO<F>::load(p + 2 * FW);
-      const bool inf = z.is_zero();
-      Affine<F> A{F::zero(), F::zero()};
-      if (!inf) {
-        F zi = inv * pre_get(j);
-        inv = inv * z;
-        auto zi2 = f_sqr(zi);
-        A = {FieldIO<F>::load(p) * zi2, FieldIO<F>::load(p + FW) * zi2 * zi};
+    if (j < cnt) {
+      F zj = z(j);
+      const bool zero = zj.is_zero();
+      F zi = F::zero();
+      if (!zero) {
+        zi = inv * pre_get(j);
+        inv = inv * zj;
       }
-      store_affine_wire<F>(out_wire + (size_t)(i0 + j) * 2 * WW, A);
-      out_inf[i0 + j] = inf ? 1 : 0;
+      emit(j, zero, zi);
     }
   }
+}
+
+template <class C, int K, bool PRE_LDS = false>
+__global__ void __launch_bounds__(PRE_LDS ? 64 : 256) k_jac_batch_affine(const uint32_t* __restrict__ jac,
+                                                                         uint32_t* __restrict__ out_wire,
+                                                                         uint8_t* __restrict__ out_inf, int n) {
+  using F = typename C::F;
+  constexpr int FW = FieldIO<F>::WORDS, WW = FieldWire<F>::WORDS;
+  extern __shared__ __attribute__((aligned(16))) uint32_t pre_lds[];
+  const int t = (blockIdx.x * blockDim.x + threadIdx.x) >> LaneShift<C>::value;
+  const int i0 = t * K;
+  if (i0 >= n) return;
+  batch_inverse_lane<F, K, PRE_LDS>(
+      pre_lds + threadIdx.x, n - i0, [&](int j) -> F { return FieldIO<F>::load(jac + ((size_t)(i0 + j) * 3 + 2) * FW); },
+      [&](int j, bool inf, const F& zi) {
+        const uint32_t* p = jac + (size_t)(i0 + j) * 3 * FW;
+        Affine<F> A{F::zero(), F::zero()};
+        if (!inf) {
+          auto zi2 = f_sqr(zi);
+          A = {FieldIO<F>::load(p) * zi2, FieldIO<F>::load(p + FW) * zi2 * zi};
+        }
+        store_affine_wire<F>(out_wire + (size_t)(i0 + j) * 2 * WW, A);
+        out_inf[i0 + j] = inf ? 1 : 0;
+      });
+}
+
+// The same over one field element per item, in place: vals[i * stride] <- its inverse, a literal zero left as it is.
+template <class C, int K, bool PRE_LDS = false>
+__global__ void __launch_bounds__(PRE_LDS ? 64 : 256) k_fe_batch_inverse(uint32_t* __restrict__ vals, int stride, int n) {
+  using F = typename C::F;
+  extern __shared__ __attribute__((aligned(16))) uint32_t pre_lds[];
+  const int i0 = (blockIdx.x * blockDim.x + threadIdx.x) * K;
+  if (i0 >= n) return;
+  batch_inverse_lane<F, K, PRE_LDS>(
+      pre_lds + threadIdx.x, n - i0, [&](int j) -> F { return FieldIO<F>::load(vals + (size_t)(i0 + j) * stride); },
+      [&](int j, bool zero, const F& zi) {
+        if (!zero) FieldIO<F>::store(vals + (size_t)(i0 + j) * stride, zi);
+      });
 }
 
 // Batch normalisation of the reference's projective points (X, Y, Z) with x = X/Z, y = Y/Z -

@@ -4,13 +4,15 @@
 // kernels use the out-of-line multiply.  The curve twin CurveSecpI (curves.hpp) gives the kernels their own names -
 // both translation units ship their own code object - and selects the fused ladder formulas.
 #define NCG_MUL_INLINE 1
-#include "mulvar.hpp"
+#include "mulvar_pairsum.hpp"
 #include "host_api.hpp"
 
 namespace ncg {
 
 hipError_t mul_var_secp_inline(const uint32_t* pts, const uint32_t* scalars, uint32_t* out, uint8_t* out_inf, int n,
                                uint32_t* jac_tmp, hipStream_t st) {
+  // large batches: one addition per window from affine pair sums (mulvar_pairsum.hpp); its two extra launches do not pay below
+  if (n >= PAIRSUM_MIN_N) return launch_mul_var_pairsum<CurveSecpI, 4, 3, 16>(pts, scalars, out, out_inf, n, jac_tmp, st);
   return launch_mul_var_gtab<CurveSecpI, 4, 3, 16>(pts, scalars, out, out_inf, n, jac_tmp, st);  // W = 4, 3 waves/SIMD
 }
 

@@ -280,6 +280,14 @@ struct SignedOddWindows {
     mp_shl<NL>(r, W);
     return 2 * (int)b - ((1 << W) - 1);
   }
+  // the windows from the other end (LSB first), for a register the windows fill exactly
+  NCG_DI int pop_low() {
+    static_assert(W * M == 32 * NL, "pop_low: the windows must fill the register");
+    uint32_t b = r[0] & ((1u << W) - 1u);
+#pragma unroll
+    for (int i = 0; i < NL; i++) r[i] = (r[i] >> W) | (i + 1 < NL ? r[i + 1] << (32 - W) : 0u);
+    return 2 * (int)b - ((1 << W) - 1);
+  }
 };
 
 }  // namespace ncg
