@@ -9,6 +9,9 @@
 //   ed25519VerifyBatch(sigs, pks, ks, zip215: bool)  -> Uint8Array n (0 / 1)
 //   x25519(kind, scalars | null, rows)               -> Uint8Array n * 33 (32-byte results, then ok flags); kind 0 scalarMult
 //                                                       (scalars: n rows, or ONE row used for every u), 1 getPublicKey, 2 toMontgomery
+//   ed25519Sign(kind, keys[, flags, dom, msgs, lens]) -> kind 0 getPublicKey (keys: n x 32) -> Uint8Array n * 32; kind 1 sign (keys: n rows
+//                                                       or ONE, flags: 4 = prehash, dom, msgs back to back, lens: n LE uint32) ->
+//                                                       Uint8Array n * 65 (64-byte signatures, then ok flags)
 //   ed448(kind, a | null, b, c)                      -> kind 0 x448.scalarMult (a scalars: n rows or ONE, b u rows), 1 x448.getPublicKey (b):
 //                                                       Uint8Array n * 57 (56-byte results, then ok flags); 2 ed448 verify (a signatures,
 //                                                       b public keys, c challenges) -> Uint8Array n (0 / 1)
@@ -272,6 +275,54 @@ static napi_value X25519(napi_env env, napi_callback_info info) {
   else if (n && kind == 1) rc = ncg_x25519_base_batch(g_ctx, n, rows, out, out + n * 32);
   else if (n) rc = ncg_ed25519_to_montgomery_batch(g_ctx, n, rows, out, out + n * 32);
   if (rc != 0) return throw_native(env);
+  return res;
+}
+
+// Ed25519 signing on packed rows (ncg_ed25519_public_key_batch, ncg_ed25519_sign_batch).  kind 0 (secret keys n x 32) -> n x 32 public
+// keys.  kind 1 (keys, flags, dom, msgs, lens): keys n x 32 - or ONE row, which selects NCG_ED25519_SIGN_ONE_KEY; flags: the PREHASH bit;
+// dom: the domain prefix (may be empty); msgs: the messages back to back; lens: n message lengths as LE uint32 -> n x 64 signatures,
+// then n ok flags (a refused row is zero).
+static napi_value Ed25519Sign(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind, flags = 0;
+  uint8_t *keys, *dom = nullptr, *msgs = nullptr, *lens = nullptr, *out;
+  size_t kl, dl = 0, ml = 0, ll = 0;
+  if (argc < 2 || napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 1 || !get_u8(env, argv[1], &keys, &kl) || kl % 32 ||
+      (kind == 1 && (argc < 6 || napi_get_value_int32(env, argv[2], &flags) != napi_ok || !get_u8(env, argv[3], &dom, &dl) ||
+                     !get_u8(env, argv[4], &msgs, &ml) || !get_u8(env, argv[5], &lens, &ll) || ll % 4))) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: ed25519Sign(kind, keys of 32 bytes[, flags, dom, msgs, lens])");
+    return nullptr;
+  }
+  if (kind == 0) {
+    const size_t n = kl / 32;
+    napi_value res = make_u8(env, n * 32, &out);
+    if (!res) return nullptr;
+    if (n && ncg_ed25519_public_key_batch(g_ctx, n, keys, out) != 0) return throw_native(env);
+    return res;
+  }
+  const size_t n = ll / 4;
+  std::vector<uint64_t> off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t len;
+    memcpy(&len, lens + 4 * i, 4);
+    off[i + 1] = off[i] + len;
+  }
+  if (flags & ~NCG_ED25519_SIGN_PREHASH) {
+    napi_throw_error(env, nullptr, "noble-gpu: ed25519Sign: flags may hold the prehash bit (4) only");
+    return nullptr;
+  }
+  if (off[n] != ml || (kl != 32 * n && kl != 32)) {
+    napi_throw_error(env, nullptr, "arrays of messages and secret keys must have equal length");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n * 65, &out);
+  if (!res) return nullptr;
+  if (kl != 32 * n) flags |= NCG_ED25519_SIGN_ONE_KEY;
+  if (n && ncg_ed25519_sign_batch(g_ctx, n, keys, flags, dl ? dom : nullptr, dl, ml ? msgs : nullptr, off.data(), out, out + n * 64) != 0)
+    return throw_native(env);
   return res;
 }
 
@@ -1062,7 +1113,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

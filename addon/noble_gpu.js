@@ -8,6 +8,10 @@
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
 //   x25519ScalarMultBatch(items)           - array form of x25519.scalarMult / getSharedSecret (abstract/montgomery.ts:314-331);
 //   x25519GetPublicKeyBatch(secretKeys)      x25519.getPublicKey; ed25519ToMontgomeryBatch(publicKeys): ed25519.utils.toMontgomery
+//   ed25519GetPublicKeyBatch(secretKeys)   - array form of eddsa.getPublicKey (abstract/edwards.ts:870-897);
+//   ed25519SignBatch(items | {msgs, secretKey}, { context, prehash }) - eddsa.sign for ed25519, ed25519ctx (context given) and
+//                                            ed25519ph (prehash: true) (edwards.ts:908-930, ed25519.ts:146-223), hashes included, on the
+//                                            device; ed25519GetPublicKey / ed25519Sign: single-item forms with the reference's messages
 //   x448ScalarMultBatch(items), x448GetPublicKeyBatch(secretKeys) - x448.scalarMult / getPublicKey (ed448.ts:284-311);
 //   ed448VerifyBatch(items, { context, prehash }) - ed448 / ed448ph verify, the SHAKE256 challenge hashed here on the host
 //   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
@@ -538,6 +542,63 @@ function ed25519ToMontgomeryBatch(publicKeys) {
   init();
   return x25519Rows(native.x25519(2, null, K), n);
 }
+// ---- Ed25519 signing (abstract/edwards.ts:870-930, ed25519.ts:146-223): getPublicKey and sign for ed25519 / ed25519ctx / ed25519ph.
+// Both hashes, the two fixed-base multiplications and the scalar arithmetic run on the device; only the domain prefix is built here.
+// opts.context: a Uint8Array selects ed25519ctx (even an empty one - pass nothing for plain ed25519); opts.prehash: true selects
+// ed25519ph.  Batch forms return null for a row the device refused (r = 0 mod L); the single-item forms throw the reference's messages.
+function ed25519Dom(opts) {                     // ed25519_domain (ed25519.ts:148-160); plain ed25519 has no prefix (edwards.ts:857-862)
+  const prehash = !!(opts && opts.prehash), has = !!(opts && opts.context !== undefined), domain = has || prehash;
+  const ctx = has ? opts.context : new Uint8Array(0);
+  if (!(ctx instanceof Uint8Array)) throw new Error('"context" expected Uint8Array, got type=' + typeof ctx);
+  if (!domain) return { dom: new Uint8Array(0), flags: 0 };
+  if (ctx.length > 255) throw new Error('Context is too big');
+  const dom = new Uint8Array(34 + ctx.length);
+  dom.set(Buffer.from('SigEd25519 no Ed25519 collisions', 'ascii'), 0);
+  dom[32] = prehash ? 1 : 0;
+  dom[33] = ctx.length;
+  dom.set(ctx, 34);
+  return { dom, flags: prehash ? 4 : 0 };
+}
+function ed25519GetPublicKeyBatch(secretKeys) {
+  const n = secretKeys.length, S = new Uint8Array(32 * n);
+  secretKeys.forEach((k, i) => S.set(abytes32(k, 'secretKey'), 32 * i));
+  if (n === 0) return [];
+  init();
+  const out = native.ed25519Sign(0, S);
+  S.fill(0);
+  return Array.from({ length: n }, (_, i) => out.slice(32 * i, 32 * i + 32));
+}
+// items: [{msg, secretKey}] - or {msgs, secretKey}: ONE key signing many messages (the key crosses once)
+function ed25519SignBatch(items, opts) {
+  const { dom, flags } = ed25519Dom(opts);
+  const one = !Array.isArray(items);
+  const msgs = one ? items.msgs : items.map((it) => it.msg);
+  const n = msgs.length;
+  const K = new Uint8Array(one ? 32 : 32 * n), lens = new Uint8Array(4 * n), view = new DataView(lens.buffer);
+  let total = 0;
+  for (let i = 0; i < n; i++) {
+    const m = msgs[i];
+    if (!(m instanceof Uint8Array)) throw new Error('"message" expected Uint8Array, got type=' + typeof m);
+    if (!one) K.set(abytes32(items[i].secretKey, 'secretKey'), 32 * i);
+    view.setUint32(4 * i, m.length, true);
+    total += m.length;
+  }
+  if (one) K.set(abytes32(items.secretKey, 'secretKey'), 0);
+  if (n === 0) return [];
+  const blob = new Uint8Array(total);
+  for (let i = 0, at = 0; i < n; at += msgs[i++].length) blob.set(msgs[i], at);
+  init();
+  const out = native.ed25519Sign(1, K, flags, dom, blob, lens);
+  K.fill(0);
+  return Array.from({ length: n }, (_, i) => (out[64 * n + i] === 1 ? out.slice(64 * i, 64 * i + 64) : null));
+}
+function ed25519GetPublicKey(secretKey) { return ed25519GetPublicKeyBatch([secretKey])[0]; }
+function ed25519Sign(msg, secretKey, opts) {
+  const r = ed25519SignBatch([{ msg, secretKey }], opts)[0];
+  if (r === null) throw new Error('invalid scalar: expected 1 <= sc < curve.n');   // BASE.multiply(0), edwards.ts:920-924
+  return r;
+}
+
 // ---- X448 and Ed448 verification (ed448.ts; abstract/montgomery.ts:247-420, abstract/edwards.ts:942-989) ----------------------
 // The same buffers-in / buffers-out convention as the X25519 calls.  Hashing stays on the host: the challenge
 // k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114) mod n and the ed448ph prehash use crypto.createHash('shake256').
@@ -1084,6 +1145,7 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    PointSet, uploadPoints, uploadEncoded, interleavedMSMUnsafe, pippengerResident, multiplyUnsafeBatchResident, ed25519VerifyBatchDevice, ecdsaVerifyBatch, ecdsaVerifyBatchMsgs, schnorrVerifyBatch, ecdsaRecoverBatch,
                    fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, registerBls, pairingBatch, blsVerifyBatch,
                    x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery,
+                   ed25519GetPublicKeyBatch, ed25519SignBatch, ed25519GetPublicKey, ed25519Sign,
                    x448ScalarMultBatch, x448GetPublicKeyBatch, ed448VerifyBatch,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,

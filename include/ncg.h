@@ -447,6 +447,34 @@ int ncg_ed25519_challenge_batch_dev(ncg_ctx* ctx, size_t n, const void* sig64_de
                                     const void* msgs_dev, const uint64_t* msg_off_dev, void* out_k32_dev,
                                     void* stream);
 
+/* ---- Ed25519 signing: eddsa.getPublicKey, getExtendedPublicKey and sign (edwards.ts:870-930, ed25519.ts:146-223) ----------
+ * seed32: the 32-byte secret keys.  An expanded key row is 96 bytes: scalar (32 bytes LE, the clamped head of SHA-512(seed)
+ * reduced mod L) || prefix (the second half of the hash) || A (the public key); ncg_ed25519_expand_key_batch writes such rows
+ * for repeated use with NCG_ED25519_SIGN_EXPANDED.  Key rows, public keys and signatures are read and written as 32-bit words:
+ * device pointers to them must be 4-byte aligned.
+ *
+ * ncg_ed25519_sign_batch: out_sig64[i] = R || S of message i under key i (or under the one key row, NCG_ED25519_SIGN_ONE_KEY)
+ * and out_ok[i] = 1; 64 zero bytes and out_ok[i] = 0 where the nonce r is 0 mod L and the reference throws.  msgs / msg_off
+ * as for ncg_ed25519_verify_batch_msgs.  dom: the domain prefix of both hashes, dom_len <= NCG_ED25519_DOM_MAX bytes, a HOST
+ * pointer in both forms (it is the same for the whole call; NULL only with dom_len 0): empty for ed25519,
+ * "SigEd25519 no Ed25519 collisions" || phflag || len(ctx) || ctx for ed25519ctx (phflag 0) and ed25519ph (phflag 1).
+ * NCG_ED25519_SIGN_PREHASH signs SHA-512(M) in place of M (ed25519ph).  The secret scalars never select an address or a branch
+ * (a table walk that reads every entry); this is not a constant-time claim.  Device and staging memory
+ * that held keys, prefixes or nonces is cleared on the call's stream before the call returns.
+ * Unknown flag bits, dom_len above the maximum, a NULL required buffer: NCG_ERR_INVALID_ARG; n = 0 returns NCG_OK. */
+#define NCG_ED25519_SIGN_EXPANDED 1   /* keys are 96-byte expanded rows, not 32-byte seeds */
+#define NCG_ED25519_SIGN_ONE_KEY  2   /* one key row serves all n messages */
+#define NCG_ED25519_SIGN_PREHASH  4   /* hash each message with SHA-512 first (ed25519ph) */
+#define NCG_ED25519_DOM_MAX 289       /* 32 + 2 + 255 */
+int ncg_ed25519_public_key_batch(ncg_ctx* ctx, size_t n, const void* seed32, void* out_pk32);
+int ncg_ed25519_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed32_dev, void* out_pk32_dev, void* stream);
+int ncg_ed25519_expand_key_batch(ncg_ctx* ctx, size_t n, const void* seed32, void* out_key96);
+int ncg_ed25519_expand_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed32_dev, void* out_key96_dev, void* stream);
+int ncg_ed25519_sign_batch(ncg_ctx* ctx, size_t n, const void* keys, int flags, const void* dom, size_t dom_len, const void* msgs,
+                           const uint64_t* msg_off, void* out_sig64, uint8_t* out_ok);
+int ncg_ed25519_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* keys_dev, int flags, const void* dom, size_t dom_len,
+                               const void* msgs_dev, const uint64_t* msg_off_dev, void* out_sig64_dev, uint8_t* out_ok_dev, void* stream);
+
 /* ---- X25519 (RFC 7748) and the Ed25519 -> Curve25519 key conversion ---------------------------------
  * Every row is 32 bytes as on the wire (little-endian), 4-byte aligned; out32[i] is the 32-byte result and out_ok[i] = 1,
  * or 32 zero bytes and out_ok[i] = 0 where the reference throws.  n = 0 returns NCG_OK and touches nothing.

@@ -20,6 +20,8 @@ FIELD_BN254_FR = 5
 POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
 X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
+ED25519_SIGN_EXPANDED, ED25519_SIGN_ONE_KEY, ED25519_SIGN_PREHASH = 1, 2, 4   # ncg_ed25519_sign_batch flags
+ED25519_DOM_MAX = 289
 RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
 # ncg_fp12_batch ops (enum ncg_fp12_op); a GT element is GT_BYTES on the wire
 (FP12_MUL, FP12_SQR, FP12_INV, FP12_CONJUGATE, FP12_FROBENIUS1, FP12_FROBENIUS2, FP12_FROBENIUS3, FP12_CYCLOTOMIC_SQR, FP12_MUL014,
@@ -149,6 +151,12 @@ _OPTIONAL_PROTOS = {
     "ncg_ed25519_verify_batch_msgs": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp],
     "ncg_ed25519_verify_batch_msgs_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "ncg_ed25519_challenge_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_ed25519_public_key_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed25519_public_key_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed25519_expand_key_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed25519_expand_key_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed25519_sign_batch": [_vp, _sz, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed25519_sign_batch_dev": [_vp, _sz, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "ncg_x25519_batch": [_vp, _sz, _vp, _vp, _i32, _vp, _vp],
     "ncg_x25519_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
     "ncg_x25519_base_batch": [_vp, _sz, _vp, _vp, _vp],
@@ -641,6 +649,41 @@ class Engine:
             self._check(self.lib.ncg_ed25519_verify_batch(self.h, n, sigs.ctypes.data, pks.ctypes.data,
                                                           ks.ctypes.data, 1 if zip215 else 0, ok.ctypes.data))
         return ok.astype(bool)
+
+    # ---- Ed25519 signing: seeds uint8 [n, 32], expanded key rows [n, 96] (scalar || prefix || A), signatures [n, 64] ----------
+    def ed25519_public_key_batch(self, seeds):
+        """eddsa.getPublicKey per row"""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((seeds.shape[0], 32), dtype=np.uint8)
+        if seeds.shape[0]:
+            self._check(self.lib.ncg_ed25519_public_key_batch(self.h, seeds.shape[0], seeds.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed25519_expand_key_batch(self, seeds):
+        """getExtendedPublicKey per row, as the 96-byte rows that ed25519_sign_batch takes with expanded=True"""
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((seeds.shape[0], 96), dtype=np.uint8)
+        if seeds.shape[0]:
+            self._check(self.lib.ncg_ed25519_expand_key_batch(self.h, seeds.shape[0], seeds.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed25519_sign_batch(self, keys, msgs_blob, msg_off, dom=b"", expanded=False, one_key=False, prehash=False):
+        """keys: seeds [n, 32] or expanded rows [n, 96] (ONE row with one_key); msgs_blob / msg_off as for
+        ed25519_verify_batch_msgs; dom: the domain prefix of ed25519ctx / ed25519ph -> (signatures uint8 [n, 64], ok bool [n])."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, 96 if expanded else 32)
+        blob = np.ascontiguousarray(msgs_blob, dtype=np.uint8).reshape(-1)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint64).reshape(-1)
+        n = off.shape[0] - 1
+        if n < 0 or keys.shape[0] != (1 if one_key else n):
+            raise ValueError("arrays of keys and message offsets must have matching lengths")
+        dom = bytes(dom)
+        flags = (ED25519_SIGN_EXPANDED if expanded else 0) | (ED25519_SIGN_ONE_KEY if one_key else 0) | (ED25519_SIGN_PREHASH if prehash else 0)
+        sig, ok = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed25519_sign_batch(self.h, n, keys.ctypes.data, flags, dom if dom else None, len(dom),
+                                                        blob.ctypes.data if blob.size else None, off.ctypes.data, sig.ctypes.data,
+                                                        ok.ctypes.data))
+        return sig, ok.astype(bool)
 
     # ---- X25519 / toMontgomery: rows of 32 bytes -> (out uint8 [n, 32], ok bool [n]); a refused row is zero ----------------
     def x25519_batch(self, scalars, us, one_scalar=False):

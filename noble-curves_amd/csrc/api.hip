@@ -364,6 +364,8 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->mul_ws) (void)hipFree(ctx->mul_ws);
   if (ctx->ed_btab) (void)hipFree(ctx->ed_btab);
   if (ctx->ed_ks) (void)hipFree(ctx->ed_ks);
+  if (ctx->ed_scan_tab) (void)hipFree(ctx->ed_scan_tab);
+  if (ctx->ed_sign_ws) (void)hipFree(ctx->ed_sign_ws);
   if (ctx->ecdsa_ws) (void)hipFree(ctx->ecdsa_ws);
   for (int i = 0; i < 4; i++)
     if (ctx->base_tab[i]) (void)hipFree(ctx->base_tab[i]);
@@ -1538,6 +1540,126 @@ int ncg_ed25519_verify_batch_msgs(ncg_ctx* ctx, size_t n, const void* sig64, con
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ed25519_verify_batch_msgs_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(msg), hc.dev<const uint64_t>(off), zip215,
                                                      hc.dev<uint8_t>(ok), ctx->stream));
+}
+
+// ---- Ed25519 signing (ed25519_sign.hip): getPublicKey, getExtendedPublicKey and sign for ed25519 / ed25519ctx / ed25519ph.
+// Expanded rows, public keys and signatures are read and written as 32-bit words (seeds byte by byte): a device pointer to them must be 4-byte
+// aligned and is refused otherwise (the host forms stage every buffer at a 256-byte boundary).  The workspace holds scalars,
+// prefixes and nonces during a call: it is cleared on the call's stream before the call returns, and so is the staged copy of the
+// keys of a host form.
+static int ensure_ed_scan_table(ncg_ctx* ctx) {
+  if (ctx->ed_scan_tab) return NCG_OK;
+  std::vector<uint32_t> host(ncg::ed25519_scan_table_words());
+  ncg::ed25519_build_scan_table(host.data());
+  uint32_t* tab = nullptr;
+  NCG_HIP(ctx, hipMalloc((void**)&tab, host.size() * 4));
+  hipError_t e = hipMemcpy(tab, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    return set_err(ctx, NCG_ERR_HIP, "noble-gpu: uploading the ed25519 signing table failed: %s", hipGetErrorString(e));
+  }
+  ctx->ed_scan_tab = tab;
+  return NCG_OK;
+}
+constexpr int ED_SIGN_FLAGS = NCG_ED25519_SIGN_EXPANDED | NCG_ED25519_SIGN_ONE_KEY | NCG_ED25519_SIGN_PREHASH;
+static Rule ed_sign_rule(ncg_ctx* ctx, const char* op, int flags, const void* dom, size_t dom_len, std::initializer_list<const void*> word_rows) {
+  int rc = NCG_OK;
+  if (flags & ~ED_SIGN_FLAGS) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
+  else if (dom_len > NCG_ED25519_DOM_MAX)
+    rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: dom_len %zu above %d", op, dom_len, NCG_ED25519_DOM_MAX);
+  else if (dom_len && !dom) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer (dom)", op);
+  else
+    for (const void* p : word_rows)
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: key and signature rows must be 4-byte aligned", op);
+  return {op, rc};
+}
+static int ed_sign_ws(ncg_ctx* ctx, size_t words) {
+  return ncg_grow_buf(ctx, &ctx->ed_sign_ws, &ctx->ed_sign_ws_bytes, words * 4, words * 4 + (words >> 1) + 4096, GrowWait::device);
+}
+// seeds (read byte by byte) -> public keys (rows false: 8 words per row at `out`) or expanded rows (rows true: 24 words per row)
+static int ed_expand_dev(ncg_ctx* ctx, const char* op, size_t n, const void* seed32_dev, void* out_dev, bool rows, void* stream) {
+  NCG_BEGIN(ctx, ed_sign_rule(ctx, op, 0, nullptr, 0, {out_dev}), n, seed32_dev, out_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_ed_scan_table(ctx)) return rc;
+  uint32_t* keys = (uint32_t*)out_dev;
+  if (!rows) {  // scalar || prefix stay in the workspace, only A goes out
+    if (int rc = ed_sign_ws(ctx, n * 24)) return rc;
+    keys = (uint32_t*)ctx->ed_sign_ws;
+  }
+  hipError_t e = ncg::ed25519_expand_batch(ctx->ed_scan_tab, (const uint8_t*)seed32_dev, keys, rows ? keys + 16 : (uint32_t*)out_dev, rows ? 24 : 8,
+                                           (int)n, st);
+  if (!rows) (void)hipMemsetAsync(ctx->ed_sign_ws, 0, n * 96, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_ed25519_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed32_dev, void* out_pk32_dev, void* stream) {
+  return ed_expand_dev(ctx, "ed25519_public_key_batch", n, seed32_dev, out_pk32_dev, false, stream);
+}
+int ncg_ed25519_expand_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed32_dev, void* out_key96_dev, void* stream) {
+  return ed_expand_dev(ctx, "ed25519_expand_key_batch", n, seed32_dev, out_key96_dev, true, stream);
+}
+// the staged copy of the keys of a host form, cleared on the context's stream on every way out once anything was enqueued
+static void ed_clear_staged(HostCall& hc, int slot, size_t bytes) {
+  if (hc.enqueued && bytes) (void)hipMemsetAsync(hc.dev(slot), 0, bytes, hc.ctx->stream);
+}
+static int ed_expand_host(ncg_ctx* ctx, const char* op, size_t n, const void* seed32, void* out, size_t out_bytes) {
+  NCG_BEGIN(ctx, no_rule(op), n, seed32, out);
+  HostCall hc(ctx);
+  const int s = hc.in(seed32, n * 32), o = hc.out(out, n * out_bytes);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, s, n * 32);
+    return rc;
+  }
+  const int rc = out_bytes == 32 ? ncg_ed25519_public_key_batch_dev(ctx, n, hc.dev(s), hc.dev(o), ctx->stream)
+                                 : ncg_ed25519_expand_key_batch_dev(ctx, n, hc.dev(s), hc.dev(o), ctx->stream);
+  ed_clear_staged(hc, s, n * 32);
+  const int frc = hc.finish(rc);
+  if (out_bytes == 96 && frc == NCG_OK) (void)hipMemsetAsync(hc.dev(o), 0, n * 96, ctx->stream);   // after the copy back, same stream
+  return frc;
+}
+int ncg_ed25519_public_key_batch(ncg_ctx* ctx, size_t n, const void* seed32, void* out_pk32) {
+  return ed_expand_host(ctx, "ed25519_public_key_batch", n, seed32, out_pk32, 32);
+}
+int ncg_ed25519_expand_key_batch(ncg_ctx* ctx, size_t n, const void* seed32, void* out_key96) {
+  return ed_expand_host(ctx, "ed25519_expand_key_batch", n, seed32, out_key96, 96);
+}
+
+int ncg_ed25519_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* keys_dev, int flags, const void* dom, size_t dom_len, const void* msgs_dev,
+                               const uint64_t* msg_off_dev, void* out_sig64_dev, uint8_t* out_ok_dev, void* stream) {
+  // seeds are read byte by byte; expanded rows and signatures as words
+  NCG_BEGIN(ctx, ed_sign_rule(ctx, "ed25519_sign_batch", flags, dom, dom_len, {(flags & NCG_ED25519_SIGN_EXPANDED) ? keys_dev : nullptr, out_sig64_dev}),
+            n, keys_dev, msg_off_dev, out_sig64_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_ed_scan_table(ctx)) return rc;
+  const int expanded = (flags & NCG_ED25519_SIGN_EXPANDED) != 0, one_key = (flags & NCG_ED25519_SIGN_ONE_KEY) != 0;
+  const int prehash = (flags & NCG_ED25519_SIGN_PREHASH) != 0;
+  const size_t words = ncg::ed25519_sign_ws_words((int)n, expanded ? 0 : (one_key ? 1 : (int)n), prehash);
+  if (int rc = ed_sign_ws(ctx, words)) return rc;
+  hipError_t e = ncg::ed25519_sign_batch(ctx->ed_scan_tab, keys_dev, expanded, one_key, prehash, (const uint8_t*)dom, (uint32_t)dom_len,
+                                         (const uint8_t*)msgs_dev, msg_off_dev, (uint32_t*)out_sig64_dev, out_ok_dev, (int)n,
+                                         (uint32_t*)ctx->ed_sign_ws, st);
+  (void)hipMemsetAsync(ctx->ed_sign_ws, 0, words * 4, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_ed25519_sign_batch(ncg_ctx* ctx, size_t n, const void* keys, int flags, const void* dom, size_t dom_len, const void* msgs,
+                           const uint64_t* msg_off, void* out_sig64, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed_sign_rule(ctx, "ed25519_sign_batch", flags, dom, dom_len, {}), n, keys, msg_off, out_sig64, out_ok);
+  const size_t kbytes = ((flags & NCG_ED25519_SIGN_ONE_KEY) ? 1 : n) * ((flags & NCG_ED25519_SIGN_EXPANDED) ? 96 : 32);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int k = hc.in(keys, kbytes);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed25519_sign_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int sig = hc.out(out_sig64, n * 64), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, kbytes);
+    return rc;
+  }
+  const int rc = ncg_ed25519_sign_batch_dev(ctx, n, hc.dev(k), flags, dom, dom_len, hc.dev(msg), hc.dev<const uint64_t>(off), hc.dev(sig),
+                                            hc.dev<uint8_t>(ok), ctx->stream);
+  ed_clear_staged(hc, k, kbytes);
+  return hc.finish(rc);
 }
 
 // ---- secp256k1 ECDSA batch verify (weierstrass.ts:1571-1620): SEC1 decode of the keys, the scalar side

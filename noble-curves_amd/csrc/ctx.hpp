@@ -46,6 +46,11 @@ struct ncg_ctx {
   uint32_t* ed_btab = nullptr;  // ed25519 base-point table (device)
   void* ed_ks = nullptr;        // ed25519 challenge scalars of the message-taking verify (device)
   size_t ed_ks_bytes = 0;
+  // ed25519 signing (ed25519_sign.hip): the 4-bit window table of B, and the workspace of one call (dom, nonces, prehashes, expanded
+  // keys) - it holds secrets during a call and is cleared on the call's stream before the call returns
+  uint32_t* ed_scan_tab = nullptr;
+  void* ed_sign_ws = nullptr;
+  size_t ed_sign_ws_bytes = 0;
   void* ecdsa_ws = nullptr;     // ECDSA batch verify: decoded keys, u1 / u2, partial points (device)
   size_t ecdsa_ws_bytes = 0;
   uint32_t* base_tab[4] = {nullptr, nullptr, nullptr, nullptr};  // fixed-base tables per curve (device)

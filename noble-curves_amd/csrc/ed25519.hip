@@ -480,20 +480,23 @@ static EdExt<FEd> ed_base_point() {  // src/ed25519.ts:57-65 Gx, Gy
 // fixed-base table for k_ed_mul_base, computed on the host with the same templates: 33 x 128
 // entries of 24 words, entry [w][j] = (2j+1) 2^(8w) B; one batched inversion for all 4224 points
 size_t ed25519_fixed_table_words() { return (size_t)ED_FB_M * ED_FB_T * ED_AFF_NIELS_WORDS; }
-void ed25519_build_fixed_table(uint32_t* out) {
+void ed25519_build_fixed_table(uint32_t* out) { ed25519_build_window_table(out, ED_FB_W, ED_FB_M); }
+// the same table at any window width: `windows` rows of 2^(w_bits - 1) entries, entry [w][j] = (2j+1) 2^(w_bits w) B
+// (ed25519_sign.hip walks one of 4-bit windows)
+void ed25519_build_window_table(uint32_t* out, int w_bits, int windows) {
   using F = FEd;
   const F d2 = EdConsts::d2();
-  const int NT = ED_FB_M * ED_FB_T;
+  const int T = 1 << (w_bits - 1), NT = windows * T;
   std::vector<EdExt<F>> pts(NT);
   EdExt<F> bw = ed_base_point();
-  for (int w = 0; w < ED_FB_M; w++) {
+  for (int w = 0; w < windows; w++) {
     EdNielsProj<F> n2 = ed_to_niels(ed_dbl(bw), d2);
     EdExt<F> cur = bw;
-    for (int j = 0; j < ED_FB_T; j++) {
+    for (int j = 0; j < T; j++) {
       if (j > 0) cur = ed_add_niels(cur, n2, false);
-      pts[(size_t)w * ED_FB_T + j] = cur;
+      pts[(size_t)w * T + j] = cur;
     }
-    for (int d = 0; d < ED_FB_W; d++) bw = ed_dbl(bw);
+    for (int d = 0; d < w_bits; d++) bw = ed_dbl(bw);
   }
   std::vector<F> pre(NT);
   F acc = F::one();

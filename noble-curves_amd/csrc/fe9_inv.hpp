@@ -175,8 +175,10 @@ NCG_DI void fe9_ds_batch(int32_t& zeta, int32_t (&f)[9], int32_t (&g)[9], int32_
   fe9_ds_fence();
 }
 
-// 1 / a (value of modular.ts:159-182 invert; 0 -> 0), the canonical residue in canonical limbs
-template <class PR, int A>
+// 1 / a (value of modular.ts:159-182 invert; 0 -> 0), the canonical residue in canonical limbs.  FIXED: always FE9_DS_CAP batches, no
+// early exit - for a secret input (ed25519_sign.hpp), so that the batch count does not follow the value; steps taken with g = 0 change
+// nothing, so the result is the same
+template <class PR, int A, bool FIXED = false>
 NCG_DI Fe9<PR, 1> fe9_inv_divsteps(const Fe9<PR, A>& a_in) {
   uint32_t c[10];
   {
@@ -205,7 +207,9 @@ NCG_DI Fe9<PR, 1> fe9_inv_divsteps(const Fe9<PR, A>& a_in) {
     gnz = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) gnz |= (uint32_t)g[i];
-    if (!fe9_wave_any(gnz != 0)) break;
+    if constexpr (!FIXED) {
+      if (!fe9_wave_any(gnz != 0)) break;
+    }
   }
   if (gnz != 0) return f_inv_fermat(a_in);  // the cap's way out (never reached by an input below 2^256)
   // f = +-1 (or p for x = 0): the inverse is d times the sign of f.  2p + (+-d) lies in (0, 4p): carry it into unsigned limbs

@@ -185,6 +185,31 @@ hipError_t ed25519_mul_base_proj(const uint32_t* table, const uint32_t* scalars,
 void ed25519_mul_var_host(const uint32_t* pt, const uint32_t* k, uint32_t* out, uint8_t* out_inf);
 bool ed25519_verify_host(const uint32_t* sig, const uint32_t* pk, const uint32_t* k, const uint32_t* btab, bool zip215);
 
+// Ed25519 signing (ed25519_sign.hip).  table: device copy of ed25519_build_scan_table's output (ed25519_scan_table_words() words),
+// [w][j] = (2 j + 1) 2^(W w) B from ed25519_build_window_table (ed25519.hip; entries of 27 stored words).  Expanded key rows are
+// 24 LE words: scalar || prefix || A.  ed25519_expand_batch: see ed25519_sign.hip.  ed25519_sign_batch: keys are seeds (32 bytes) or
+// expanded rows, one per message or one in all; dom_host is a HOST pointer; msgs / msg_off as for ed25519_challenge_batch; sigs: 16
+// words per row; ws: ed25519_sign_ws_words(n, rows to expand, prehash) words of device memory that hold secrets afterwards.
+constexpr int ED25519_DOM_MAX = 289;      // 32 + 2 + 255
+constexpr int ED_SIGN_DOM_WORDS = 80;     // dom at the head of the workspace
+void ed25519_build_window_table(uint32_t* out_words, int w_bits, int windows);
+size_t ed25519_scan_table_words();
+void ed25519_build_scan_table(uint32_t* out_words);
+hipError_t ed25519_mul_base_scan_batch(const uint32_t* table, const uint32_t* scalars, int in_stride, uint32_t* out, int out_stride, int n,
+                                       hipStream_t st);
+hipError_t ed25519_expand_batch(const uint32_t* table, const uint8_t* seeds, uint32_t* keys, uint32_t* out_a, int out_stride, int n,
+                                hipStream_t st);
+size_t ed25519_sign_ws_words(int n, int nkeys_to_expand, int prehash);
+hipError_t ed25519_sign_batch(const uint32_t* table, const void* keys, int expanded, int one_key, int prehash, const uint8_t* dom_host,
+                              uint32_t dom_len, const uint8_t* msgs, const uint64_t* msg_off, uint32_t* sigs, uint8_t* ok, int n, uint32_t* ws,
+                              hipStream_t st);
+void ed25519_mul_base_scan_host(const uint32_t* table, const uint32_t* scalars, uint32_t* out, int n);
+void ed25519_expand_host(const uint32_t* table, const uint8_t* seeds, uint32_t* keys, int n);
+void ed25519_sign_host(const uint32_t* table, const void* key, int expanded, int prehash, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg,
+                       uint64_t len, const uint32_t* r_in, uint32_t* sig, uint8_t* ok);
+void sha512_segments_host(const uint8_t* dom, uint32_t dom_len, const uint8_t* a32, const uint8_t* b32, const uint8_t* msg, uint64_t len,
+                          uint8_t* out64);
+
 // X25519 and ed25519.utils.toMontgomery (x25519.hip): rows of 8 LE words (32 bytes) in and out, out_ok = 0 and a zero row where
 // the reference throws.  one_scalar: `scalars` is one row used for every item.  x25519_base_batch walks the fixed-base Edwards
 // table of ed25519_build_fixed_table; tmp: x25519_base_tmp_words(n) words of device memory.

@@ -27,6 +27,7 @@
 #include "pairing.hip"
 #include "ed448.hip"
 #include "decaf448.hip"
+#include "ed25519_sign.hip"
 
 using namespace ncg;
 
@@ -339,6 +340,44 @@ int ht_ed25519_to_montgomery(const uint32_t* pk, uint32_t* out, uint8_t* ok, int
   return 0;
 }
 int ht_x25519_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return x25519_check_host(op, variant, a, b, out); }
+
+// Ed25519 signing on the CPU twins of ed25519_sign.hip.  Rows are 4-byte aligned: seeds 32 bytes, expanded keys 96 (scalar || prefix ||
+// A), scalars and compressed points 8 LE words, signatures 64 bytes.  flags as ncg_ed25519_sign_batch (ONE_KEY has no meaning for one
+// row and is refused); -1 for unknown flag bits or dom_len above the maximum.
+static const uint32_t* ht_ed_scan_table() {
+  static const std::vector<uint32_t> tab = [] {
+    std::vector<uint32_t> t(ed25519_scan_table_words());
+    ed25519_build_scan_table(t.data());
+    return t;
+  }();
+  return tab.data();
+}
+int ht_ed25519_expand(const uint8_t* seeds, uint32_t* out_key96, int n) {
+  ed25519_expand_host(ht_ed_scan_table(), seeds, out_key96, n);
+  return 0;
+}
+int ht_ed25519_sign_with_r(const void* key, int flags, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg, uint64_t len, const uint32_t* r,
+                           uint32_t* out_sig64, uint8_t* out_ok) {
+  if ((flags & ~(NCG_ED25519_SIGN_EXPANDED | NCG_ED25519_SIGN_PREHASH)) || dom_len > NCG_ED25519_DOM_MAX) return -1;
+  ed25519_sign_host(ht_ed_scan_table(), key, flags & NCG_ED25519_SIGN_EXPANDED, flags & NCG_ED25519_SIGN_PREHASH, dom, dom_len, msg, len, r,
+                    out_sig64, out_ok);
+  return 0;
+}
+int ht_ed25519_sign(const void* key, int flags, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg, uint64_t len, uint32_t* out_sig64,
+                    uint8_t* out_ok) {
+  return ht_ed25519_sign_with_r(key, flags, dom, dom_len, msg, len, nullptr, out_sig64, out_ok);
+}
+// out[i] = compress(scalars[i] B) by the uniform-scan walk
+int ht_ed_mul_base_scan(const uint32_t* scalars, uint32_t* out, int n) {
+  ed25519_mul_base_scan_host(ht_ed_scan_table(), scalars, out, n);
+  return 0;
+}
+// SHA-512(dom || a32 || b32 || msg); a32 / b32 may be NULL (segment left out)
+int ht_sha512_segments(const uint8_t* dom, uint32_t dom_len, const uint8_t* a32, const uint8_t* b32, const uint8_t* msg, uint64_t len,
+                       uint8_t* out64) {
+  sha512_segments_host(dom, dom_len, a32, b32, msg, len, out64);
+  return 0;
+}
 
 // X448 and Ed448 on the CPU twins of ed448.hip: 56-byte rows as 14 LE words, encodings 57 packed bytes, signatures 114, affine
 // points 28 words; flags as ncg_x448_batch / ncg_ed448_mul_batch.  u = NULL / enc = NULL: the base point.  ht_fe448_op: one row of

@@ -8,6 +8,11 @@ the reference) and the curve arithmetic both run in HIP kernels (`ncg_ed25519_ve
 
 `toMontgomery` / `toMontgomery_batch` (ed25519.utils.toMontgomery: the X25519 key of an Ed25519 public key) run on the device
 (`ncg_ed25519_to_montgomery_batch`); `toMontgomerySecret` is one SHA-512 on the host.
+
+Signing (edwards.ts:870-930): `getPublicKey[_batch]`, `getExtendedPublicKey`, `expand_keys`, `sign`, `sign_batch` run on the device,
+hashes included (`ncg_ed25519_public_key_batch`, `ncg_ed25519_expand_key_batch`, `ncg_ed25519_sign_batch`); the namespaces
+`ed25519ctx` and `ed25519ph` (src/ed25519.ts:146-223) add the domain prefix and the prehash flag.  `verify` / `verify_batch` take
+`context=` / `prehash=`: their domain-separated challenge is hashed here and goes through the k32 entry point.
 """
 import hashlib
 
@@ -32,13 +37,23 @@ def challenge(r_bytes, pk_bytes, msg):
     return int.from_bytes(hashlib.sha512(bytes(r_bytes) + bytes(pk_bytes) + bytes(msg)).digest(), "little") % L
 
 
-def verify_batch(sigs, msgs, publicKeys, zip215=True, engine=None, hash_on_device=True):
-    """List of booleans, one per (signature, message, publicKey) triple."""
+def verify_batch(sigs, msgs, publicKeys, zip215=True, engine=None, hash_on_device=True, context=None, prehash=False):
+    """List of booleans, one per (signature, message, publicKey) triple.  A non-empty `context` verifies as ed25519ctx and
+    `prehash=True` as ed25519ph (the reference's plain `ed25519.verify` throws for a context; here the keywords select the variant,
+    and an empty context is plain ed25519 as it is there): the domain-separated challenge is computed with hashlib and goes through
+    the k32 entry point.  ed25519ctx with an EMPTY context is `ed25519ctx.verify_batch`."""
+    return _verify_rows(sigs, msgs, publicKeys, zip215, engine, hash_on_device,
+                        _dom(context, prehash, prehash or (context is not None and len(context) > 0)), prehash)
+
+
+def _verify_rows(sigs, msgs, publicKeys, zip215, engine, hash_on_device, dom, prehash):
     n = len(sigs)
     if len(msgs) != n or len(publicKeys) != n:
         raise ValueError("arrays of signatures, messages and public keys must have equal length")
     if not isinstance(zip215, bool):
         raise TypeError('"zip215" expected boolean')
+    if dom or prehash:
+        hash_on_device = False
     S = np.zeros((n, 64), np.uint8)
     P = np.zeros((n, 32), np.uint8)
     K = np.zeros((n, 32), np.uint8)
@@ -52,20 +67,146 @@ def verify_batch(sigs, msgs, publicKeys, zip215=True, engine=None, hash_on_devic
         if hash_on_device:
             ms.append(msg)
         else:
-            K[i] = np.frombuffer(challenge(sig[:32], pk, msg).to_bytes(32, "little"), np.uint8)
+            if prehash:
+                msg = hashlib.sha512(msg).digest()
+            K[i] = np.frombuffer(challenge(dom + sig[:32], pk, msg).to_bytes(32, "little"), np.uint8)
     eng = engine or get_engine()
     if hash_on_device:
-        off = np.zeros((n + 1,), np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(m) for m in ms], dtype=np.uint64)
-        blob = np.frombuffer(b"".join(ms), np.uint8) if n and off[n] else np.zeros((0,), np.uint8)
+        blob, off = _blob(ms)
         return [bool(x) for x in eng.ed25519_verify_batch_msgs(S, P, blob, off, zip215)]
     return [bool(x) for x in eng.ed25519_verify_batch(S, P, K, zip215)]
 
 
-def verify(sig, msg, publicKey, zip215=True, engine=None):
+def verify(sig, msg, publicKey, zip215=True, engine=None, context=None, prehash=False):
     """eddsa.verify (edwards.ts:942): one signature = a batch of one."""
-    return verify_batch([sig], [msg], [publicKey], zip215, engine)[0]
+    return verify_batch([sig], [msg], [publicKey], zip215, engine, context=context, prehash=prehash)[0]
+
+
+def _blob(ms):
+    """messages back to back + their n + 1 offsets (the layout of the message-taking entry points)"""
+    n = len(ms)
+    off = np.zeros((n + 1,), np.uint64)
+    if n:
+        off[1:] = np.cumsum([len(m) for m in ms], dtype=np.uint64)
+    blob = np.frombuffer(b"".join(ms), np.uint8) if n and off[n] else np.zeros((0,), np.uint8)
+    return blob, off
+
+
+# ---- signing: eddsa.getPublicKey / getExtendedPublicKey / sign (edwards.ts:870-930), ed25519ctx / ed25519ph (ed25519.ts:146-223)
+_DOM_PREFIX = b"SigEd25519 no Ed25519 collisions"
+
+
+def _dom(context, prehash, domain):
+    """the bytes in front of both hashes: empty for plain ed25519, ed25519_domain (ed25519.ts:148-160) for ctx / ph"""
+    ctx = b"" if context is None else _abytes(context, None, "context")
+    if not domain:
+        if len(ctx) or prehash:
+            raise ValueError("Contexts/pre-hash are not supported")
+        return b""
+    if len(ctx) > 255:
+        raise ValueError("Context is too big")
+    return _DOM_PREFIX + bytes([1 if prehash else 0, len(ctx)]) + ctx
+
+
+def _seeds(secretKeys):
+    K = np.zeros((len(secretKeys), 32), np.uint8)
+    for i, sk in enumerate(secretKeys):
+        K[i] = np.frombuffer(_abytes(sk, 32, "secretKey"), np.uint8)
+    return K
+
+
+def getPublicKey_batch(secretKeys, engine=None):
+    """eddsa.getPublicKey for every 32-byte secret key, on the device (`ncg_ed25519_public_key_batch`): list of bytes"""
+    K = _seeds(secretKeys)
+    out = (engine or get_engine()).ed25519_public_key_batch(K)
+    K[:] = 0
+    return [out[i].tobytes() for i in range(out.shape[0])]
+
+
+def getPublicKey(secretKey, engine=None):
+    return getPublicKey_batch([secretKey], engine)[0]
+
+
+def expand_keys(secretKeys, engine=None):
+    """96-byte rows scalar || prefix || publicKey (uint8 [n, 96]) for repeated use with sign_batch(..., expanded=True)"""
+    K = _seeds(secretKeys)
+    out = (engine or get_engine()).ed25519_expand_key_batch(K)
+    K[:] = 0
+    return out
+
+
+def getExtendedPublicKey(secretKey, engine=None):
+    """head, prefix, scalar, pointBytes of the reference's getExtendedPublicKey; scalar and pointBytes come from the device,
+    head is the clamped first half of SHA-512(secretKey) (the device keeps it only reduced mod L)"""
+    row = expand_keys([secretKey], engine)[0].tobytes()
+    return {"head": toMontgomerySecret(secretKey), "prefix": row[32:64], "scalar": int.from_bytes(row[:32], "little"),
+            "pointBytes": row[64:]}
+
+
+def sign_batch(msgs, secretKeys, context=None, engine=None, expanded=False):
+    """ed25519.sign per message (plain ed25519: a non-empty context raises like the reference; ed25519ctx / ed25519ph are the
+    namespaces below).  secretKeys: ONE key for every message (bytes, or one 96-byte row with expanded=True) or a list / array as
+    long as msgs.  Returns a list of 64-byte signatures; None where the device refused the row (r = 0 mod L)."""
+    return _sign_rows(msgs, secretKeys, _dom(context, False, False), False, engine, expanded)
+
+
+def _sign_rows(msgs, secretKeys, dom, prehash, engine, expanded):
+    ms = [_abytes(m, None, "message") for m in msgs]
+    width = 96 if expanded else 32
+    one = isinstance(secretKeys, (bytes, bytearray, memoryview)) or (isinstance(secretKeys, np.ndarray) and secretKeys.ndim == 1)
+    rows = [secretKeys] if one else secretKeys
+    if not one and len(rows) != len(ms):
+        raise ValueError("arrays of messages and secret keys must have equal length")
+    K = np.zeros((len(rows), width), np.uint8)
+    for i, sk in enumerate(rows):
+        K[i] = np.frombuffer(_abytes(sk, width, "secretKey"), np.uint8)
+    blob, off = _blob(ms)
+    sig, ok = (engine or get_engine()).ed25519_sign_batch(K, blob, off, dom, expanded=expanded, one_key=one, prehash=prehash)
+    K[:] = 0
+    return [sig[i].tobytes() if ok[i] else None for i in range(len(ms))]
+
+
+def _sign_one(msg, secretKey, dom, prehash, engine):
+    _abytes(secretKey, 32, "secretKey")
+    out = _sign_rows([msg], secretKey, dom, prehash, engine, False)[0]
+    if out is None:
+        raise ValueError("invalid scalar: expected 1 <= sc < curve.n")
+    return out
+
+
+def sign(msg, secretKey, context=None, engine=None):
+    """ed25519.sign (edwards.ts:909): a batch of one; raises where the reference throws"""
+    _abytes(secretKey, 32, "secretKey")
+    return _sign_one(msg, secretKey, _dom(context, False, False), False, engine)
+
+
+class _Variant:
+    """ed25519ctx / ed25519ph: the same functions with the domain of ed25519.ts:148-160 and, for ph, SHA-512 of the message"""
+
+    def __init__(self, prehash):
+        self._ph = prehash
+
+    getPublicKey = staticmethod(getPublicKey)
+    getPublicKey_batch = staticmethod(getPublicKey_batch)
+    getExtendedPublicKey = staticmethod(getExtendedPublicKey)
+    expand_keys = staticmethod(expand_keys)
+
+    def sign(self, msg, secretKey, context=None, engine=None):
+        _abytes(secretKey, 32, "secretKey")
+        return _sign_one(msg, secretKey, _dom(context, self._ph, True), self._ph, engine)
+
+    def sign_batch(self, msgs, secretKeys, context=None, engine=None, expanded=False):
+        return _sign_rows(msgs, secretKeys, _dom(context, self._ph, True), self._ph, engine, expanded)
+
+    def verify(self, sig, msg, publicKey, zip215=True, engine=None, context=None):
+        return self.verify_batch([sig], [msg], [publicKey], zip215, engine, context)[0]
+
+    def verify_batch(self, sigs, msgs, publicKeys, zip215=True, engine=None, context=None):
+        return _verify_rows(sigs, msgs, publicKeys, zip215, engine, False, _dom(context, self._ph, True), self._ph)
+
+
+ed25519ctx = _Variant(False)
+ed25519ph = _Variant(True)
 
 
 # ---- ed25519.utils.toMontgomery / toMontgomerySecret (src/ed25519.ts:128-143, edwards.ts:1022-1031)
