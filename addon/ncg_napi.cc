@@ -9,6 +9,8 @@
 //   ed25519VerifyBatch(sigs, pks, ks, zip215: bool)  -> Uint8Array n (0 / 1)
 //   x25519(kind, scalars | null, rows)               -> Uint8Array n * 33 (32-byte results, then ok flags); kind 0 scalarMult
 //                                                       (scalars: n rows, or ONE row used for every u), 1 getPublicKey, 2 toMontgomery
+//   secpSign(kind, keys, flags | mode[, data, lens, extra]) -> secp256k1 public keys (kind 0), ECDSA signatures with RFC 6979 nonces
+//       (kind 1) and BIP-340 signatures (kind 2) on packed rows; see SecpSign
 //   ed25519Sign(kind, keys[, flags, dom, msgs, lens]) -> kind 0 getPublicKey (keys: n x 32) -> Uint8Array n * 32; kind 1 sign (keys: n rows
 //                                                       or ONE, flags: 4 = prehash, dom, msgs back to back, lens: n LE uint32) ->
 //                                                       Uint8Array n * 65 (64-byte signatures, then ok flags)
@@ -323,6 +325,61 @@ static napi_value Ed25519Sign(napi_env env, napi_callback_info info) {
   if (kl != 32 * n) flags |= NCG_ED25519_SIGN_ONE_KEY;
   if (n && ncg_ed25519_sign_batch(g_ctx, n, keys, flags, dl ? dom : nullptr, dl, ml ? msgs : nullptr, off.data(), out, out + n * 64) != 0)
     return throw_native(env);
+  return res;
+}
+
+// secp256k1 signing on packed rows (ncg_secp256k1_public_key_batch, ncg_ecdsa_sign_batch[_msgs], ncg_schnorr_sign_batch).  Keys are n x 32
+// big-endian bytes; ONE key row against n > 1 messages selects NCG_SECP_SIGN_ONE_KEY.  An empty Uint8Array stands for "not given".
+//   kind 0 (keys, mode)                       -> n public keys of 33 / 65 / 32 bytes (mode 0 / 1 / 2), then n ok flags
+//   kind 1 (keys, flags, data, lens, extra)   ECDSA: lens empty: data = n x 32 hashes (prehash false); else data = the messages back to
+//                                             back and lens = n lengths as LE uint32; extra: empty or n x 32; flags: the lowS bit
+//                                             -> n x 64 signatures, n recovery ids, n ok flags
+//   kind 2 (keys, 0, msgs, lens, aux)         BIP-340: aux n x 32 -> n x 64 signatures, n ok flags
+// A refused row is zero.
+static napi_value SecpSign(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind, flags = 0;
+  uint8_t *keys, *data = nullptr, *lens = nullptr, *extra = nullptr, *out;
+  size_t kl, dl = 0, ll = 0, xl = 0;
+  if (argc < 3 || napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 2 || !get_u8(env, argv[1], &keys, &kl) || kl % 32 ||
+      napi_get_value_int32(env, argv[2], &flags) != napi_ok ||
+      (kind > 0 && (argc < 6 || !get_u8(env, argv[3], &data, &dl) || !get_u8(env, argv[4], &lens, &ll) || ll % 4 || !get_u8(env, argv[5], &extra, &xl)))) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: secpSign(kind, keys of 32 bytes, flags | mode[, data, lens, extra | aux])");
+    return nullptr;
+  }
+  if (kind == 0) {
+    const size_t n = kl / 32, w = flags == NCG_SECP_PK_UNCOMPRESSED ? 65 : flags == NCG_SECP_PK_XONLY ? 32 : 33;
+    napi_value res = make_u8(env, n * (w + 1), &out);
+    if (!res) return nullptr;
+    if (n && ncg_secp256k1_public_key_batch(g_ctx, n, keys, flags, out, out + n * w) != 0) return throw_native(env);
+    return res;
+  }
+  const bool hashes = kind == 1 && ll == 0 && dl != 0;
+  const size_t n = hashes ? dl / 32 : ll / 4;
+  std::vector<uint64_t> off(n + 1, 0);
+  for (size_t i = 0; i < n && !hashes; i++) {
+    uint32_t len;
+    memcpy(&len, lens + 4 * i, 4);
+    off[i + 1] = off[i] + len;
+  }
+  if ((hashes ? dl != 32 * n : off[n] != dl) || (kl != 32 * n && kl != 32) || (kind == 2 ? xl != 32 * n : (xl != 0 && xl != 32 * n)) ||
+      (flags & ~NCG_ECDSA_LOW_S)) {
+    napi_throw_error(env, nullptr, "noble-gpu: secpSign: arrays of messages, secret keys and extra rows must have matching lengths");
+    return nullptr;
+  }
+  if (kl != 32 * n) flags |= NCG_SECP_SIGN_ONE_KEY;
+  napi_value res = make_u8(env, n * (kind == 1 ? 66 : 65), &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (n && kind == 2) rc = ncg_schnorr_sign_batch(g_ctx, n, keys, extra, dl ? data : nullptr, off.data(), flags, out, out + n * 64);
+  else if (n && hashes) rc = ncg_ecdsa_sign_batch(g_ctx, NCG_SECP256K1, n, keys, data, xl ? extra : nullptr, flags, out, out + n * 64, out + n * 65);
+  else if (n)
+    rc = ncg_ecdsa_sign_batch_msgs(g_ctx, NCG_SECP256K1, n, keys, dl ? data : nullptr, off.data(), xl ? extra : nullptr, flags, out, out + n * 64,
+                                   out + n * 65);
+  if (rc != 0) return throw_native(env);
   return res;
 }
 
@@ -1113,7 +1170,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -8,6 +8,9 @@
 //   ed25519VerifyBatch(items, zip215)      - array form of eddsa.verify (edwards.ts:942-989)
 //   x25519ScalarMultBatch(items)           - array form of x25519.scalarMult / getSharedSecret (abstract/montgomery.ts:314-331);
 //   x25519GetPublicKeyBatch(secretKeys)      x25519.getPublicKey; ed25519ToMontgomeryBatch(publicKeys): ed25519.utils.toMontgomery
+//   secp256k1GetPublicKeyBatch(secretKeys, isCompressed), schnorrGetPublicKeyBatch(secretKeys), ecdsaSignBatch(items, opts),
+//   schnorrSignBatch(items)                - array forms of secp256k1.getPublicKey / sign (RFC 6979) and schnorr.getPublicKey / sign
+//                                            (BIP-340) on the device; secp256k1Sign / schnorrSign: single-item forms with the reference's messages
 //   ed25519GetPublicKeyBatch(secretKeys)   - array form of eddsa.getPublicKey (abstract/edwards.ts:870-897);
 //   ed25519SignBatch(items | {msgs, secretKey}, { context, prehash }) - eddsa.sign for ed25519, ed25519ctx (context given) and
 //                                            ed25519ph (prehash: true) (edwards.ts:908-930, ed25519.ts:146-223), hashes included, on the
@@ -599,6 +602,159 @@ function ed25519Sign(msg, secretKey, opts) {
   return r;
 }
 
+// ---- secp256k1 signing (abstract/weierstrass.ts:1480-1568, secp256k1.ts:147-221): getPublicKey, ECDSA sign with RFC 6979 nonces and
+// BIP-340 sign.  The DRBG, every hash, the fixed-base multiplications and the scalar arithmetic run on the device; DER is encoded here.
+// Batch forms return null for a row the device refused; the single-item forms throw the reference's messages.
+const SECP_N = BigInt('0xfffffffffffffffffffffffffffffffebaaedce6af48a03bbfd25e8cd0364141');
+function secpKeyRows(keys, check) {             // the keys packed into one array; nothing of them is left behind when a check throws
+  const S = new Uint8Array(32 * keys.length);
+  try {
+    keys.forEach((k, i) => S.set(check(k), 32 * i));
+  } catch (e) {
+    S.fill(0);
+    throw e;
+  }
+  return S;
+}
+function fnBytes32(b) {                        // Fn.fromBytes of the ECDSA side: its own message for a wrong length
+  if (!(b instanceof Uint8Array)) throw new Error('"secretKey" expected Uint8Array, got type=' + typeof b);
+  if (b.length !== 32) throw new Error('Field.fromBytes: expected 32 bytes, got ' + b.length);
+  return b;
+}
+function secpRefusedKey(sk, zeroMessage) {     // the reference's message for a key outside [1, n), null for a key in range
+  const d = BigInt('0x' + Buffer.from(sk).toString('hex'));
+  if (d === BigInt(0)) return zeroMessage;
+  return d >= SECP_N ? 'invalid field element: outside of range 0..ORDER' : null;
+}
+function secpPublicKeys(secretKeys, mode, check) {
+  const n = secretKeys.length, w = mode === 1 ? 65 : mode === 2 ? 32 : 33;
+  const S = secpKeyRows(secretKeys, check);
+  if (n === 0) return [];
+  let out;
+  try {
+    init();
+    out = native.secpSign(0, S, mode);
+  } finally {
+    S.fill(0);
+  }
+  return Array.from({ length: n }, (_, i) => (out[w * n + i] === 1 ? out.slice(w * i, w * i + w) : null));
+}
+function secp256k1GetPublicKeyBatch(secretKeys, isCompressed) {
+  return secpPublicKeys(secretKeys, isCompressed === false ? 1 : 0, fnBytes32);
+}
+function schnorrGetPublicKeyBatch(secretKeys) { return secpPublicKeys(secretKeys, 2, (k) => abytes32(k, 'secretKey')); }
+function secpPackMsgs(msgs) {
+  const n = msgs.length, lens = new Uint8Array(4 * n), view = new DataView(lens.buffer);
+  let total = 0;
+  msgs.forEach((m, i) => {
+    if (!(m instanceof Uint8Array)) throw new Error('"message" expected Uint8Array, got type=' + typeof m);
+    view.setUint32(4 * i, m.length, true);
+    total += m.length;
+  });
+  const blob = new Uint8Array(total);
+  for (let i = 0, at = 0; i < n; at += msgs[i++].length) blob.set(msgs[i], at);
+  return { blob, lens };
+}
+function derOfCompact(sig) {                   // DER.hexFromSig: SEQUENCE of two minimal positive INTEGERs
+  const int = (b) => {
+    let i = 0;
+    while (i < 31 && b[i] === 0) i++;
+    const body = b[i] & 0x80 ? [0, ...b.slice(i)] : [...b.slice(i)];
+    return [2, body.length, ...body];
+  };
+  const body = [...int(sig.slice(0, 32)), ...int(sig.slice(32, 64))];
+  return Uint8Array.from([0x30, body.length, ...body]);
+}
+// items: [{msg, secretKey[, extraEntropy]}] - or {msgs, secretKey}: ONE key signing many messages (the key crosses once).
+// opts: lowS (true), prehash (true), format 'compact' | 'recovered' | 'der', extraEntropy: true draws 32 random bytes per row (a per-row
+// extraEntropy of an item wins); only 32-byte extra entropy is offered in batch.
+function ecdsaSignBatch(items, opts) {
+  const o = Object.assign({ lowS: true, prehash: true, format: 'compact', extraEntropy: false }, opts || {});
+  if (!['compact', 'recovered', 'der'].includes(o.format)) throw new Error('Signature format must be "compact", "recovered", or "der"');
+  const one = !Array.isArray(items);
+  const msgs = one ? items.msgs : items.map((it) => it.msg);
+  const n = msgs.length;
+  msgs.forEach((m) => { if (!(m instanceof Uint8Array)) throw new Error('"message" expected Uint8Array, got type=' + typeof m); });
+  const K = secpKeyRows(one ? [items.secretKey] : items.map((it) => it.secretKey), fnBytes32);
+  let X = new Uint8Array(0), out;
+  try {                                           // the packed keys and extra entropy are zeroed on every way out
+    const perRow = !one && items.some((it) => it.extraEntropy !== undefined && it.extraEntropy !== false);
+    if (perRow || o.extraEntropy === true) {
+      X = new Uint8Array(32 * n);
+      for (let i = 0; i < n; i++) {
+        const e = !one && items[i].extraEntropy instanceof Uint8Array ? items[i].extraEntropy : require('crypto').randomBytes(32);
+        if (e.length !== 32) throw new Error('noble-gpu: only 32-byte extra entropy is offered in batch');
+        X.set(e, 32 * i);
+      }
+    } else if (o.extraEntropy) throw new Error('noble-gpu: only 32-byte extra entropy is offered in batch');
+    if (n === 0) return [];
+    init();
+    if (o.prehash) {
+      const { blob, lens } = secpPackMsgs(msgs);
+      out = native.secpSign(1, K, o.lowS ? 1 : 0, blob, lens, X);
+    } else {
+      const H = new Uint8Array(32 * n);           // bits2int keeps the leading 32 bytes; a shorter message is left-padded
+      msgs.forEach((m, i) => {
+        if (m.length > 8192) throw new Error('input is too large');
+        if (m.length >= 32) H.set(m.slice(0, 32), 32 * i);
+        else H.set(m, 32 * i + 32 - m.length);
+      });
+      out = native.secpSign(1, K, o.lowS ? 1 : 0, H, new Uint8Array(0), X);
+    }
+  } finally {
+    K.fill(0);
+    X.fill(0);
+  }
+  return Array.from({ length: n }, (_, i) => {
+    if (out[65 * n + i] !== 1) return null;
+    const sig = out.slice(64 * i, 64 * i + 64);
+    if (o.format === 'der') return derOfCompact(sig);
+    if (o.format === 'recovered') return Uint8Array.from([out[64 * n + i], ...sig]);
+    return sig;
+  });
+}
+// items: [{msg, secretKey[, auxRand]}]: auxRand defaults to 32 fresh random bytes, as in the reference
+function schnorrSignBatch(items) {
+  const n = items.length;
+  const K = secpKeyRows(items.map((it) => it.secretKey), (k) => abytes32(k, 'secretKey'));
+  const A = new Uint8Array(32 * n);
+  let out;
+  try {                                           // the packed keys and aux rows are zeroed on every way out
+    items.forEach((it, i) => A.set(it.auxRand === undefined ? require('crypto').randomBytes(32) : abytes32(it.auxRand, 'auxRand'), 32 * i));
+    const { blob, lens } = secpPackMsgs(items.map((it) => it.msg));
+    if (n === 0) return [];
+    init();
+    out = native.secpSign(2, K, 0, blob, lens, A);
+  } finally {
+    K.fill(0);
+    A.fill(0);
+  }
+  return Array.from({ length: n }, (_, i) => (out[64 * n + i] === 1 ? out.slice(64 * i, 64 * i + 64) : null));
+}
+function secp256k1GetPublicKey(secretKey, isCompressed) {
+  const r = secp256k1GetPublicKeyBatch([secretKey], isCompressed)[0];
+  if (r === null) throw new Error(secpRefusedKey(secretKey, 'invalid scalar: out of range'));
+  return r;
+}
+function schnorrGetPublicKey(secretKey) {
+  const r = schnorrGetPublicKeyBatch([secretKey])[0];
+  if (r === null) throw new Error(secpRefusedKey(secretKey, 'invalid scalar: out of range'));
+  return r;
+}
+function secp256k1Sign(msg, secretKey, opts) {
+  const item = { msg, secretKey };
+  if (opts && opts.extraEntropy instanceof Uint8Array) item.extraEntropy = opts.extraEntropy;
+  const r = ecdsaSignBatch([item], opts)[0];
+  if (r === null) throw new Error(secpRefusedKey(secretKey, 'invalid private key') || 'drbg: tried max amount of iterations');
+  return r;
+}
+function schnorrSign(msg, secretKey, auxRand) {
+  const r = schnorrSignBatch([{ msg, secretKey, auxRand }])[0];
+  if (r === null) throw new Error(secpRefusedKey(secretKey, 'invalid scalar: out of range') || 'sign failed: k is zero');
+  if (!schnorrVerifyBatch([{ sig: r, msg, publicKey: schnorrGetPublicKey(secretKey) }])[0]) throw new Error('sign: Invalid signature produced');
+  return r;
+}
+
 // ---- X448 and Ed448 verification (ed448.ts; abstract/montgomery.ts:247-420, abstract/edwards.ts:942-989) ----------------------
 // The same buffers-in / buffers-out convention as the X25519 calls.  Hashing stays on the host: the challenge
 // k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114) mod n and the ed448ph prehash use crypto.createHash('shake256').
@@ -1146,6 +1302,8 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    fromBytesBatch, toBytesBatch, aggregateFromBytes, fftFr, polyFr, hashToCurveBatch, registerBls, pairingBatch, blsVerifyBatch,
                    x25519ScalarMultBatch, x25519GetPublicKeyBatch, ed25519ToMontgomeryBatch, x25519ScalarMult, x25519GetPublicKey, ed25519ToMontgomery,
                    ed25519GetPublicKeyBatch, ed25519SignBatch, ed25519GetPublicKey, ed25519Sign,
+                   secp256k1GetPublicKeyBatch, ecdsaSignBatch, schnorrGetPublicKeyBatch, schnorrSignBatch, secp256k1GetPublicKey, schnorrGetPublicKey,
+                   secp256k1Sign, schnorrSign,
                    x448ScalarMultBatch, x448GetPublicKeyBatch, ed448VerifyBatch,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,

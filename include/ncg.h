@@ -715,6 +715,60 @@ int ncg_schnorr_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig64_
                                       const uint64_t* msg_off_dev, const void* pkx32_dev, uint8_t* out_ok_dev,
                                       void* stream);
 
+/* ---- secp256k1 signing: secp256k1.getPublicKey / sign and schnorr.getPublicKey / sign ----------------------------------------
+ * (src/abstract/weierstrass.ts:1480-1568 with the HMAC-DRBG of src/utils.ts:755-813; src/secp256k1.ts:147-221).
+ * sk32, hash32, extra32 and aux32 are rows of 32 big-endian bytes, read byte by byte (no alignment rule); signatures are rows of
+ * 64 bytes.  Every row gets out_ok[i] = 1 and its result, or out_ok[i] = 0 and a row of zero bytes where the reference throws: a
+ * key outside [1, n), the DRBG's cap of 1000 candidates (ECDSA), k' = 0 (BIP-340).  A refused row does not disturb its neighbours.
+ *
+ * ncg_secp256k1_public_key_batch: out[i] = the public key of sk32[i] as flags says - NCG_SECP_PK_COMPRESSED (0, the default,
+ *   33 bytes), NCG_SECP_PK_UNCOMPRESSED (65 bytes 04 || x || y) or NCG_SECP_PK_XONLY (32 bytes, schnorr.getPublicKey).
+ * ncg_ecdsa_sign_batch: out_sig64[i] = r || s of sign(hash32[i], sk32[i], { prehash: false, lowS, extraEntropy }) with RFC 6979
+ *   nonces; out_recid[i] (the array may be NULL) = (y(R) odd) | (x(R) >= n) << 1, bit 0 flipped where lowS replaced s by n - s.
+ *   hash32: 32 bytes taken as h1 = bits2int_modN.  extra32: NULL, or 32 bytes PER ROW that join the DRBG's seed (RFC 6979 3.6) -
+ *   n rows also with NCG_SECP_SIGN_ONE_KEY, any other length of extra entropy is not offered.  The reference's blinding of the
+ *   inversion changes no output bit and is not reproduced.
+ * ncg_ecdsa_sign_batch_msgs: the same with hash32[i] = SHA-256(message i) computed on the device ({ prehash: true }); msgs /
+ *   msg_off as for ncg_ecdsa_verify_batch_msgs.
+ *   flags of both: NCG_ECDSA_LOW_S, NCG_SECP_SIGN_ONE_KEY (sk32 is ONE row used for all n rows); curve: NCG_SECP256K1 only.
+ * ncg_schnorr_sign_batch: out_sig64[i] = schnorr.sign(message i, sk32[i], aux32[i]) without its self-verification (run
+ *   ncg_schnorr_verify_batch_msgs over the output for that).  aux32: n rows, required.  flags: NCG_SECP_SIGN_ONE_KEY.
+ * The secret scalars never select an address or a branch of a multiplication (a table walk that reads every entry, DESIGN.md
+ * section 8); this is not a constant-time claim.  Device and staging memory that held keys, nonces or DRBG state is cleared on
+ * the call's stream before the call returns.  Unknown flag bits, a NULL required buffer: NCG_ERR_INVALID_ARG; n = 0 returns NCG_OK. */
+#define NCG_SECP_PK_COMPRESSED   0
+#define NCG_SECP_PK_UNCOMPRESSED 1
+#define NCG_SECP_PK_XONLY        2
+#define NCG_SECP_SIGN_ONE_KEY    4   /* beside NCG_ECDSA_LOW_S (1); bit 1 is the verify forms' NCG_ECDSA_PUB_UNCOMPRESSED */
+int ncg_secp256k1_public_key_batch(ncg_ctx* ctx, size_t n, const void* sk32, int flags, void* out, uint8_t* out_ok);
+int ncg_secp256k1_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* sk32_dev, int flags, void* out_dev, uint8_t* out_ok_dev,
+                                       void* stream);
+int ncg_ecdsa_sign_batch(ncg_ctx* ctx, int curve, size_t n, const void* sk32, const void* hash32, const void* extra32, int flags,
+                         void* out_sig64, uint8_t* out_recid, uint8_t* out_ok);
+int ncg_ecdsa_sign_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* sk32_dev, const void* hash32_dev, const void* extra32_dev,
+                             int flags, void* out_sig64_dev, uint8_t* out_recid_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_ecdsa_sign_batch_msgs(ncg_ctx* ctx, int curve, size_t n, const void* sk32, const void* msgs, const uint64_t* msg_off,
+                              const void* extra32, int flags, void* out_sig64, uint8_t* out_recid, uint8_t* out_ok);
+int ncg_ecdsa_sign_batch_msgs_dev(ncg_ctx* ctx, int curve, size_t n, const void* sk32_dev, const void* msgs_dev,
+                                  const uint64_t* msg_off_dev, const void* extra32_dev, int flags, void* out_sig64_dev,
+                                  uint8_t* out_recid_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_schnorr_sign_batch(ncg_ctx* ctx, size_t n, const void* sk32, const void* aux32, const void* msgs, const uint64_t* msg_off,
+                           int flags, void* out_sig64, uint8_t* out_ok);
+int ncg_schnorr_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* sk32_dev, const void* aux32_dev, const void* msgs_dev,
+                               const uint64_t* msg_off_dev, int flags, void* out_sig64_dev, uint8_t* out_ok_dev, void* stream);
+/* The pieces of csrc/secp256k1_sign.hpp on raw 32-bit words, one row per lane (host pointers; n <= 2^24): the branches of the
+ * signing code that real inputs reach with probability about 2^-128 can only be tested by feeding them directly.  An op nobody
+ * defines reads nothing and leaves rows of 16 zero words.  Words per row (a, b, out):
+ *   0  candidate j = variant >> 1 (j <= 3) of the HMAC-SHA256 DRBG from the 96 seed bytes a, as they lie in memory (the last 32
+ *      only when variant & 1: extra entropy): the candidate's 32 bytes                                            24, 1, 8
+ *   1  the uniform-scan multiply: x || y of a G, canonical, 8 + 8 little-endian words                              8, 1, 16
+ *   2  the ECDSA finish: a = k || x(R) || m || d (8 LE words each), b = (y(R) odd) | lowS << 1:
+ *      r || s || recid || accepted                                                                                32, 1, 18
+ *   3  the BIP-340 scalar half: a = k' || e || d, b = y(R) odd: s = (k + e d) mod n                               24, 1, 8
+ *   4  one whole ECDSA row with the DRBG's candidates below variant >> 1 (<= 3) refused (variant & 1: extra entropy):
+ *      a = sk || hash || extra as bytes, b = lowS: sig64 as bytes || recid || ok                                  24, 1, 18 */
+int ncg_secp256k1_sign_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
 /* Runs instruction-rate / field-multiply micro-benchmark `kind` (see csrc/ubench.hip) and
  * returns the kernel time in milliseconds. */
 int ncg_ubench(ncg_ctx* ctx, int kind, int blocks, int threads, int iters, float* out_ms);

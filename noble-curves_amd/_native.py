@@ -22,6 +22,11 @@ POLY_MAX_POINTS = 8
 X25519_ONE_SCALAR = 1   # ncg_x25519_batch flag: one secret for every row
 ED25519_SIGN_EXPANDED, ED25519_SIGN_ONE_KEY, ED25519_SIGN_PREHASH = 1, 2, 4   # ncg_ed25519_sign_batch flags
 ED25519_DOM_MAX = 289
+ECDSA_LOW_S, SECP_SIGN_ONE_KEY = 1, 4   # ncg_ecdsa_sign_batch / ncg_schnorr_sign_batch flags
+SECP_PK_COMPRESSED, SECP_PK_UNCOMPRESSED, SECP_PK_XONLY = 0, 1, 2   # ncg_secp256k1_public_key_batch flags
+SECP_PK_BYTES = {SECP_PK_COMPRESSED: 33, SECP_PK_UNCOMPRESSED: 65, SECP_PK_XONLY: 32}
+# ncg_secp256k1_sign_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/secp256k1_sign.hpp)
+SECP_SIGN_CHECK_WORDS = {0: (24, 1, 8), 1: (8, 1, 16), 2: (32, 1, 18), 3: (24, 1, 8), 4: (24, 1, 18)}
 RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
 # ncg_fp12_batch ops (enum ncg_fp12_op); a GT element is GT_BYTES on the wire
 (FP12_MUL, FP12_SQR, FP12_INV, FP12_CONJUGATE, FP12_FROBENIUS1, FP12_FROBENIUS2, FP12_FROBENIUS3, FP12_CYCLOTOMIC_SQR, FP12_MUL014,
@@ -230,6 +235,15 @@ _OPTIONAL_PROTOS = {
     "ncg_schnorr_verify_batch_msgs_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "ncg_schnorr_verify_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "ncg_ecdsa_verify_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _i32, _vp, _vp],
+    "ncg_secp256k1_public_key_batch": [_vp, _sz, _vp, _i32, _vp, _vp],
+    "ncg_secp256k1_public_key_batch_dev": [_vp, _sz, _vp, _i32, _vp, _vp, _vp],
+    "ncg_ecdsa_sign_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_ecdsa_sign_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "ncg_ecdsa_sign_batch_msgs": [_vp, _i32, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_ecdsa_sign_batch_msgs_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "ncg_schnorr_sign_batch": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
+    "ncg_schnorr_sign_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_secp256k1_sign_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
     "ncg_points_verify_subgroup": [_vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_points_in_subgroup": [_vp],
     "ncg_points_precompute": [_vp, _vp],
@@ -1171,6 +1185,77 @@ class Engine:
     def ecdsa_verify_batch_dev(self, n, d_sigs, d_hashes, d_pubs, low_s, d_ok, stream=None, uncompressed=False):
         self._check(self.lib.ncg_ecdsa_verify_batch_dev(self.h, SECP256K1, n, d_sigs, d_hashes, d_pubs,
                                                         (1 if low_s else 0) | (2 if uncompressed else 0), d_ok, stream))
+
+    # ---- secp256k1 signing: keys, hashes, extra entropy and aux rows uint8 [n, 32] big-endian, signatures [n, 64] ----------------
+    def secp256k1_public_key_batch(self, secret_keys, mode=SECP_PK_COMPRESSED):
+        """secp256k1.getPublicKey (33 or 65 bytes) / schnorr.getPublicKey (x-only, 32 bytes) per row -> (keys uint8 [n, w], ok bool [n]);
+        a key outside [1, n) gives a zero row and ok False"""
+        sk = np.ascontiguousarray(secret_keys, dtype=np.uint8).reshape(-1, 32)
+        n = sk.shape[0]
+        out, ok = np.zeros((n, SECP_PK_BYTES[mode]), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_secp256k1_public_key_batch(self.h, n, sk.ctypes.data, mode, out.ctypes.data, ok.ctypes.data))
+        return out, ok.astype(bool)
+
+    def ecdsa_sign_batch(self, secret_keys, hashes=None, msgs=None, extra=None, low_s=True, one_key=False):
+        """ECDSA with RFC 6979 nonces over 32-byte hashes (prehash: false) or, with msgs, over SHA-256 of each message computed on the
+        device (prehash: true).  secret_keys [n, 32], or ONE row with one_key; extra: None or [n, 32] extra entropy
+        -> (signatures uint8 [n, 64] r || s, recovery ids uint8 [n], ok bool [n]); a refused row is zero."""
+        sk = np.ascontiguousarray(secret_keys, dtype=np.uint8).reshape(-1, 32)
+        if (hashes is None) == (msgs is None):
+            raise ValueError("ecdsa_sign_batch takes hashes or messages")
+        if msgs is None:
+            hashes = np.ascontiguousarray(hashes, dtype=np.uint8).reshape(-1, 32)
+            n = hashes.shape[0]
+        else:
+            n = len(msgs)
+            blob, off = self._msg_blob(msgs)
+        if sk.shape[0] != (1 if one_key else n):
+            raise ValueError("arrays of secret keys and messages must have matching lengths")
+        if extra is not None:
+            extra = np.ascontiguousarray(extra, dtype=np.uint8).reshape(-1, 32)
+            if extra.shape[0] != n:
+                raise ValueError("one row of extra entropy per message")
+        flags = (ECDSA_LOW_S if low_s else 0) | (SECP_SIGN_ONE_KEY if one_key else 0)
+        sig, rec, ok = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            xp = None if extra is None else extra.ctypes.data
+            if msgs is None:
+                self._check(self.lib.ncg_ecdsa_sign_batch(self.h, SECP256K1, n, sk.ctypes.data, hashes.ctypes.data, xp, flags, sig.ctypes.data,
+                                                          rec.ctypes.data, ok.ctypes.data))
+            else:
+                self._check(self.lib.ncg_ecdsa_sign_batch_msgs(self.h, SECP256K1, n, sk.ctypes.data, blob.ctypes.data if blob.size else None,
+                                                               off.ctypes.data, xp, flags, sig.ctypes.data, rec.ctypes.data, ok.ctypes.data))
+        return sig, rec, ok.astype(bool)
+
+    def schnorr_sign_batch(self, secret_keys, aux, msgs, one_key=False):
+        """BIP-340 signatures without the reference's self-verification: secret_keys [n, 32] (ONE row with one_key), aux [n, 32]
+        -> (signatures uint8 [n, 64], ok bool [n]); a refused row is zero."""
+        sk = np.ascontiguousarray(secret_keys, dtype=np.uint8).reshape(-1, 32)
+        aux = np.ascontiguousarray(aux, dtype=np.uint8).reshape(-1, 32)
+        n = len(msgs)
+        if sk.shape[0] != (1 if one_key else n) or aux.shape[0] != n:
+            raise ValueError("arrays of secret keys, aux rows and messages must have matching lengths")
+        blob, off = self._msg_blob(msgs)
+        sig, ok = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_schnorr_sign_batch(self.h, n, sk.ctypes.data, aux.ctypes.data, blob.ctypes.data if blob.size else None,
+                                                        off.ctypes.data, SECP_SIGN_ONE_KEY if one_key else 0, sig.ctypes.data, ok.ctypes.data))
+        return sig, ok.astype(bool)
+
+    def secp256k1_sign_check(self, op, a_words, b_words, variant=0):
+        """The lane code of secp256k1 signing on raw uint32 rows (ncg_secp256k1_sign_check; SECP_SIGN_CHECK_WORDS has the widths):
+        a [n, wa], b [n, wb] -> out [n, wo]; an op nobody defines gives rows of 16 zero words."""
+        wa, wb, wo = SECP_SIGN_CHECK_WORDS.get(op, (1, 1, 0))
+        a = np.ascontiguousarray(a_words, dtype=np.uint32).reshape(-1, wa) if op in SECP_SIGN_CHECK_WORDS else np.ascontiguousarray(a_words, dtype=np.uint32)
+        b = np.ascontiguousarray(b_words, dtype=np.uint32).reshape(-1, wb) if op in SECP_SIGN_CHECK_WORDS else np.ascontiguousarray(b_words, dtype=np.uint32)
+        n = a.shape[0]
+        if b.shape[0] != n:
+            raise ValueError("secp256k1_sign_check: op %d takes rows of %d and %d words" % (op, wa, wb))
+        out = np.zeros((n, wo if wo else 16), dtype=np.uint32)
+        if n:
+            self._check(self.lib.ncg_secp256k1_sign_check(self.h, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
 
     def map_to_curve_batch(self, curve, u, count):
         """u uint8 [n, count * FIELD_BYTES * (2 for G2)] -> (affine [n, PB], is_inf [n]):

@@ -366,6 +366,8 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->ed_ks) (void)hipFree(ctx->ed_ks);
   if (ctx->ed_scan_tab) (void)hipFree(ctx->ed_scan_tab);
   if (ctx->ed_sign_ws) (void)hipFree(ctx->ed_sign_ws);
+  if (ctx->secp_scan_tab) (void)hipFree(ctx->secp_scan_tab);
+  if (ctx->secp_sign_ws) (void)hipFree(ctx->secp_sign_ws);
   if (ctx->ecdsa_ws) (void)hipFree(ctx->ecdsa_ws);
   for (int i = 0; i < 4; i++)
     if (ctx->base_tab[i]) (void)hipFree(ctx->base_tab[i]);
@@ -1830,6 +1832,202 @@ int ncg_ecdsa_verify_batch(ncg_ctx* ctx, int curve, size_t n, const void* sig64,
   const int sig = hc.in(sig64, n * 64), hash = hc.in(hash32, n * 32), pub = hc.in(pub33, n * kb), ok = hc.out(out_ok, n);
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ecdsa_verify_batch_dev(ctx, curve, n, hc.dev(sig), hc.dev(hash), hc.dev(pub), flags, hc.dev<uint8_t>(ok), ctx->stream));
+}
+
+// ---- secp256k1 signing (secp256k1_sign.hip): getPublicKey, ECDSA sign with RFC 6979 nonces, BIP-340 sign.  Every row is read and
+// written byte by byte, so no pointer has an alignment rule.  The workspace holds keys, nonces and the DRBG's state during a call: it
+// is cleared on the call's stream before the call returns, and so are the staged copies of the keys and the extra entropy of a
+// host form.
+static int ensure_secp_scan_table(ncg_ctx* ctx) {
+  if (ctx->secp_scan_tab) return NCG_OK;
+  std::vector<uint32_t> host(ncg::secp_scan_table_words());
+  ncg::secp_build_scan_table(host.data());
+  uint32_t* tab = nullptr;
+  NCG_HIP(ctx, hipMalloc((void**)&tab, host.size() * 4));
+  hipError_t e = hipMemcpy(tab, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    return set_err(ctx, NCG_ERR_HIP, "noble-gpu: uploading the secp256k1 signing table failed: %s", hipGetErrorString(e));
+  }
+  ctx->secp_scan_tab = tab;
+  return NCG_OK;
+}
+static int secp_sign_ws(ncg_ctx* ctx, size_t words) {
+  return ncg_grow_buf(ctx, &ctx->secp_sign_ws, &ctx->secp_sign_ws_bytes, words * 4, words * 4 + (words >> 1) + 4096, GrowWait::device);
+}
+// the rule of the signing entry points: the curve (where the entry point takes one) and the flag bits it knows
+static Rule secp_sign_rule(ncg_ctx* ctx, const char* op, int curve, int flags, int known_flags) {
+  Rule r = secp_rule(ctx, op, curve);
+  if (r.rc == NCG_OK && (flags & ~known_flags)) r.rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
+  return r;
+}
+static Rule secp_pk_rule(ncg_ctx* ctx, int flags) {
+  return {"secp256k1_public_key_batch", flags >= NCG_SECP_PK_COMPRESSED && flags <= NCG_SECP_PK_XONLY
+                                            ? NCG_OK
+                                            : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: secp256k1_public_key_batch: unknown flags 0x%x", flags)};
+}
+static size_t secp_pk_row_bytes(int flags) { return flags == NCG_SECP_PK_UNCOMPRESSED ? 65 : flags == NCG_SECP_PK_XONLY ? 32 : 33; }
+
+int ncg_secp256k1_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* sk32_dev, int flags, void* out_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, secp_pk_rule(ctx, flags), n, sk32_dev, out_dev, out_ok_dev);
+  if (int rc = ensure_secp_scan_table(ctx)) return rc;
+  NCG_HIP(ctx, ncg::secp_public_key_batch(ctx->secp_scan_tab, (const uint8_t*)sk32_dev, flags, (uint8_t*)out_dev, out_ok_dev, (int)n,
+                                          stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_secp256k1_public_key_batch(ncg_ctx* ctx, size_t n, const void* sk32, int flags, void* out, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, secp_pk_rule(ctx, flags), n, sk32, out, out_ok);
+  HostCall hc(ctx);
+  const int s = hc.in(sk32, n * 32), o = hc.out(out, n * secp_pk_row_bytes(flags)), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, s, n * 32);
+    return rc;
+  }
+  const int rc = ncg_secp256k1_public_key_batch_dev(ctx, n, hc.dev(s), flags, hc.dev(o), hc.dev<uint8_t>(ok), ctx->stream);
+  ed_clear_staged(hc, s, n * 32);
+  return hc.finish(rc);
+}
+
+constexpr int ECDSA_SIGN_FLAGS = NCG_ECDSA_LOW_S | NCG_SECP_SIGN_ONE_KEY;
+// hash32_dev, or (msgs_dev, msg_off_dev) with hash32_dev NULL: the prehash then runs first, into the workspace
+static int ecdsa_sign_dev(ncg_ctx* ctx, size_t n, const void* sk32_dev, const void* hash32_dev, const void* msgs_dev, const uint64_t* msg_off_dev,
+                          const void* extra32_dev, int flags, void* out_sig64_dev, uint8_t* out_recid_dev, uint8_t* out_ok_dev, hipStream_t st) {
+  if (int rc = ensure_secp_scan_table(ctx)) return rc;
+  const size_t row_words = ncg::secp_sign_ws_words((int)n, 0), words = row_words + (hash32_dev ? 0 : n * 8);
+  if (int rc = secp_sign_ws(ctx, words)) return rc;
+  uint32_t* ws = (uint32_t*)ctx->secp_sign_ws;
+  hipError_t e = hipSuccess;
+  if (!hash32_dev) {
+    e = ncg::sha256_msgs((const uint8_t*)msgs_dev, msg_off_dev, nullptr, nullptr, 0, (int)n, (uint8_t*)(ws + row_words), st);
+    hash32_dev = ws + row_words;
+  }
+  if (e == hipSuccess)
+    e = ncg::ecdsa_sign_batch(ctx->secp_scan_tab, (const uint8_t*)sk32_dev, (flags & NCG_SECP_SIGN_ONE_KEY) != 0, (const uint8_t*)hash32_dev,
+                              (const uint8_t*)extra32_dev, (flags & NCG_ECDSA_LOW_S) != 0, (uint8_t*)out_sig64_dev, out_recid_dev, out_ok_dev,
+                              (int)n, ws, st);
+  (void)hipMemsetAsync(ctx->secp_sign_ws, 0, words * 4, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_ecdsa_sign_batch_dev(ncg_ctx* ctx, int curve, size_t n, const void* sk32_dev, const void* hash32_dev, const void* extra32_dev, int flags,
+                             void* out_sig64_dev, uint8_t* out_recid_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, secp_sign_rule(ctx, "ecdsa_sign_batch", curve, flags, ECDSA_SIGN_FLAGS), n, sk32_dev, hash32_dev, out_sig64_dev, out_ok_dev);
+  return ecdsa_sign_dev(ctx, n, sk32_dev, hash32_dev, nullptr, nullptr, extra32_dev, flags, out_sig64_dev, out_recid_dev, out_ok_dev,
+                        stream_of(ctx, stream));
+}
+int ncg_ecdsa_sign_batch_msgs_dev(ncg_ctx* ctx, int curve, size_t n, const void* sk32_dev, const void* msgs_dev, const uint64_t* msg_off_dev,
+                                  const void* extra32_dev, int flags, void* out_sig64_dev, uint8_t* out_recid_dev, uint8_t* out_ok_dev,
+                                  void* stream) {
+  NCG_BEGIN(ctx, secp_sign_rule(ctx, "ecdsa_sign_batch_msgs", curve, flags, ECDSA_SIGN_FLAGS), n, sk32_dev, msg_off_dev, out_sig64_dev, out_ok_dev);
+  return ecdsa_sign_dev(ctx, n, sk32_dev, nullptr, msgs_dev, msg_off_dev, extra32_dev, flags, out_sig64_dev, out_recid_dev, out_ok_dev,
+                        stream_of(ctx, stream));
+}
+// the host forms of both: hash32, or (msgs, msg_off) with hash32 NULL
+static int ecdsa_sign_host(ncg_ctx* ctx, Rule rule, int curve, size_t n, const void* sk32, const void* hash32, const void* msgs,
+                           const uint64_t* msg_off, const void* extra32, int flags, void* out_sig64, uint8_t* out_recid, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, rule, n, sk32, msg_off ? (const void*)msg_off : hash32, out_sig64, out_ok);
+  const size_t kbytes = ((flags & NCG_SECP_SIGN_ONE_KEY) ? 1 : n) * 32, xbytes = extra32 ? n * 32 : 0;
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int k = hc.in(sk32, kbytes), x = hc.in(extra32, xbytes);
+  int h = -1, msg = -1, off = -1;
+  if (msg_off) {
+    if (int rc = stage_msgs(hc, rule.op, n, msgs, msg_off, rel, &msg, &off)) return rc;
+  } else {
+    h = hc.in(hash32, n * 32);
+  }
+  const int sig = hc.out(out_sig64, n * 64), rec = hc.out(out_recid, n), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, kbytes);
+    ed_clear_staged(hc, x, xbytes);
+    return rc;
+  }
+  uint8_t* d_rec = out_recid ? hc.dev<uint8_t>(rec) : nullptr;
+  const void* d_x = extra32 ? hc.dev(x) : nullptr;
+  const int rc = msg_off ? ncg_ecdsa_sign_batch_msgs_dev(ctx, curve, n, hc.dev(k), hc.dev(msg), hc.dev<const uint64_t>(off), d_x, flags, hc.dev(sig),
+                                                         d_rec, hc.dev<uint8_t>(ok), ctx->stream)
+                         : ncg_ecdsa_sign_batch_dev(ctx, curve, n, hc.dev(k), hc.dev(h), d_x, flags, hc.dev(sig), d_rec, hc.dev<uint8_t>(ok),
+                                                    ctx->stream);
+  ed_clear_staged(hc, k, kbytes);
+  ed_clear_staged(hc, x, xbytes);
+  return hc.finish(rc);
+}
+int ncg_ecdsa_sign_batch(ncg_ctx* ctx, int curve, size_t n, const void* sk32, const void* hash32, const void* extra32, int flags, void* out_sig64,
+                         uint8_t* out_recid, uint8_t* out_ok) {
+  return ecdsa_sign_host(ctx, secp_sign_rule(ctx, "ecdsa_sign_batch", curve, flags, ECDSA_SIGN_FLAGS), curve, n, sk32, hash32, nullptr, nullptr,
+                         extra32, flags, out_sig64, out_recid, out_ok);
+}
+int ncg_ecdsa_sign_batch_msgs(ncg_ctx* ctx, int curve, size_t n, const void* sk32, const void* msgs, const uint64_t* msg_off, const void* extra32,
+                              int flags, void* out_sig64, uint8_t* out_recid, uint8_t* out_ok) {
+  const Rule rule = secp_sign_rule(ctx, "ecdsa_sign_batch_msgs", curve, flags, ECDSA_SIGN_FLAGS);
+  if (ctx && rule.rc == NCG_OK && n && !msg_off) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ecdsa_sign_batch_msgs: NULL buffer");
+  return ecdsa_sign_host(ctx, rule, curve, n, sk32, nullptr, msgs, msg_off, extra32, flags, out_sig64, out_recid, out_ok);
+}
+
+int ncg_schnorr_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* sk32_dev, const void* aux32_dev, const void* msgs_dev, const uint64_t* msg_off_dev,
+                               int flags, void* out_sig64_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, secp_sign_rule(ctx, "schnorr_sign_batch", NCG_SECP256K1, flags, NCG_SECP_SIGN_ONE_KEY), n, sk32_dev, aux32_dev, msg_off_dev,
+            out_sig64_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  if (int rc = ensure_secp_scan_table(ctx)) return rc;
+  const int one_key = (flags & NCG_SECP_SIGN_ONE_KEY) != 0;
+  const size_t words = ncg::secp_sign_ws_words((int)n, one_key ? 1 : (int)n);
+  if (int rc = secp_sign_ws(ctx, words)) return rc;
+  hipError_t e = ncg::schnorr_sign_batch(ctx->secp_scan_tab, (const uint8_t*)sk32_dev, one_key, (const uint8_t*)aux32_dev, (const uint8_t*)msgs_dev,
+                                         msg_off_dev, (uint8_t*)out_sig64_dev, out_ok_dev, (int)n, (uint32_t*)ctx->secp_sign_ws, st);
+  (void)hipMemsetAsync(ctx->secp_sign_ws, 0, words * 4, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_schnorr_sign_batch(ncg_ctx* ctx, size_t n, const void* sk32, const void* aux32, const void* msgs, const uint64_t* msg_off, int flags,
+                           void* out_sig64, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, secp_sign_rule(ctx, "schnorr_sign_batch", NCG_SECP256K1, flags, NCG_SECP_SIGN_ONE_KEY), n, sk32, aux32, msg_off, out_sig64, out_ok);
+  const size_t kbytes = ((flags & NCG_SECP_SIGN_ONE_KEY) ? 1 : n) * 32;
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int k = hc.in(sk32, kbytes), a = hc.in(aux32, n * 32);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "schnorr_sign_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int sig = hc.out(out_sig64, n * 64), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, kbytes);
+    ed_clear_staged(hc, a, n * 32);
+    return rc;
+  }
+  const int rc = ncg_schnorr_sign_batch_dev(ctx, n, hc.dev(k), hc.dev(a), hc.dev(msg), hc.dev<const uint64_t>(off), flags, hc.dev(sig),
+                                            hc.dev<uint8_t>(ok), ctx->stream);
+  ed_clear_staged(hc, k, kbytes);
+  ed_clear_staged(hc, a, n * 32);
+  return hc.finish(rc);
+}
+
+// The pieces of secp256k1_sign.hpp on raw words, in the style of ncg_decaf448_check: an op nobody defines reads nothing and leaves
+// rows of 16 zero words.  The rows of workspace the DRBG ops use are a device-only slot, cleared before the call returns.
+int ncg_secp256k1_sign_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out) {
+  int wa, wb, wo;
+  ncg::secp_sign_check_row_words(op, &wa, &wb, &wo);
+  int rrc = NCG_OK;
+  if (ctx && n > (1u << 24)) rrc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: secp256k1_sign_check: batch too large (max 2^24)");
+  else if (ctx && wo && (op == 0 || op == 4) && (variant < 0 || (variant >> 1) > 3))
+    rrc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: secp256k1_sign_check: variant %d out of range", variant);
+  const Rule rule = {"secp256k1_sign_check", rrc};
+  NCG_BEGIN(ctx, rule, n, a, b, out);
+  if (wo)
+    if (int rc = ensure_secp_scan_table(ctx)) return rc;
+  const size_t ws_bytes = ncg::secp_sign_ws_words((int)n, 0) * 4;
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * wa * 4), db = hc.in(b, n * wb * 4);
+  const int o = hc.out(out, n * (wo ? wo : 16) * 4, true), w = hc.dev_only(wo ? ws_bytes : 0);
+  if (int rc = hc.stage()) return rc;
+  hipError_t e = hipSuccess;
+  if (wo) {
+    e = ncg::secp_sign_check(op, variant, ctx->secp_scan_tab, hc.dev<uint32_t>(w), hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db),
+                             hc.dev<uint32_t>(o), (int)n, ctx->stream);
+    (void)hipMemsetAsync(hc.dev(w), 0, ws_bytes, ctx->stream);
+    (void)hipMemsetAsync(hc.dev(da), 0, n * wa * 4, ctx->stream);
+  }
+  NCG_HIP(ctx, e);
+  return hc.finish(NCG_OK);
 }
 
 // ---- X25519 (x25519.hip).  Rows are 32 bytes, read as 8 LE words: 4-byte aligned like every other byte row of this ABI.

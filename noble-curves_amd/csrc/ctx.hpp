@@ -51,6 +51,12 @@ struct ncg_ctx {
   uint32_t* ed_scan_tab = nullptr;
   void* ed_sign_ws = nullptr;
   size_t ed_sign_ws_bytes = 0;
+  // secp256k1 signing (secp256k1_sign.hip): the 4-bit window table of G with the hash constants behind it, and the workspace of one
+  // call (keys, nonces, DRBG state, staged hashes) - it holds secrets during a call and is cleared on the call's stream before the
+  // call returns
+  uint32_t* secp_scan_tab = nullptr;
+  void* secp_sign_ws = nullptr;
+  size_t secp_sign_ws_bytes = 0;
   void* ecdsa_ws = nullptr;     // ECDSA batch verify: decoded keys, u1 / u2, partial points (device)
   size_t ecdsa_ws_bytes = 0;
   uint32_t* base_tab[4] = {nullptr, nullptr, nullptr, nullptr};  // fixed-base tables per curve (device)

@@ -8,59 +8,10 @@
 // inversion (Montgomery's trick, the shape of FpInvertBatch, modular.ts:722-747), and the final comparison.
 #include "host_api.hpp"
 #include "scalar.hpp"
+#include "secp_fn.hpp"
 #include "sha256.hpp"
 
 namespace ncg {
-
-// Montgomery constants of the group order n (R = 2^256): python -c "n=0xFFFF...4141; R=1<<256; print(-pow(n,-1,2**32) % 2**32, R % n, R*R % n)"
-struct ParamsSecpN {
-  static constexpr int N = 8;
-  static constexpr uint32_t P[8] = {0xd0364141u, 0xbfd25e8cu, 0xaf48a03bu, 0xbaaedce6u, 0xfffffffeu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-  static constexpr uint32_t INV = 0x5588b13fu;  // -n^-1 mod 2^32
-  static constexpr uint32_t R1[8] = {0x2fc9bebfu, 0x402da173u, 0x50b75fc4u, 0x45512319u, 0x00000001u, 0x00000000u, 0x00000000u, 0x00000000u};
-  static constexpr uint32_t R2[8] = {0x67d7d140u, 0x896cf214u, 0x0e7cf878u, 0x741496c2u, 0x5bcd07c6u, 0xe697f5e4u, 0x81c69bc5u, 0x9d671cd5u};
-  static constexpr bool TOP_SPARE = false;  // n > 2^255: the product keeps its carry word (fp_mul_fips_asm / fp_mul_body)
-  static constexpr bool FOLD = false;
-  static constexpr uint32_t HALF[8] = {0x681b20a0u, 0xdfe92f46u, 0x57a4501du, 0x5d576e73u, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x7fffffffu};  // n >> 1
-};
-using Fn = Fp<ParamsSecpN>;
-
-NCG_DI Fn fn_from_words(const uint32_t (&w)[8]) {
-  Fn r;
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = w[i];
-  return r;
-}
-// a^(n-2), a != 0 (Montgomery form in and out): 4-bit windows over the exponent, 252 squarings + <= 78 products
-NCG_DI Fn fn_inv(const Fn& a) {
-  Fn tab[16];
-  tab[0] = Fn::one();
-  tab[1] = a;
-  for (int j = 2; j < 16; j++) tab[j] = tab[j - 1] * a;
-  uint32_t e[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) e[i] = ParamsSecpN::P[i];
-  e[0] -= 2u;  // n - 2 (no borrow: the low limb is 0xd0364141)
-  Fn acc = tab[e[7] >> 28];
-  for (int w = 62; w >= 0; w--) {
-    for (int s = 0; s < 4; s++) acc = fp_sqr<ParamsSecpN>(acc);
-    const uint32_t dg = (e[w >> 3] >> ((w & 7) * 4)) & 15u;
-    if (dg) acc = acc * tab[dg];
-  }
-  return acc;
-}
-
-NCG_DI void be32_to_words(uint32_t (&w)[8], const uint8_t* __restrict__ p) {  // 32 big-endian bytes -> 8 LE limbs
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const uint8_t* q = p + 4 * (7 - i);
-    w[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
-  }
-}
-NCG_DI bool words_lt(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
-  uint32_t d[8];
-  return mp_sub<8>(d, a, b) != 0;
-}
 
 // One lane: K consecutive signatures.  sig: r || s (32 big-endian bytes each, Signature.fromBytes 'compact',
 // weierstrass.ts:1275-1290: both in [1, n)); hash: 32 bytes, h = bits2int_modN (:1333-1347: the integer of the
@@ -373,10 +324,6 @@ hipError_t secp_load_uncompressed(const uint8_t* d_pub65, uint32_t* d_out, uint8
 // ---- message hashing on the device (sha256.hpp): one lane per item; msgs = all messages back to back,
 // msg_off = n + 1 byte offsets.  mode 0: out[i] = SHA-256(msg_i) (the prehash of ecdsa.verify); mode 1: the BIP-340
 // challenge e_i = int(SHA-256(tag || tag || r_i || pk_i || msg_i)) mod n as 32 big-endian bytes.
-struct Bip340Tag {  // SHA-256("BIP0340/challenge")
-  static constexpr uint8_t H[32] = {0x7b, 0xb5, 0x2d, 0x7a, 0x9f, 0xef, 0x58, 0x32, 0x3e, 0xb1, 0xbf, 0x7a, 0x40, 0x7d, 0xb3, 0x82,
-                                    0xd2, 0xf3, 0xf2, 0xd8, 0x1b, 0xb1, 0x22, 0x4f, 0x49, 0xfe, 0x51, 0x8f, 0x6d, 0x48, 0xd3, 0x7c};
-};
 __global__ void __launch_bounds__(256) k_sha256_msgs(const uint8_t* __restrict__ msgs, const uint64_t* __restrict__ msg_off,
                                                      const uint8_t* __restrict__ sig64, const uint8_t* __restrict__ pkx, int mode, int n,
                                                      uint8_t* __restrict__ out32) {

@@ -210,6 +210,30 @@ void ed25519_sign_host(const uint32_t* table, const void* key, int expanded, int
 void sha512_segments_host(const uint8_t* dom, uint32_t dom_len, const uint8_t* a32, const uint8_t* b32, const uint8_t* msg, uint64_t len,
                           uint8_t* out64);
 
+// secp256k1 signing (secp256k1_sign.hip).  table: device copy of secp_build_scan_table's output (secp_scan_table_words() words):
+// [w][j] = (2 j + 1) 2^(4 w) G as affine points of 18 stored words, then the BIP-340 tag hashes.
+// Keys, hashes, extra entropy and aux rows are 32 big-endian bytes; signatures 64 bytes r || s (ECDSA) or x(R) || s (BIP-340).
+// one_key: `sk` is one row used for every message.  ws: secp_sign_ws_words(n, keys whose point is needed) words of device memory that
+// hold secrets afterwards.  pk_mode: 0 compressed (33 bytes), 1 uncompressed (65), 2 x-only (32).
+size_t secp_scan_table_words();
+void secp_build_scan_table(uint32_t* out_words);
+size_t secp_sign_ws_words(int n, int nkeys);
+hipError_t secp_public_key_batch(const uint32_t* table, const uint8_t* sk, int pk_mode, uint8_t* out, uint8_t* ok, int n, hipStream_t st);
+hipError_t ecdsa_sign_batch(const uint32_t* table, const uint8_t* sk, int one_key, const uint8_t* hash, const uint8_t* extra, int low_s, uint8_t* sig,
+                            uint8_t* recid, uint8_t* ok, int n, uint32_t* ws, hipStream_t st);
+hipError_t schnorr_sign_batch(const uint32_t* table, const uint8_t* sk, int one_key, const uint8_t* aux, const uint8_t* msgs, const uint64_t* off,
+                              uint8_t* sig, uint8_t* ok, int n, uint32_t* ws, hipStream_t st);
+// the pieces of secp256k1_sign.hpp on raw words (ncg_secp256k1_sign_check); words per row of each op: secp_sign_check_row_words
+// (0 = unknown op); ws: n rows of secp_sign_ws_words(1, 0) words
+void secp_sign_check_row_words(int op, int* wa, int* wb, int* wo);
+hipError_t secp_sign_check(int op, int variant, const uint32_t* table, uint32_t* ws, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n,
+                           hipStream_t st);
+int secp_sign_check_host(int op, int variant, const uint32_t* table, const uint32_t* a, const uint32_t* b, uint32_t* out);
+void secp_public_key_host(const uint32_t* table, const uint8_t* sk, int pk_mode, uint8_t* out, uint8_t* ok, int n);
+void ecdsa_sign_host(const uint32_t* table, const uint8_t* sk, const uint8_t* hash, const uint8_t* extra, int low_s, int refuse_first, uint8_t* sig,
+                     uint8_t* recid, uint8_t* ok);
+void schnorr_sign_host(const uint32_t* table, const uint8_t* sk, const uint8_t* aux, const uint8_t* msg, uint64_t len, uint8_t* sig, uint8_t* ok);
+
 // X25519 and ed25519.utils.toMontgomery (x25519.hip): rows of 8 LE words (32 bytes) in and out, out_ok = 0 and a zero row where
 // the reference throws.  one_scalar: `scalars` is one row used for every item.  x25519_base_batch walks the fixed-base Edwards
 // table of ed25519_build_fixed_table; tmp: x25519_base_tmp_words(n) words of device memory.

@@ -28,6 +28,7 @@
 #include "ed448.hip"
 #include "decaf448.hip"
 #include "ed25519_sign.hip"
+#include "secp256k1_sign.hip"
 
 using namespace ncg;
 
@@ -376,6 +377,46 @@ int ht_ed_mul_base_scan(const uint32_t* scalars, uint32_t* out, int n) {
 int ht_sha512_segments(const uint8_t* dom, uint32_t dom_len, const uint8_t* a32, const uint8_t* b32, const uint8_t* msg, uint64_t len,
                        uint8_t* out64) {
   sha512_segments_host(dom, dom_len, a32, b32, msg, len, out64);
+  return 0;
+}
+
+// secp256k1 signing on the CPU twins of secp256k1_sign.hip.  Keys, hashes, extra entropy and aux rows are 32 big-endian bytes,
+// signatures 64 bytes.  ht_secp_sign_op: one row of ncg_secp256k1_sign_check, -1 for an unknown op or variant; ht_secp_sign_widths: its
+// words per row.  ht_ecdsa_sign: flags as ncg_ecdsa_sign_batch (ONE_KEY has no meaning for one row and is refused: -1); extra may be
+// NULL; refuse_first > 0 refuses that many leading candidates of the DRBG.  pk_mode: 0 compressed, 1 uncompressed, 2 x-only.
+static const uint32_t* ht_secp_scan_table() {
+  static const std::vector<uint32_t> tab = [] {
+    std::vector<uint32_t> t(secp_scan_table_words());
+    secp_build_scan_table(t.data());
+    return t;
+  }();
+  return tab.data();
+}
+int ht_secp_sign_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  return secp_sign_check_host(op, variant, ht_secp_scan_table(), a, b, out);
+}
+void ht_secp_sign_widths(int op, int* wa, int* wb, int* wo) { secp_sign_check_row_words(op, wa, wb, wo); }
+int ht_secp_public_key(const uint8_t* sk, int pk_mode, uint8_t* out, uint8_t* ok, int n) {
+  if (pk_mode < 0 || pk_mode > 2) return -1;
+  secp_public_key_host(ht_secp_scan_table(), sk, pk_mode, out, ok, n);
+  return 0;
+}
+int ht_ecdsa_sign(const uint8_t* sk, const uint8_t* hash, const uint8_t* extra, int flags, int refuse_first, uint8_t* out_sig64, uint8_t* out_recid,
+                  uint8_t* out_ok) {
+  if (flags & ~NCG_ECDSA_LOW_S) return -1;
+  ecdsa_sign_host(ht_secp_scan_table(), sk, hash, extra, (flags & NCG_ECDSA_LOW_S) != 0, refuse_first, out_sig64, out_recid, out_ok);
+  return 0;
+}
+int ht_schnorr_sign(const uint8_t* sk, const uint8_t* aux, const uint8_t* msg, uint64_t len, uint8_t* out_sig64, uint8_t* out_ok) {
+  schnorr_sign_host(ht_secp_scan_table(), sk, aux, msg, len, out_sig64, out_ok);
+  return 0;
+}
+// SHA-256(a || b || msg) through sha256_segments; a / b may be NULL (segment left out)
+int ht_sha256_segments(const uint8_t* a, uint32_t a_len, const uint8_t* b, uint32_t b_len, const uint8_t* msg, uint64_t len, uint8_t* out32) {
+  const Sha256Seg seg[3] = {{a, a ? a_len : 0u}, {b, b ? b_len : 0u}, {msg, len}};
+  uint32_t h[8];
+  sha256_segments<3>(h, seg);
+  sha256_store_be(out32, h);
   return 0;
 }
 

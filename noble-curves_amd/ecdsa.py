@@ -1,5 +1,7 @@
 """secp256k1 ECDSA host shim: `verify` / `verify_batch` with the reference's semantics
-(src/abstract/weierstrass.ts:1571-1620, options :1196-1230: lowS true, prehash true, format 'compact').
+(src/abstract/weierstrass.ts:1571-1620, options :1196-1230: lowS true, prehash true, format 'compact'), and `getPublicKey` /
+`sign` with their batch forms (weierstrass.ts:1480-1568): RFC 6979 nonces from the HMAC-SHA256 DRBG, the fixed-base multiply
+and s = k^-1 (m + r d) run in HIP kernels (`ncg_ecdsa_sign_batch[_msgs]`, `ncg_secp256k1_public_key_batch`).
 
 The shim does what the reference does on the host around the group operation - argument checks, SHA-256 of the
 message when `prehash`, bits2int, DER parsing for format 'der', the length / prefix / on-curve check of an
@@ -7,10 +9,11 @@ uncompressed key - and hands fixed-size rows (r || s, h, compressed key) to the 
 s^-1 mod n, u1 G + u2 P and the comparison run in HIP kernels (`ncg_ecdsa_verify_batch`).
 """
 import hashlib
+import os
 
 import numpy as np
 
-from ._native import get_engine
+from ._native import SECP_PK_COMPRESSED, SECP_PK_UNCOMPRESSED, get_engine
 
 P = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEFFFFFC2F
 N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
@@ -239,3 +242,136 @@ def getSharedSecretBatch(secretKeys, publicKeys, isCompressed=True, engine=None)
     if isCompressed:
         return [bytes(b) for b in G.toBytesBatch(K1, shared, engine=engine)]
     return [b"\x04" + x.to_bytes(32, "big") + y.to_bytes(32, "big") for x, y in (p.toAffine() for p in shared)]
+
+
+# ---- signing.  The messages of the errors are the reference's own (tests/golden/secp256k1_sign_kat.json, "errors").
+_JS_TYPES = {str: "string", int: "number", float: "number", bool: "boolean", type(None): "object"}
+
+
+def _amsg(b, title="message"):
+    if not isinstance(b, (bytes, bytearray, memoryview, np.ndarray)):
+        raise TypeError('"%s" expected Uint8Array, got type=%s' % (title, _JS_TYPES.get(type(b), "object")))
+    return bytes(b)
+
+
+def _secret_rows(secretKeys):
+    """(uint8 [k, 32], one_key): a single bytes-like key serves every row; Fn.fromBytes checks the length of each"""
+    one = isinstance(secretKeys, (bytes, bytearray, memoryview))
+    keys = [secretKeys] if one else list(secretKeys)
+    rows = np.zeros((len(keys), 32), np.uint8)
+    for i, sk in enumerate(keys):
+        sk = _amsg(sk, "secretKey")
+        if len(sk) != 32:
+            rows.fill(0)
+            raise ValueError("Field.fromBytes: expected 32 bytes, got %d" % len(sk))
+        rows[i] = np.frombuffer(sk, np.uint8)
+    return rows, one
+
+
+def _public_keys(eng, rows, mode, zero_message):
+    """the public keys of packed secret-key rows as bytes; a refused key raises the reference's message"""
+    out, ok = eng.secp256k1_public_key_batch(rows, mode)
+    for i in range(rows.shape[0]):
+        if not ok[i]:
+            raise ValueError(_refused_key(rows[i], zero_message))
+    return [bytes(r) for r in out]
+
+
+def _refused_key(row, zero_message):
+    """the reference's message for a secret key the device refused (outside [1, n)), or None for a key in range"""
+    d = int.from_bytes(bytes(row), "big")
+    if d == 0:
+        return zero_message
+    return "invalid field element: outside of range 0..ORDER" if d >= N else None
+
+
+def rs_to_der(r, s):
+    """DER.hexFromSig (weierstrass.ts:325-331): SEQUENCE of two minimal positive INTEGERs"""
+    def enc(v):
+        b = v.to_bytes(v.bit_length() // 8 + 1, "big")        # one leading 00 exactly where the top bit would be set
+        return b"\x02" + bytes([len(b)]) + b
+    body = enc(r) + enc(s)
+    return b"\x30" + bytes([len(body)]) + body
+
+
+def getPublicKeyBatch(secretKeys, isCompressed=True, engine=None):
+    """[secp256k1.getPublicKey(sk, isCompressed) for each key]: 33-byte compressed or 65-byte uncompressed SEC1 keys"""
+    if not isinstance(isCompressed, bool):
+        raise TypeError('"isCompressed" expected boolean')
+    rows, _ = _secret_rows(list(secretKeys))
+    if rows.shape[0] == 0:
+        return []
+    try:
+        return _public_keys(engine or get_engine(), rows, SECP_PK_COMPRESSED if isCompressed else SECP_PK_UNCOMPRESSED,
+                            "invalid scalar: out of range")
+    finally:
+        rows.fill(0)                                                       # the packed copy of the keys, on every way out
+
+
+def getPublicKey(secretKey, isCompressed=True, engine=None):
+    return getPublicKeyBatch([secretKey], isCompressed, engine)[0]
+
+
+def sign_batch(messages, secretKeys, lowS=True, prehash=True, extraEntropy=False, format="compact", engine=None, verify=False):
+    """[secp256k1.sign(msg, sk, {lowS, prehash, extraEntropy, format}) for each pair] in one launch.  secretKeys: one key per
+    message, or a single bytes object that signs every message.  With prehash the SHA-256 of every message runs on the device; with
+    prehash=False a message of up to 8192 bytes is brought here to the 32 bytes bits2int keeps (left-padded, or cut to its leading
+    32).  extraEntropy: False / None, True (32 fresh bytes from os.urandom per row), one 32-byte value for every row, or a list of
+    32-byte values; the batch form offers no other length.  format: "compact", "recovered" (recovery id || r || s, what
+    recoverPublicKeyBatch takes) or "der".  verify=True runs verify_batch over the result."""
+    n = len(messages)
+    for name, v in (("lowS", lowS), ("prehash", prehash)):
+        if not isinstance(v, bool):
+            raise TypeError('"%s" expected boolean' % name)
+    if format not in ("compact", "recovered", "der"):
+        raise ValueError('Signature format must be "compact", "recovered", or "der"')
+    rows, one_key = _secret_rows(secretKeys)
+    X = None
+    try:                                                                   # the packed keys and extra entropy are zeroed on every way out
+        if not one_key and rows.shape[0] != n:
+            raise ValueError("arrays of messages and secret keys must have equal length")
+        msgs = [_amsg(m) for m in messages]
+        if extraEntropy is True:
+            X = np.frombuffer(os.urandom(32 * n), np.uint8).reshape(n, 32).copy()
+        elif extraEntropy is not None and extraEntropy is not False:
+            extra = [extraEntropy] * n if isinstance(extraEntropy, (bytes, bytearray, memoryview)) else list(extraEntropy)
+            extra = [_amsg(e, "extraEntropy") for e in extra]
+            if len(extra) != n:
+                raise ValueError("arrays of messages and extra entropy must have equal length")
+            if any(len(e) != 32 for e in extra):
+                raise ValueError("only 32-byte extra entropy is offered in batch")
+            X = np.frombuffer(b"".join(extra), np.uint8).reshape(n, 32).copy()
+        if n == 0:
+            return []
+        eng = engine or get_engine()
+        if prehash:
+            sig, rec, ok = eng.ecdsa_sign_batch(rows, msgs=msgs, extra=X, low_s=lowS, one_key=one_key)
+        else:
+            H = np.zeros((n, 32), np.uint8)
+            for i, m in enumerate(msgs):
+                H[i] = np.frombuffer(bits2int(m).to_bytes(32, "big"), np.uint8)
+            sig, rec, ok = eng.ecdsa_sign_batch(rows, hashes=H, extra=X, low_s=lowS, one_key=one_key)
+        out = []
+        for i in range(n):
+            if not ok[i]:
+                raise ValueError(_refused_key(rows[0 if one_key else i], "invalid private key") or "drbg: tried max amount of iterations")
+            b = bytes(sig[i])
+            if format == "recovered":
+                b = bytes([rec[i]]) + b
+            elif format == "der":
+                b = rs_to_der(int.from_bytes(b[:32], "big"), int.from_bytes(b[32:], "big"))
+            out.append(b)
+        if verify:
+            pub = _public_keys(eng, rows, SECP_PK_COMPRESSED, "invalid scalar: out of range")
+            keys = pub * n if one_key else pub
+            if not all(verify_batch([bytes(r) for r in sig], msgs, keys, lowS=lowS, prehash=prehash, engine=eng)):
+                raise ValueError("sign: Invalid signature produced")
+        return out
+    finally:
+        rows.fill(0)
+        if X is not None:
+            X.fill(0)
+
+
+def sign(message, secretKey, **opts):
+    return sign_batch([message], [secretKey], **opts)[0]
