@@ -280,6 +280,68 @@ static napi_value X25519(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// Ed448 signing and verification from messages on packed rows (ncg_ed448_public_key_batch, ncg_ed448_sign_batch,
+// ncg_ed448_verify_batch_msgs).  kind 0 (secret keys n x 57) -> n x 57 public keys.  kind 1 (keys, flags, dom, msgs, lens): keys n x 57 -
+// or ONE row, which selects NCG_ED448_SIGN_ONE_KEY; flags: the PREHASH bit; dom: the domain prefix; msgs: the messages back to back;
+// lens: n message lengths as LE uint32 -> n x 114 signatures, then n ok flags (a refused row is zero).  kind 2 (sigs n x 114, flags, dom,
+// msgs, lens, publicKeys n x 57) -> n verdicts, the challenge hashed on the device.
+static napi_value Ed448Sign(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t kind, flags = 0;
+  uint8_t *keys, *dom = nullptr, *msgs = nullptr, *lens = nullptr, *pks = nullptr, *out;
+  size_t kl, dl = 0, ml = 0, ll = 0, pl = 0;
+  if (argc < 2 || napi_get_value_int32(env, argv[0], &kind) != napi_ok || kind < 0 || kind > 2 || !get_u8(env, argv[1], &keys, &kl) ||
+      kl % (kind == 2 ? 114 : 57) ||
+      (kind >= 1 && (argc < 6 || napi_get_value_int32(env, argv[2], &flags) != napi_ok || !get_u8(env, argv[3], &dom, &dl) ||
+                     !get_u8(env, argv[4], &msgs, &ml) || !get_u8(env, argv[5], &lens, &ll) || ll % 4)) ||
+      (kind == 2 && (argc < 7 || !get_u8(env, argv[6], &pks, &pl)))) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: ed448Sign(kind, keys of 57 bytes | signatures of 114[, flags, dom, msgs, lens[, publicKeys]])");
+    return nullptr;
+  }
+  if (kind == 0) {
+    const size_t n = kl / 57;
+    napi_value res = make_u8(env, n * 57, &out);
+    if (!res) return nullptr;
+    if (n && ncg_ed448_public_key_batch(g_ctx, n, keys, out) != 0) return throw_native(env);
+    return res;
+  }
+  const size_t n = ll / 4;
+  std::vector<uint64_t> off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    uint32_t len;
+    memcpy(&len, lens + 4 * i, 4);
+    off[i + 1] = off[i] + len;
+  }
+  if (flags & ~NCG_ED448_PREHASH) {
+    napi_throw_error(env, nullptr, "noble-gpu: ed448Sign: flags may hold the prehash bit (4) only");
+    return nullptr;
+  }
+  if (kind == 2) {
+    if (off[n] != ml || kl != 114 * n || pl != 57 * n) {
+      napi_throw_error(env, nullptr, "arrays of signatures, messages and public keys must have equal length");
+      return nullptr;
+    }
+    napi_value res = make_u8(env, n, &out);
+    if (!res) return nullptr;
+    if (n && ncg_ed448_verify_batch_msgs(g_ctx, n, keys, pks, flags, dl ? dom : nullptr, dl, ml ? msgs : nullptr, off.data(), out) != 0)
+      return throw_native(env);
+    return res;
+  }
+  if (off[n] != ml || (kl != 57 * n && kl != 57)) {
+    napi_throw_error(env, nullptr, "arrays of messages and secret keys must have equal length");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n * 115, &out);
+  if (!res) return nullptr;
+  if (kl != 57 * n) flags |= NCG_ED448_SIGN_ONE_KEY;
+  if (n && ncg_ed448_sign_batch(g_ctx, n, keys, flags, dl ? dom : nullptr, dl, ml ? msgs : nullptr, off.data(), out, out + n * 114) != 0)
+    return throw_native(env);
+  return res;
+}
+
 // Ed25519 signing on packed rows (ncg_ed25519_public_key_batch, ncg_ed25519_sign_batch).  kind 0 (secret keys n x 32) -> n x 32 public
 // keys.  kind 1 (keys, flags, dom, msgs, lens): keys n x 32 - or ONE row, which selects NCG_ED25519_SIGN_ONE_KEY; flags: the PREHASH bit;
 // dom: the domain prefix (may be empty); msgs: the messages back to back; lens: n message lengths as LE uint32 -> n x 64 signatures,
@@ -1170,7 +1232,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

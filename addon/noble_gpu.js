@@ -16,7 +16,10 @@
 //                                            ed25519ph (prehash: true) (edwards.ts:908-930, ed25519.ts:146-223), hashes included, on the
 //                                            device; ed25519GetPublicKey / ed25519Sign: single-item forms with the reference's messages
 //   x448ScalarMultBatch(items), x448GetPublicKeyBatch(secretKeys) - x448.scalarMult / getPublicKey (ed448.ts:284-311);
-//   ed448VerifyBatch(items, { context, prehash }) - ed448 / ed448ph verify, the SHAKE256 challenge hashed here on the host
+//   ed448VerifyBatch(items, { context, prehash, deviceHash }) - ed448 / ed448ph verify, the SHAKE256 challenge hashed here on the
+//                                            host, or on the device with deviceHash: true
+//   ed448GetPublicKeyBatch(secretKeys), ed448SignBatch(items | {msgs, secretKey}, { context, prehash }) - eddsa.getPublicKey / sign
+//                                            for ed448 and ed448ph, every hash on the device; ed448GetPublicKey / ed448Sign: single items
 //   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
 //                                            BASE.multiply, an MSM from encodings and ristretto255_hasher.deriveToCurve
 //                                            (src/ed25519.ts:443-668), with single-item forms that throw the reference's messages
@@ -756,8 +759,9 @@ function schnorrSign(msg, secretKey, auxRand) {
 }
 
 // ---- X448 and Ed448 verification (ed448.ts; abstract/montgomery.ts:247-420, abstract/edwards.ts:942-989) ----------------------
-// The same buffers-in / buffers-out convention as the X25519 calls.  Hashing stays on the host: the challenge
-// k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114) mod n and the ed448ph prehash use crypto.createHash('shake256').
+// The same buffers-in / buffers-out convention as the X25519 calls.  ed448VerifyBatch hashes on the host by default: the challenge
+// k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114) mod n and the ed448ph prehash use crypto.createHash('shake256');
+// opts.deviceHash: true sends the messages and the domain prefix to the device instead (ncg_ed448_verify_batch_msgs).
 function abytesT(b, len, title) {               // utils abytes(value, length | undefined, title)
   const bytes = b instanceof Uint8Array;
   if (!bytes || (len !== undefined && b.length !== len))
@@ -828,16 +832,79 @@ function ed448VerifyBatch(items, opts = {}) {
         throw new Error('context must be smaller than 255, got: ' + context.length);
       continue;
     }
-    if (prehash) msg = shake256(64, msg);
-    const dom = Buffer.concat([Buffer.from('SigEd448'), Buffer.from([prehash ? 1 : 0, context.length]), context]);
     S.set(sig, 114 * i);
     A.set(pk, 57 * i);
+    if (opts.deviceHash) continue;
+    if (prehash) msg = shake256(64, msg);
+    const dom = Buffer.concat([Buffer.from('SigEd448'), Buffer.from([prehash ? 1 : 0, context.length]), context]);
     leBytes(leNumber(shake256(114, dom, sig.subarray(0, 57), pk, msg), 0, 114) % ED448_N, 56, K, 56 * i);
   }
   if (n === 0) return [];
   if (context.length > 255) return new Array(n).fill(false);
   init();
+  if (opts.deviceHash) {
+    const { blob, lens } = ed448Blob(items.map((it) => it.msg));
+    return Array.from(native.ed448Sign(2, S, prehash ? 4 : 0, ed448Dom(opts).dom, blob, lens, A), (v) => v === 1);
+  }
   return Array.from(native.ed448(2, S, A, K), (v) => v === 1);
+}
+// ---- Ed448 signing (abstract/edwards.ts:866-930, ed448.ts:190-246): getPublicKey and sign for ed448 / ed448ph.  Every SHAKE256, the two
+// multiplications and the scalar arithmetic run on the device; only the domain prefix is built here.  opts.context: at most 255 bytes;
+// opts.prehash: true selects ed448ph.  Batch forms return null for a row the device refused (r = 0 mod n); the single-item forms throw
+// the reference's messages.
+function ed448Dom(opts) {                       // dom4 (ed448.ts:190-201)
+  const prehash = !!(opts && opts.prehash);
+  const ctx = opts && opts.context !== undefined ? abytesT(opts.context, undefined, 'context') : new Uint8Array(0);
+  if (ctx.length > 255) throw new Error('context must be smaller than 255, got: ' + ctx.length);
+  const dom = new Uint8Array(10 + ctx.length);
+  dom.set(Buffer.from('SigEd448', 'ascii'), 0);
+  dom[8] = prehash ? 1 : 0;
+  dom[9] = ctx.length;
+  dom.set(ctx, 10);
+  return { dom, flags: prehash ? 4 : 0 };
+}
+function ed448Blob(msgs) {                      // the messages back to back and their lengths as LE uint32
+  const n = msgs.length, lens = new Uint8Array(4 * n), view = new DataView(lens.buffer);
+  let total = 0;
+  for (let i = 0; i < n; i++) {
+    view.setUint32(4 * i, abytesT(msgs[i], undefined, 'message').length, true);
+    total += msgs[i].length;
+  }
+  const blob = new Uint8Array(total);
+  for (let i = 0, at = 0; i < n; at += msgs[i++].length) blob.set(msgs[i], at);
+  return { blob, lens };
+}
+function ed448GetPublicKeyBatch(secretKeys) {
+  const n = secretKeys.length, S = new Uint8Array(57 * n);
+  secretKeys.forEach((k, i) => S.set(abytesT(k, 57, 'secretKey'), 57 * i));
+  if (n === 0) return [];
+  init();
+  const out = native.ed448Sign(0, S);
+  S.fill(0);
+  return Array.from({ length: n }, (_, i) => out.slice(57 * i, 57 * i + 57));
+}
+// items: [{msg, secretKey}] - or {msgs, secretKey}: ONE key signing many messages (opts.oneKey says the same: the key crosses once)
+function ed448SignBatch(items, opts) {
+  const one = !Array.isArray(items);
+  if (opts && opts.oneKey !== undefined && !!opts.oneKey !== one) throw new Error('oneKey goes with {msgs, secretKey}');
+  const msgs = one ? items.msgs : items.map((it) => it.msg);
+  const n = msgs.length;
+  const K = new Uint8Array(one ? 57 : 57 * n);
+  const { blob, lens } = ed448Blob(msgs);
+  if (one) K.set(abytesT(items.secretKey, 57, 'secretKey'), 0);
+  else items.forEach((it, i) => K.set(abytesT(it.secretKey, 57, 'secretKey'), 57 * i));
+  const { dom, flags } = ed448Dom(opts);          // the key is checked before the context, as in the reference
+  if (n === 0) return [];
+  init();
+  const out = native.ed448Sign(1, K, flags, dom, blob, lens);
+  K.fill(0);
+  return Array.from({ length: n }, (_, i) => (out[114 * n + i] === 1 ? out.slice(114 * i, 114 * i + 114) : null));
+}
+function ed448GetPublicKey(secretKey) { return ed448GetPublicKeyBatch([secretKey])[0]; }
+function ed448Sign(msg, secretKey, opts) {
+  const r = ed448SignBatch([{ msg, secretKey }], opts)[0];
+  if (r === null) throw new Error('invalid scalar: expected 1 <= sc < curve.n');   // BASE.multiply(0), edwards.ts:920-924
+  return r;
 }
 
 const X25519_P = (1n << 255n) - 19n;
@@ -1305,6 +1372,7 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    secp256k1GetPublicKeyBatch, ecdsaSignBatch, schnorrGetPublicKeyBatch, schnorrSignBatch, secp256k1GetPublicKey, schnorrGetPublicKey,
                    secp256k1Sign, schnorrSign,
                    x448ScalarMultBatch, x448GetPublicKeyBatch, ed448VerifyBatch,
+                   ed448GetPublicKeyBatch, ed448SignBatch, ed448GetPublicKey, ed448Sign,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
                    ristrettoDeriveToCurve,

@@ -624,6 +624,64 @@ int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const voi
 int ncg_ed448_verify_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, const void* k56_dev,
                                uint8_t* out_ok_dev, void* stream);
 
+/* ---- SHAKE256, Ed448 signing and Ed448 verification from messages ----------------------------------------------------------
+ * eddsa.getPublicKey / getExtendedPublicKey / sign / verify of ed448 and ed448ph (src/ed448.ts:190-246 over
+ * src/abstract/edwards.ts:866-989) with every hash on the device (Keccak-f[1600], one message per lane):
+ *   h = SHAKE256(seed57, 114); scalar = clamp(h[0..57)) mod n; prefix = h[57..114); A = [scalar]B
+ *   r = SHAKE256(dom || prefix || PH(M), 114) mod n; R = [r]B; k = SHAKE256(dom || R || A || PH(M), 114) mod n; S = r + k scalar mod n
+ * msgs / msg_off are as for ncg_ed25519_verify_batch_msgs: n + 1 byte offsets into one blob; the offsets must not decrease; msgs
+ * may be NULL when every message is empty.  dom is the domain prefix "SigEd448" || phflag || len(ctx) || ctx that the CALLER
+ * builds, a HOST pointer in both forms, NULL only with dom_len 0, at most NCG_ED448_DOM_MAX bytes; the library hashes whatever
+ * it is given.  Packed rows of 57 (seeds, public keys) and 114 bytes (signatures) may sit at any address; expanded key rows
+ * (NCG_ED448_KEY_BYTES) and out_k56 are read and written as words: a DEVICE pointer to them must be 4-byte aligned and is refused
+ * otherwise.  Unknown flag bits, dom_len above the maximum and out_len outside 1 .. 65535 return NCG_ERR_INVALID_ARG; n = 0 returns
+ * NCG_OK and touches nothing; n >= 2^31 is refused ("too large") before any buffer is read.
+ *
+ * ncg_shake256_batch: out[i] = SHAKE256(message i, out_len), rows of out_len bytes.
+ * ncg_ed448_challenge_batch_dev: out_k56[i] = k of row i, reduced mod n (56 bytes).  flags: NCG_ED448_PREHASH.
+ * ncg_ed448_verify_batch_msgs: ncg_ed448_challenge_batch_dev, then ncg_ed448_verify_batch_dev, on one stream.
+ * ncg_ed448_public_key_batch: out_pk57[i] = getPublicKey(seed57[i]).
+ * ncg_ed448_expand_key_batch: out_key172[i] = scalar (56 bytes LE, below n) || prefix (57) || A (57) || 2 zero bytes, the row that
+ * ncg_ed448_sign_batch takes with NCG_ED448_SIGN_EXPANDED.
+ * ncg_ed448_sign_batch: out_sig114[i] = R || S of message i under key i (or under the one key row, NCG_ED448_SIGN_ONE_KEY).
+ * out_ok[i] = 0 with 114 zero bytes where r = 0 mod n, the one case in which the reference throws (edwards.ts:920-924); the scalar
+ * of a key is never 0 mod n.  The secret scalars never select an address or a branch (double, always add, select), but the library
+ * makes no constant-time claim.  The workspace and the staged keys of a host form are cleared on the call's stream before the call
+ * returns.
+ *
+ * ncg_ed448_sign_check: the lane code of csrc/keccak.hpp and csrc/ed448_sign.hpp on n rows of RAW uint32 words, in the style of
+ * ncg_fe448_check.  Words per row (a, b, out), per op:
+ *   0  keccak_f1600                (50,  0, 50)   the 25 lanes as 50 LE words
+ *   1  x mod n                     (29,  0, 14)   x below 2^912: word 28 is taken below 2^16
+ *   2  (r + k s) mod n             (28, 14, 14)   a = r || k, b = s, all below n
+ *   3  sign with the nonce GIVEN   (43, 30, 30)   a = an expanded key row, b = r (14 words, below n) || a 64-byte message;
+ *                                                 out = R || S, 2 zero bytes, ok as one word; ed448, empty context
+ * `variant` is not read.  b is required (non-NULL) even where its width is 0.  An op nobody defines reads nothing and leaves out
+ * zero (rows of 16 words).  n above 2^24 is refused. */
+#define NCG_ED448_SIGN_EXPANDED 1   /* keys are NCG_ED448_KEY_BYTES rows, not 57-byte seeds */
+#define NCG_ED448_SIGN_ONE_KEY  2   /* one key row serves all n messages */
+#define NCG_ED448_PREHASH       4   /* hash each message with SHAKE256(M, 64) first (ed448ph); sign, challenge and verify_msgs */
+#define NCG_ED448_DOM_MAX   265     /* "SigEd448" || phflag || len(ctx) || ctx: 10 + 255 */
+#define NCG_ED448_KEY_BYTES 172     /* scalar (56 LE, < n) || prefix (57) || A (57) || 2 zero bytes; 4-byte aligned on the device */
+int ncg_shake256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, size_t out_len, void* out);
+int ncg_shake256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, size_t out_len, void* out_dev,
+                           void* stream);
+int ncg_ed448_challenge_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, int flags, const void* dom,
+                                  size_t dom_len, const void* msgs_dev, const uint64_t* msg_off_dev, void* out_k56_dev, void* stream);
+int ncg_ed448_verify_batch_msgs(ncg_ctx* ctx, size_t n, const void* sig114, const void* pk57, int flags, const void* dom, size_t dom_len,
+                                const void* msgs, const uint64_t* msg_off, uint8_t* out_ok);
+int ncg_ed448_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, int flags, const void* dom,
+                                    size_t dom_len, const void* msgs_dev, const uint64_t* msg_off_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_ed448_public_key_batch(ncg_ctx* ctx, size_t n, const void* seed57, void* out_pk57);
+int ncg_ed448_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed57_dev, void* out_pk57_dev, void* stream);
+int ncg_ed448_expand_key_batch(ncg_ctx* ctx, size_t n, const void* seed57, void* out_key172);
+int ncg_ed448_expand_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed57_dev, void* out_key172_dev, void* stream);
+int ncg_ed448_sign_batch(ncg_ctx* ctx, size_t n, const void* keys, int flags, const void* dom, size_t dom_len, const void* msgs,
+                         const uint64_t* msg_off, void* out_sig114, uint8_t* out_ok);
+int ncg_ed448_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* keys_dev, int flags, const void* dom, size_t dom_len,
+                             const void* msgs_dev, const uint64_t* msg_off_dev, void* out_sig114_dev, uint8_t* out_ok_dev, void* stream);
+int ncg_ed448_sign_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
 /* ---- decaf448 (RFC 9496 section 5): _DecafPoint and decaf448_hasher of the reference's src/ed448.ts ---------------------
  * The prime-order group over edwards448.  An element is handled through an Edwards representative: an Ed448 affine point x || y,
  * 56 canonical little-endian bytes each, the format ncg_ed448_add_pairs_batch and ncg_ed448_encode_batch take.  Encodings, scalars,

@@ -41,6 +41,10 @@ FIELD_CHECK_WORDS = {
     16: (36, 9, 36), 17: (36, 9, 36)}
 X448_ONE_SCALAR = 1     # ncg_x448_batch flag: one secret for every row
 ED448_ONE_SCALAR = 1    # ncg_ed448_mul_batch flag: one scalar for every row
+ED448_SIGN_EXPANDED, ED448_SIGN_ONE_KEY, ED448_PREHASH = 1, 2, 4   # ncg_ed448_sign_batch flags (PREHASH: challenge and verify_msgs too)
+ED448_DOM_MAX, ED448_KEY_BYTES = 265, 172
+# ncg_ed448_sign_check: op -> words per row of a, b, out
+ED448_SIGN_CHECK_WORDS = {0: (50, 0, 50), 1: (29, 0, 14), 2: (28, 14, 14), 3: (43, 30, 30)}
 # ncg_fe448_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/ed448.hpp)
 FE448_CHECK_WORDS = {0: (16, 16, 16), 1: (16, 0, 16), 2: (16, 16, 48), 3: (16, 16, 16), 4: (16, 0, 14), 5: (14, 0, 16), 6: (16, 0, 16),
                      7: (16, 0, 16), 8: (64, 16, 64), 9: (48, 48, 48), 10: (48, 0, 48)}
@@ -187,6 +191,18 @@ _OPTIONAL_PROTOS = {
     "ncg_ed448_verify_batch": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_ed448_verify_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp, _vp],
     "ncg_fe448_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
+    "ncg_shake256_batch": [_vp, _sz, _vp, _vp, _sz, _vp],
+    "ncg_shake256_batch_dev": [_vp, _sz, _vp, _vp, _sz, _vp, _vp],
+    "ncg_ed448_challenge_batch_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_verify_batch_msgs": [_vp, _sz, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_verify_batch_msgs_dev": [_vp, _sz, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_public_key_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed448_public_key_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_expand_key_batch": [_vp, _sz, _vp, _vp],
+    "ncg_ed448_expand_key_batch_dev": [_vp, _sz, _vp, _vp, _vp],
+    "ncg_ed448_sign_batch": [_vp, _sz, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_ed448_sign_batch_dev": [_vp, _sz, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_ed448_sign_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
     "ncg_decaf448_decode_batch": [_vp, _sz, _vp, _vp, _vp],
     "ncg_decaf448_decode_batch_dev": [_vp, _sz, _vp, _vp, _vp, _vp],
     "ncg_decaf448_encode_batch": [_vp, _sz, _vp, _vp],
@@ -839,6 +855,110 @@ class Engine:
         out = np.zeros((n, wo), dtype=np.uint32)
         if n:
             self._check(self.lib.ncg_fe448_check(self.h, op, variant, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
+        return out
+
+    # ---- SHAKE256, Ed448 signing and verification from messages: seeds [n, 57], expanded key rows [n, 172] (scalar || prefix || A ||
+    # 2 zero bytes), signatures [n, 114]; dom is the whole domain prefix "SigEd448" || phflag || len(ctx) || ctx ------------------
+    @staticmethod
+    def _blob_off(msgs_blob, msg_off):
+        blob = np.ascontiguousarray(msgs_blob, dtype=np.uint8).reshape(-1)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint64).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError("message offsets: n + 1 values are needed")
+        return blob, off, off.shape[0] - 1
+
+    def shake256_batch(self, msgs_blob, msg_off, out_len):
+        """SHAKE256(message i, out_len) per row -> uint8 [n, out_len]"""
+        blob, off, n = self._blob_off(msgs_blob, msg_off)
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_shake256_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, out_len,
+                                                    out.ctypes.data))
+        return out
+
+    def shake256_batch_dev(self, n, d_msgs, d_off, out_len, d_out, stream=None):
+        self._check(self.lib.ncg_shake256_batch_dev(self.h, n, d_msgs, d_off, out_len, d_out, stream))
+
+    def ed448_challenge_batch_dev(self, n, d_sigs, d_pks, dom, d_msgs, d_off, d_ks, prehash=False, stream=None):
+        dom = bytes(dom)
+        self._check(self.lib.ncg_ed448_challenge_batch_dev(self.h, n, d_sigs, d_pks, ED448_PREHASH if prehash else 0, dom if dom else None,
+                                                           len(dom), d_msgs, d_off, d_ks, stream))
+
+    def ed448_verify_batch_msgs(self, sigs, pks, msgs_blob, msg_off, dom, prehash=False):
+        """ed448 verify (strict, cofactored) from the messages: the challenge hash runs on the device -> bool [n]"""
+        sigs, pks = self._rows(sigs, 114), self._rows(pks, 57)
+        blob, off, n = self._blob_off(msgs_blob, msg_off)
+        if sigs.shape[0] != n or pks.shape[0] != n:
+            raise ValueError("arrays of signatures, public keys and message offsets must have matching lengths")
+        dom = bytes(dom)
+        ok = np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_verify_batch_msgs(self.h, n, sigs.ctypes.data, pks.ctypes.data, ED448_PREHASH if prehash else 0,
+                                                             dom if dom else None, len(dom), blob.ctypes.data if blob.size else None,
+                                                             off.ctypes.data, ok.ctypes.data))
+        return ok.astype(bool)
+
+    def ed448_verify_batch_msgs_dev(self, n, d_sigs, d_pks, dom, d_msgs, d_off, d_ok, prehash=False, stream=None):
+        dom = bytes(dom)
+        self._check(self.lib.ncg_ed448_verify_batch_msgs_dev(self.h, n, d_sigs, d_pks, ED448_PREHASH if prehash else 0, dom if dom else None,
+                                                             len(dom), d_msgs, d_off, d_ok, stream))
+
+    def ed448_public_key_batch(self, seeds):
+        """eddsa.getPublicKey per row: [n, 57] -> [n, 57]"""
+        seeds = self._rows(seeds, 57)
+        out = np.zeros((seeds.shape[0], 57), dtype=np.uint8)
+        if seeds.shape[0]:
+            self._check(self.lib.ncg_ed448_public_key_batch(self.h, seeds.shape[0], seeds.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed448_public_key_batch_dev(self, n, d_seeds, d_out, stream=None):
+        self._check(self.lib.ncg_ed448_public_key_batch_dev(self.h, n, d_seeds, d_out, stream))
+
+    def ed448_expand_key_batch(self, seeds):
+        """getExtendedPublicKey per row, as the 172-byte rows that ed448_sign_batch takes with expanded=True"""
+        seeds = self._rows(seeds, 57)
+        out = np.zeros((seeds.shape[0], ED448_KEY_BYTES), dtype=np.uint8)
+        if seeds.shape[0]:
+            self._check(self.lib.ncg_ed448_expand_key_batch(self.h, seeds.shape[0], seeds.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed448_expand_key_batch_dev(self, n, d_seeds, d_out, stream=None):
+        self._check(self.lib.ncg_ed448_expand_key_batch_dev(self.h, n, d_seeds, d_out, stream))
+
+    def ed448_sign_batch(self, keys, msgs_blob, msg_off, dom, expanded=False, one_key=False, prehash=False):
+        """keys: seeds [n, 57] or expanded rows [n, 172] (ONE row with one_key); msgs_blob / msg_off as for ed448_verify_batch_msgs
+        -> (signatures uint8 [n, 114], ok bool [n])."""
+        keys = self._rows(keys, ED448_KEY_BYTES if expanded else 57)
+        blob, off, n = self._blob_off(msgs_blob, msg_off)
+        if keys.shape[0] != (1 if one_key else n):
+            raise ValueError("arrays of keys and message offsets must have matching lengths")
+        dom = bytes(dom)
+        flags = (ED448_SIGN_EXPANDED if expanded else 0) | (ED448_SIGN_ONE_KEY if one_key else 0) | (ED448_PREHASH if prehash else 0)
+        sig, ok = np.zeros((n, 114), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_sign_batch(self.h, n, keys.ctypes.data, flags, dom if dom else None, len(dom),
+                                                      blob.ctypes.data if blob.size else None, off.ctypes.data, sig.ctypes.data,
+                                                      ok.ctypes.data))
+        return sig, ok.astype(bool)
+
+    def ed448_sign_batch_dev(self, n, d_keys, dom, d_msgs, d_off, d_sigs, d_ok, flags=0, stream=None):
+        dom = bytes(dom)
+        self._check(self.lib.ncg_ed448_sign_batch_dev(self.h, n, d_keys, flags, dom if dom else None, len(dom), d_msgs, d_off, d_sigs, d_ok,
+                                                      stream))
+
+    def ed448_sign_check(self, op, a_words, b_words):
+        """The lane code of Keccak-f[1600], the reduction mod the Ed448 group order and signing with a given nonce on raw uint32 rows
+        (ncg_ed448_sign_check; ED448_SIGN_CHECK_WORDS has the widths): a [n, wa], b [n, wb] (any array where wb = 0) -> [n, wo];
+        an unknown op gives [n, 16] zeros."""
+        wa, wb, wo = ED448_SIGN_CHECK_WORDS.get(op, (0, 0, 16))
+        a = np.ascontiguousarray(a_words, dtype=np.uint32)
+        b = np.ascontiguousarray(b_words, dtype=np.uint32)
+        n = a.shape[0]
+        if (wa and a.shape[1] != wa) or (wb and (b.shape[0] != n or b.shape[1] != wb)):
+            raise ValueError("ed448_sign_check: op %d takes rows of %d and %d words" % (op, wa, wb))
+        out = np.zeros((n, wo), dtype=np.uint32)
+        if n:
+            self._check(self.lib.ncg_ed448_sign_check(self.h, op, 0, n, a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out
 
     # ---- decaf448: encodings and scalars uint8 [n, 56], Edwards representatives (Ed448 affine points) and uniform bytes [n, 112] ----

@@ -368,6 +368,7 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->ed_sign_ws) (void)hipFree(ctx->ed_sign_ws);
   if (ctx->secp_scan_tab) (void)hipFree(ctx->secp_scan_tab);
   if (ctx->secp_sign_ws) (void)hipFree(ctx->secp_sign_ws);
+  if (ctx->ed448_ws) (void)hipFree(ctx->ed448_ws);
   if (ctx->ecdsa_ws) (void)hipFree(ctx->ecdsa_ws);
   for (int i = 0; i < 4; i++)
     if (ctx->base_tab[i]) (void)hipFree(ctx->base_tab[i]);
@@ -1564,16 +1565,20 @@ static int ensure_ed_scan_table(ncg_ctx* ctx) {
   return NCG_OK;
 }
 constexpr int ED_SIGN_FLAGS = NCG_ED25519_SIGN_EXPANDED | NCG_ED25519_SIGN_ONE_KEY | NCG_ED25519_SIGN_PREHASH;
-static Rule ed_sign_rule(ncg_ctx* ctx, const char* op, int flags, const void* dom, size_t dom_len, std::initializer_list<const void*> word_rows) {
+// the rule of the EdDSA signers (Ed25519 here, Ed448 below): the flag bits the entry point knows, dom, and the rows it reads as words
+static Rule eddsa_sign_rule(ncg_ctx* ctx, const char* op, int flags, int known_flags, const void* dom, size_t dom_len, size_t dom_max,
+                            const char* what_rows, std::initializer_list<const void*> word_rows) {
   int rc = NCG_OK;
-  if (flags & ~ED_SIGN_FLAGS) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
-  else if (dom_len > NCG_ED25519_DOM_MAX)
-    rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: dom_len %zu above %d", op, dom_len, NCG_ED25519_DOM_MAX);
+  if (flags & ~known_flags) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
+  else if (dom_len > dom_max) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: dom_len %zu above %d", op, dom_len, (int)dom_max);
   else if (dom_len && !dom) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer (dom)", op);
   else
     for (const void* p : word_rows)
-      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: key and signature rows must be 4-byte aligned", op);
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: %s must be 4-byte aligned", op, what_rows);
   return {op, rc};
+}
+static Rule ed_sign_rule(ncg_ctx* ctx, const char* op, int flags, const void* dom, size_t dom_len, std::initializer_list<const void*> word_rows) {
+  return eddsa_sign_rule(ctx, op, flags, ED_SIGN_FLAGS, dom, dom_len, NCG_ED25519_DOM_MAX, "key and signature rows", word_rows);
 }
 static int ed_sign_ws(ncg_ctx* ctx, size_t words) {
   return ncg_grow_buf(ctx, &ctx->ed_sign_ws, &ctx->ed_sign_ws_bytes, words * 4, words * 4 + (words >> 1) + 4096, GrowWait::device);
@@ -2211,6 +2216,184 @@ int ncg_ed448_verify_batch(ncg_ctx* ctx, size_t n, const void* sig114, const voi
   const int sig = hc.in(sig114, n * 114), pk = hc.in(pk57, n * 57), k = hc.in(k56, n * 56), ok = hc.out(out_ok, n);
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ed448_verify_batch_dev(ctx, n, hc.dev(sig), hc.dev(pk), hc.dev(k), hc.dev<uint8_t>(ok), ctx->stream));
+}
+
+// ---- SHAKE256, Ed448 signing and verification from messages (ed448_sign.hip).  Seeds, public keys and signatures are packed bytes at
+// any address; expanded key rows and challenges are read and written as words and refused when misaligned on the device.  The
+// workspace holds scalars, prefixes and nonces during a signing call: it is cleared on the call's stream before the call returns,
+// and so is the staged copy of the keys of a host form.
+constexpr int ED448_SIGN_FLAGS = NCG_ED448_SIGN_EXPANDED | NCG_ED448_SIGN_ONE_KEY | NCG_ED448_PREHASH;
+static Rule ed448_sign_rule(ncg_ctx* ctx, const char* op, int flags, int known_flags, const void* dom, size_t dom_len,
+                            std::initializer_list<const void*> word_rows) {
+  return eddsa_sign_rule(ctx, op, flags, known_flags, dom, dom_len, NCG_ED448_DOM_MAX, "key rows and 56-byte rows", word_rows);
+}
+static Rule shake256_rule(ncg_ctx* ctx, size_t out_len) {
+  return {"shake256_batch", out_len >= 1 && out_len <= 65535
+                                ? NCG_OK
+                                : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: shake256_batch: out_len %zu out of range 1..65535", out_len)};
+}
+static int ed448_ws(ncg_ctx* ctx, size_t words) {
+  return ncg_grow_buf(ctx, &ctx->ed448_ws, &ctx->ed448_ws_bytes, words * 4, words * 4 + (words >> 1) + 4096, GrowWait::device);
+}
+int ncg_shake256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, size_t out_len, void* out_dev,
+                           void* stream) {
+  NCG_BEGIN(ctx, shake256_rule(ctx, out_len), n, msg_off_dev, out_dev);
+  NCG_HIP(ctx, ncg::shake256_batch((const uint8_t*)msgs_dev, msg_off_dev, (uint32_t)out_len, (uint8_t*)out_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_shake256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, size_t out_len, void* out) {
+  NCG_BEGIN(ctx, shake256_rule(ctx, out_len), n, msg_off, out);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "shake256_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out, n * out_len);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_shake256_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), out_len, hc.dev(o), ctx->stream));
+}
+
+int ncg_ed448_challenge_batch_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, int flags, const void* dom,
+                                  size_t dom_len, const void* msgs_dev, const uint64_t* msg_off_dev, void* out_k56_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, "ed448_challenge_batch", flags, NCG_ED448_PREHASH, dom, dom_len, {out_k56_dev}), n, sig114_dev, pk57_dev,
+            msg_off_dev, out_k56_dev);
+  const int prehash = (flags & NCG_ED448_PREHASH) != 0;
+  if (int rc = ed448_ws(ctx, ncg::ed448_challenge_ws_words((int)n, prehash))) return rc;
+  NCG_HIP(ctx, ncg::ed448_challenge_batch((const uint8_t*)sig114_dev, (const uint8_t*)pk57_dev, prehash, (const uint8_t*)dom, (uint32_t)dom_len,
+                                          (const uint8_t*)msgs_dev, msg_off_dev, (uint32_t*)out_k56_dev, (int)n, (uint32_t*)ctx->ed448_ws,
+                                          stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_verify_batch_msgs_dev(ncg_ctx* ctx, size_t n, const void* sig114_dev, const void* pk57_dev, int flags, const void* dom,
+                                    size_t dom_len, const void* msgs_dev, const uint64_t* msg_off_dev, uint8_t* out_ok_dev, void* stream) {
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, "ed448_verify_msgs", flags, NCG_ED448_PREHASH, dom, dom_len, {}), n, sig114_dev, pk57_dev, msg_off_dev,
+            out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  const int prehash = (flags & NCG_ED448_PREHASH) != 0;
+  const size_t cw = ncg::ed448_challenge_ws_words((int)n, prehash);   // the challenges follow the workspace of their hash
+  if (int rc = ed448_ws(ctx, cw + n * 14)) return rc;
+  uint32_t* ws = (uint32_t*)ctx->ed448_ws;
+  NCG_HIP(ctx, ncg::ed448_challenge_batch((const uint8_t*)sig114_dev, (const uint8_t*)pk57_dev, prehash, (const uint8_t*)dom, (uint32_t)dom_len,
+                                          (const uint8_t*)msgs_dev, msg_off_dev, ws + cw, (int)n, ws, st));
+  return ncg_ed448_verify_batch_dev(ctx, n, sig114_dev, pk57_dev, ws + cw, out_ok_dev, st);
+}
+int ncg_ed448_verify_batch_msgs(ncg_ctx* ctx, size_t n, const void* sig114, const void* pk57, int flags, const void* dom, size_t dom_len,
+                                const void* msgs, const uint64_t* msg_off, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, "ed448_verify_msgs", flags, NCG_ED448_PREHASH, dom, dom_len, {}), n, sig114, pk57, msg_off, out_ok);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int sig = hc.in(sig114, n * 114), pk = hc.in(pk57, n * 57);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed448_verify_msgs", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_verify_batch_msgs_dev(ctx, n, hc.dev(sig), hc.dev(pk), flags, dom, dom_len, hc.dev(msg), hc.dev<const uint64_t>(off),
+                                                   hc.dev<uint8_t>(ok), ctx->stream));
+}
+
+// seeds -> public keys (rows false: 57 packed bytes per row at `out`) or expanded rows (rows true: NCG_ED448_KEY_BYTES per row)
+static int ed448_expand_dev(ncg_ctx* ctx, const char* op, size_t n, const void* seed57_dev, void* out_dev, bool rows, void* stream) {
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, op, 0, 0, nullptr, 0, {rows ? out_dev : nullptr}), n, seed57_dev, out_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint32_t* keys = (uint32_t*)out_dev;
+  if (!rows) {  // scalar || prefix stay in the workspace, only A goes out
+    if (int rc = ed448_ws(ctx, n * 43)) return rc;
+    keys = (uint32_t*)ctx->ed448_ws;
+  }
+  hipError_t e = ncg::ed448_expand_batch((const uint8_t*)seed57_dev, keys, rows ? (uint8_t*)keys + 113 : (uint8_t*)out_dev,
+                                         rows ? NCG_ED448_KEY_BYTES : 57, (int)n, st);
+  if (!rows) (void)hipMemsetAsync(ctx->ed448_ws, 0, n * NCG_ED448_KEY_BYTES, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_ed448_public_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed57_dev, void* out_pk57_dev, void* stream) {
+  return ed448_expand_dev(ctx, "ed448_public_key_batch", n, seed57_dev, out_pk57_dev, false, stream);
+}
+int ncg_ed448_expand_key_batch_dev(ncg_ctx* ctx, size_t n, const void* seed57_dev, void* out_key172_dev, void* stream) {
+  return ed448_expand_dev(ctx, "ed448_expand_key_batch", n, seed57_dev, out_key172_dev, true, stream);
+}
+static int ed448_expand_host(ncg_ctx* ctx, const char* op, size_t n, const void* seed57, void* out, size_t out_bytes) {
+  NCG_BEGIN(ctx, no_rule(op), n, seed57, out);
+  HostCall hc(ctx);
+  const int s = hc.in(seed57, n * 57), o = hc.out(out, n * out_bytes);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, s, n * 57);
+    return rc;
+  }
+  const int rc = out_bytes == 57 ? ncg_ed448_public_key_batch_dev(ctx, n, hc.dev(s), hc.dev(o), ctx->stream)
+                                 : ncg_ed448_expand_key_batch_dev(ctx, n, hc.dev(s), hc.dev(o), ctx->stream);
+  ed_clear_staged(hc, s, n * 57);
+  const int frc = hc.finish(rc);
+  if (out_bytes != 57 && frc == NCG_OK) (void)hipMemsetAsync(hc.dev(o), 0, n * out_bytes, ctx->stream);   // after the copy back, same stream
+  return frc;
+}
+int ncg_ed448_public_key_batch(ncg_ctx* ctx, size_t n, const void* seed57, void* out_pk57) {
+  return ed448_expand_host(ctx, "ed448_public_key_batch", n, seed57, out_pk57, 57);
+}
+int ncg_ed448_expand_key_batch(ncg_ctx* ctx, size_t n, const void* seed57, void* out_key172) {
+  return ed448_expand_host(ctx, "ed448_expand_key_batch", n, seed57, out_key172, NCG_ED448_KEY_BYTES);
+}
+
+int ncg_ed448_sign_batch_dev(ncg_ctx* ctx, size_t n, const void* keys_dev, int flags, const void* dom, size_t dom_len, const void* msgs_dev,
+                             const uint64_t* msg_off_dev, void* out_sig114_dev, uint8_t* out_ok_dev, void* stream) {
+  // seeds and signatures are read and written byte by byte; expanded rows as words
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, "ed448_sign_batch", flags, ED448_SIGN_FLAGS, dom, dom_len,
+                                 {(flags & NCG_ED448_SIGN_EXPANDED) ? keys_dev : nullptr}),
+            n, keys_dev, msg_off_dev, out_sig114_dev, out_ok_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  const int expanded = (flags & NCG_ED448_SIGN_EXPANDED) != 0, one_key = (flags & NCG_ED448_SIGN_ONE_KEY) != 0;
+  const int prehash = (flags & NCG_ED448_PREHASH) != 0;
+  const size_t words = ncg::ed448_sign_ws_words((int)n, expanded ? 0 : (one_key ? 1 : (int)n), prehash);
+  if (int rc = ed448_ws(ctx, words)) return rc;
+  hipError_t e = ncg::ed448_sign_batch(keys_dev, expanded, one_key, prehash, (const uint8_t*)dom, (uint32_t)dom_len, (const uint8_t*)msgs_dev,
+                                       msg_off_dev, (uint8_t*)out_sig114_dev, out_ok_dev, (int)n, (uint32_t*)ctx->ed448_ws, st);
+  (void)hipMemsetAsync(ctx->ed448_ws, 0, words * 4, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+int ncg_ed448_sign_batch(ncg_ctx* ctx, size_t n, const void* keys, int flags, const void* dom, size_t dom_len, const void* msgs,
+                         const uint64_t* msg_off, void* out_sig114, uint8_t* out_ok) {
+  NCG_BEGIN(ctx, ed448_sign_rule(ctx, "ed448_sign_batch", flags, ED448_SIGN_FLAGS, dom, dom_len, {}), n, keys, msg_off, out_sig114, out_ok);
+  const size_t kbytes = ((flags & NCG_ED448_SIGN_ONE_KEY) ? 1 : n) * ((flags & NCG_ED448_SIGN_EXPANDED) ? NCG_ED448_KEY_BYTES : 57);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  const int k = hc.in(keys, kbytes);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed448_sign_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int sig = hc.out(out_sig114, n * 114), ok = hc.out(out_ok, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, kbytes);
+    return rc;
+  }
+  const int rc = ncg_ed448_sign_batch_dev(ctx, n, hc.dev(k), flags, dom, dom_len, hc.dev(msg), hc.dev<const uint64_t>(off), hc.dev(sig),
+                                          hc.dev<uint8_t>(ok), ctx->stream);
+  ed_clear_staged(hc, k, kbytes);
+  return hc.finish(rc);
+}
+
+// The pieces of keccak.hpp / ed448_sign.hpp on raw words, in the style of ncg_fe448_check: an op nobody defines reads nothing and
+// leaves rows of 16 zero words.  Op 3 takes a key row and a nonce: the staged inputs and the workspace are cleared before the call
+// returns.
+int ncg_ed448_sign_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out) {
+  (void)variant;  // no op has variants
+  const Rule rule = {"ed448_sign_check", !ctx || n <= (1u << 24) ? NCG_OK
+                                             : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: ed448_sign_check: batch too large (max 2^24)")};
+  NCG_BEGIN(ctx, rule, n, a, b, out);
+  int wa, wb, wo;
+  ncg::ed448_sign_check_row_words(op, &wa, &wb, &wo);
+  const size_t ws_bytes = wo ? ncg::ed448_sign_check_ws_words() * 4 : 0;
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * wa * 4), db = hc.in(b, n * wb * 4);
+  const int o = hc.out(out, n * (wo ? wo : 16) * 4, true), w = hc.dev_only(ws_bytes);
+  if (int rc = hc.stage()) return rc;
+  hipError_t e = hipSuccess;
+  if (wo) {
+    e = ncg::ed448_sign_check(op, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, hc.dev<uint32_t>(w),
+                              ctx->stream);
+    (void)hipMemsetAsync(hc.dev(da), 0, n * wa * 4, ctx->stream);
+    if (wb) (void)hipMemsetAsync(hc.dev(db), 0, n * wb * 4, ctx->stream);
+  }
+  NCG_HIP(ctx, e);
+  return hc.finish(NCG_OK);
 }
 
 // ---- decaf448 (decaf448.hip).  Every buffer but the flag bytes is made of 56-byte rows read as 14 LE words: the alignment rule of

@@ -57,6 +57,10 @@ struct ncg_ctx {
   uint32_t* secp_scan_tab = nullptr;
   void* secp_sign_ws = nullptr;
   size_t secp_sign_ws_bytes = 0;
+  // Ed448 signing and the message-taking verify (ed448_sign.hip): the workspace of one call (dom, nonces or challenges, prehashes,
+  // expanded keys) - it holds secrets during a signing call and is cleared on the call's stream before the call returns
+  void* ed448_ws = nullptr;
+  size_t ed448_ws_bytes = 0;
   void* ecdsa_ws = nullptr;     // ECDSA batch verify: decoded keys, u1 / u2, partial points (device)
   size_t ecdsa_ws_bytes = 0;
   uint32_t* base_tab[4] = {nullptr, nullptr, nullptr, nullptr};  // fixed-base tables per curve (device)

@@ -271,6 +271,31 @@ void ed448_to_montgomery_host(const uint8_t* pk, uint32_t* out, uint8_t* out_ok,
 void ed448_verify_host(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, uint8_t* out_ok, int n);
 int fe448_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// SHAKE256, Ed448 signing and the challenge of Ed448 verification (ed448_sign.hip).  Seeds are 57 packed bytes; an expanded key is 43
+// LE words: scalar (14) || prefix (57 bytes) || A (57 bytes) || 2 zero bytes; signatures are 114 packed bytes, r and k 14 words.
+// dom_host is a HOST pointer (at most 265 bytes).  ed448_sign_batch: keys are seeds or expanded rows (`expanded`), one per message or
+// ONE for all (`one_key`); ws: ed448_sign_ws_words(n, rows to expand, prehash) words of device memory that hold secrets afterwards.
+// ed448_challenge_batch: ws of ed448_challenge_ws_words(n, prehash) words.  ed448_expand_batch: see ed448_sign.hip.
+hipError_t shake256_batch(const uint8_t* msgs, const uint64_t* msg_off, uint32_t out_len, uint8_t* out, int n, hipStream_t st);
+hipError_t ed448_expand_batch(const uint8_t* seeds, uint32_t* keys, uint8_t* out_a, int out_stride, int n, hipStream_t st);
+size_t ed448_sign_ws_words(int n, int nkeys_to_expand, int prehash);
+hipError_t ed448_sign_batch(const void* keys, int expanded, int one_key, int prehash, const uint8_t* dom_host, uint32_t dom_len,
+                            const uint8_t* msgs, const uint64_t* msg_off, uint8_t* sigs, uint8_t* ok, int n, uint32_t* ws, hipStream_t st);
+size_t ed448_challenge_ws_words(int n, int prehash);
+hipError_t ed448_challenge_batch(const uint8_t* sigs, const uint8_t* pks, int prehash, const uint8_t* dom_host, uint32_t dom_len,
+                                 const uint8_t* msgs, const uint64_t* msg_off, uint32_t* out_k, int n, uint32_t* ws, hipStream_t st);
+// the pieces of keccak.hpp / ed448_sign.hpp on raw words (ncg_ed448_sign_check); words per row of each op: ed448_sign_check_row_words
+// (0 = unknown op); ws: ed448_sign_check_ws_words() words
+void ed448_sign_check_row_words(int op, int* wa, int* wb, int* wo);
+size_t ed448_sign_check_ws_words();
+hipError_t ed448_sign_check(int op, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, uint32_t* ws, hipStream_t st);
+int ed448_sign_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+void ed448_expand_host(const uint8_t* seeds, uint32_t* keys, int n);
+void ed448_sign_host(const void* key, int expanded, int prehash, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg, uint64_t len,
+                     const uint32_t* r_in, uint8_t* sig, uint8_t* ok);
+void shake256_segments_host(const uint8_t* dom, uint32_t dom_len, const uint8_t* a, uint32_t a_len, const uint8_t* b, uint32_t b_len,
+                            const uint8_t* msg, uint64_t len, uint8_t* out, uint32_t out_len);
+
 // decaf448 (decaf448.hip): every row is made of 56-byte values read as 14 LE words: encodings and scalars 14 words, Edwards
 // representatives (Ed448 affine points x || y) and uniform input 28.  A refused encoding gives out_ok = 0 and a zero row.
 // enc = NULL (decaf448_mul_batch): the decaf base point, out_ok is not written.  one_scalar: one row of `k` for every item.

@@ -29,6 +29,7 @@
 #include "decaf448.hip"
 #include "ed25519_sign.hip"
 #include "secp256k1_sign.hip"
+#include "ed448_sign.hip"
 
 using namespace ncg;
 
@@ -455,6 +456,49 @@ int ht_ed448_verify(const uint8_t* sig, const uint8_t* pk, const uint32_t* k, ui
 }
 int ht_fe448_op(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return fe448_check_host(op, variant, a, b, out); }
 void ht_fe448_widths(int op, int* wa, int* wb, int* wo) { fe448_check_row_words(op, wa, wb, wo); }
+
+// SHAKE256 and Ed448 signing on the CPU twins of ed448_sign.hip.  Seeds 57 bytes, expanded keys 172 (4-byte aligned: scalar || prefix
+// || A || 2 zero bytes), scalars 14 LE words, signatures 114 bytes.  flags as ncg_ed448_sign_batch (ONE_KEY has no meaning for one row
+// and is refused); -1 for unknown flag bits or dom_len above the maximum.  ht_ed448_sign_op: one row of ops 0-2 of
+// ncg_ed448_sign_check, -1 for any other op; ht_ed448_sign_widths: the words per row of ops 0-3.
+// SHAKE256(dom || a || b || msg, out_len); a / b may be NULL (segment left out)
+int ht_shake256(const uint8_t* dom, uint32_t dom_len, const uint8_t* a, uint32_t a_len, const uint8_t* b, uint32_t b_len, const uint8_t* msg,
+                uint64_t len, uint8_t* out, uint32_t out_len) {
+  shake256_segments_host(dom, dom_len, a, a_len, b, b_len, msg, len, out, out_len);
+  return 0;
+}
+int ht_ed448_sign_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) { return ed448_sign_check_host(op, a, b, out); }
+void ht_ed448_sign_widths(int op, int* wa, int* wb, int* wo) { ed448_sign_check_row_words(op, wa, wb, wo); }
+int ht_ed448_mod_n(const uint32_t* x29, uint32_t* out14, int n) {
+  for (int i = 0; i < n; i++)
+    if (ed448_sign_check_host(1, x29 + (size_t)i * 29, nullptr, out14 + (size_t)i * 14)) return -1;
+  return 0;
+}
+int ht_ed448_muladd(const uint32_t* r, const uint32_t* k, const uint32_t* s, uint32_t* out14, int n) {
+  for (int i = 0; i < n; i++) {
+    uint32_t a[28];
+    for (int j = 0; j < 14; j++) {
+      a[j] = r[(size_t)i * 14 + j];
+      a[14 + j] = k[(size_t)i * 14 + j];
+    }
+    if (ed448_sign_check_host(2, a, s + (size_t)i * 14, out14 + (size_t)i * 14)) return -1;
+  }
+  return 0;
+}
+int ht_ed448_expand(const uint8_t* seeds, uint32_t* out_key172, int n) {
+  ed448_expand_host(seeds, out_key172, n);
+  return 0;
+}
+int ht_ed448_sign_with_r(const void* key, int flags, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg, uint64_t len, const uint32_t* r,
+                         uint8_t* out_sig114, uint8_t* out_ok) {
+  if ((flags & ~(NCG_ED448_SIGN_EXPANDED | NCG_ED448_PREHASH)) || dom_len > NCG_ED448_DOM_MAX) return -1;
+  ed448_sign_host(key, flags & NCG_ED448_SIGN_EXPANDED, flags & NCG_ED448_PREHASH, dom, dom_len, msg, len, r, out_sig114, out_ok);
+  return 0;
+}
+int ht_ed448_sign(const void* key, int flags, const uint8_t* dom, uint32_t dom_len, const uint8_t* msg, uint64_t len, uint8_t* out_sig114,
+                  uint8_t* out_ok) {
+  return ht_ed448_sign_with_r(key, flags, dom, dom_len, msg, len, nullptr, out_sig114, out_ok);
+}
 
 // decaf448 on the CPU twins of decaf448.hip: encodings and scalars 14 LE words per row, Edwards representatives and uniform bytes
 // 28; flags as ncg_decaf448_mul_batch, enc = NULL: the decaf base.  ht_decaf448_encode_proj: X Y Z as wire words (42 per row).

@@ -6,10 +6,14 @@ u coordinate (the peer's key) is checked before the scalar (montgomery.ts:324-32
 low-order test and the 448-step ladder run in HIP kernels.  `_batch` forms return (list of bytes-or-None, list of bool), None
 where the reference throws 'invalid private or public key received'; `scalars` may be ONE bytes value against many peers.
 
-`ed448` / `ed448ph`: verify / verify_batch (`ncg_ed448_verify_batch`), getPublicKey[_batch], utils.toMontgomery[_batch] and
-utils.toMontgomerySecret.  HASHING STAYS ON THE HOST: the challenge k = SHAKE256(dom4(phflag, context) || R || A || PH(M), 114)
-mod n, the prehash of ed448ph and the SHAKE256 of getPublicKey are hashlib.shake_256 here; the decoding of A and R, the
-small-order test, s < n and the cofactored equation run on the device.  `zip215=True` is not supported.
+`ed448` / `ed448ph`: getPublicKey[_batch], getExtendedPublicKey, expand_keys, sign / sign_batch, verify / verify_batch,
+shake256_batch, utils.toMontgomery[_batch] and utils.toMontgomerySecret.  THE HASHES RUN ON THE DEVICE (Keccak-f[1600], one message
+per lane): the key expansion SHAKE256(secretKey, 114), the prehash of ed448ph, the nonce r = SHAKE256(dom4 || prefix || PH(M), 114)
+mod n and the challenge k = SHAKE256(dom4 || R || A || PH(M), 114) mod n (`ncg_ed448_public_key_batch`, `ncg_ed448_expand_key_batch`,
+`ncg_ed448_sign_batch`, `ncg_ed448_verify_batch_msgs`, `ncg_shake256_batch`).  verify_batch hashes the challenge with hashlib on the
+host by default, as it always has, and on the device with `device_hash=True`; the decoding of A and R, the small-order test, s < n
+and the cofactored equation run on the device either way.  The signing multiplications double, always add and select, so no branch or
+address follows a key or a nonce; no constant-time claim is made.  `zip215=True` is not supported.
 
 `ed448_Point`: fromBytes_batch / toBytes_batch / multiplyUnsafe_batch / multiplyBase_batch / add_batch on encodings, with the
 range errors of multiply / multiplyUnsafe raised here.
@@ -17,14 +21,14 @@ range errors of multiply / multiplyUnsafe raised here.
 decaf448 and its hasher, the prime-order group of this curve, live in `noble_curves_amd.decaf448`.
 
 Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), `ed448_hasher` (hash-to-curve), FROST
-and OPRF suites, signing, an MSM over Ed448, and a fixed-base table (multiplyBase runs the variable-base kernel on the base
+and OPRF suites, an MSM over Ed448, and a fixed-base table (multiplyBase runs the variable-base kernel on the base
 point).
 """
 import hashlib
 
 import numpy as np
 
-from ._native import get_engine
+from ._native import ED448_KEY_BYTES, get_engine
 
 P = 2**448 - 2**224 - 1
 N = 2**446 - 13818066809895115352007386748515426880336692474882178609894547503885
@@ -175,8 +179,10 @@ class _EdDSA:
         return int.from_bytes(hashlib.shake_256(_dom4(bytes(r_bytes) + bytes(pk_bytes) + bytes(msg), context, self.prehash)).digest(114),
                               "little") % N
 
-    def verify_batch(self, sigs, msgs, publicKeys, context=b"", zip215=False, engine=None):
-        """list of bool, one per (signature, message, publicKey) triple, all under one context"""
+    def verify_batch(self, sigs, msgs, publicKeys, context=b"", zip215=False, engine=None, device_hash=False):
+        """list of bool, one per (signature, message, publicKey) triple, all under one context.  device_hash=True hashes the
+        challenges (and the prehash of ed448ph) on the device (`ncg_ed448_verify_batch_msgs`) instead of with hashlib here; the rows
+        under a context longer than 255 bytes keep their host handling either way."""
         n = len(sigs)
         if len(msgs) != n or len(publicKeys) != n:
             raise ValueError("arrays of signatures, messages and public keys must have equal length")
@@ -187,11 +193,13 @@ class _EdDSA:
         context = _abytes(context, None, "context")
         long_context = len(context) > 255
         S, A, K = np.zeros((n, 114), np.uint8), np.zeros((n, 57), np.uint8), np.zeros((n, 56), np.uint8)
+        raw = []
         for i in range(n):
             sig = _abytes(sigs[i], 114, "signature")
             msg = _abytes(msgs[i], None, "message")
             pk = _abytes(publicKeys[i], 57, "publicKey")
-            if self.prehash:
+            raw.append(msg)
+            if self.prehash and not device_hash:
                 msg = hashlib.shake_256(msg).digest(64)
             S[i], A[i] = np.frombuffer(sig, np.uint8), np.frombuffer(pk, np.uint8)
             if long_context:
@@ -201,26 +209,96 @@ class _EdDSA:
                         and pk.hex() not in ED448_TORSION_SUBGROUP):
                     _dom4(b"", context, self.prehash)
                 continue
-            K[i] = np.frombuffer(self.challenge(sig[:57], pk, msg, context).to_bytes(56, "little"), np.uint8)
+            if not device_hash:
+                K[i] = np.frombuffer(self.challenge(sig[:57], pk, msg, context).to_bytes(56, "little"), np.uint8)
         if long_context:
             return [False] * n
+        if device_hash:
+            off = np.zeros(n + 1, np.uint64)
+            off[1:] = np.cumsum([len(m) for m in raw], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(raw), np.uint8) if off[-1] else np.zeros(0, np.uint8)
+            ok = (engine or get_engine()).ed448_verify_batch_msgs(S, A, blob, off, _dom4(b"", context, self.prehash), prehash=self.prehash)
+            return [bool(x) for x in ok]
         return [bool(x) for x in (engine or get_engine()).ed448_verify_batch(S, A, K)]
 
-    def verify(self, sig, msg, publicKey, context=b"", zip215=False, engine=None):
+    def verify(self, sig, msg, publicKey, context=b"", zip215=False, engine=None, device_hash=False):
         """eddsa.verify (edwards.ts:942): one signature = a batch of one"""
-        return self.verify_batch([sig], [msg], [publicKey], context, zip215, engine)[0]
+        return self.verify_batch([sig], [msg], [publicKey], context, zip215, engine, device_hash)[0]
 
     def getPublicKey_batch(self, secretKeys, engine=None):
-        """getExtendedPublicKey(secretKey).pointBytes (edwards.ts:871-897): SHAKE256 on the host, [scalar]B on the device"""
+        """getExtendedPublicKey(secretKey).pointBytes (edwards.ts:871-897) for every key: SHAKE256, the clamp, the reduction mod n and
+        [scalar]B on the device (`ncg_ed448_public_key_batch`).  An engine that has only the multiply (the CPU twins of the host
+        tests) gets the head hashed here, as before the device had a Keccak: the bytes are the same."""
+        eng = engine or get_engine()
+        if hasattr(eng, "ed448_public_key_batch"):
+            K = _rows(secretKeys, 57, "secretKey")
+            out = eng.ed448_public_key_batch(K)
+            K[:] = 0
+            return [out[i].tobytes() for i in range(len(secretKeys))]
         K = np.zeros((len(secretKeys), 56), np.uint8)
         for i, sk in enumerate(secretKeys):
             head = _adjust(hashlib.shake_256(_abytes(sk, 57, "secretKey")).digest(114)[:57])
             K[i] = np.frombuffer(head[:56], np.uint8)
-        out = (engine or get_engine()).ed448_mul_base_batch(K)
+        out = eng.ed448_mul_base_batch(K)
         return [out[i].tobytes() for i in range(len(secretKeys))]
 
     def getPublicKey(self, secretKey, engine=None):
         return self.getPublicKey_batch([secretKey], engine)[0]
+
+    @staticmethod
+    def expand_keys(secretKeys, engine=None):
+        """172-byte rows scalar (56, below n) || prefix (57) || publicKey (57) || 2 zero bytes (uint8 [n, 172]) for repeated use with
+        sign_batch(..., expanded=True) (`ncg_ed448_expand_key_batch`)"""
+        K = _rows(secretKeys, 57, "secretKey")
+        out = (engine or get_engine()).ed448_expand_key_batch(K)
+        K[:] = 0
+        return out
+
+    def getExtendedPublicKey(self, secretKey, engine=None):
+        """head, prefix, scalar, pointBytes of the reference's getExtendedPublicKey (edwards.ts:871-892); prefix, scalar and pointBytes
+        come from the device, head is the clamped first 57 bytes of SHAKE256(secretKey, 114) (the device keeps it only reduced mod n)"""
+        row = self.expand_keys([secretKey], engine)[0].tobytes()
+        head = _adjust(hashlib.shake_256(bytes(secretKey)).digest(114)[:57])
+        return {"head": head, "prefix": row[56:113], "scalar": int.from_bytes(row[:56], "little"), "pointBytes": row[113:170]}
+
+    def sign_batch(self, msgs, secretKeys, context=b"", engine=None, expanded=False):
+        """sign per message, all under one context (`ncg_ed448_sign_batch`).  secretKeys: ONE key for every message (bytes, or one
+        172-byte row with expanded=True) or a list / array as long as msgs.  Returns a list of 114-byte signatures; None where the
+        device refused the row (r = 0 mod n, where the reference throws)."""
+        ms = [_abytes(m, None, "message") for m in msgs]
+        width = ED448_KEY_BYTES if expanded else 57
+        one = isinstance(secretKeys, (bytes, bytearray, memoryview)) or (isinstance(secretKeys, np.ndarray) and secretKeys.ndim == 1)
+        keys = [secretKeys] if one else secretKeys
+        if not one and len(keys) != len(ms):
+            raise ValueError("arrays of messages and secret keys must have equal length")
+        K = _rows(keys, width, "secretKey")
+        dom = _dom4(b"", _abytes(context, None, "context"), self.prehash)
+        off = np.zeros(len(ms) + 1, np.uint64)
+        off[1:] = np.cumsum([len(m) for m in ms], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(ms), np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        sig, ok = (engine or get_engine()).ed448_sign_batch(K, blob, off, dom, expanded=expanded, one_key=one, prehash=self.prehash)
+        K[:] = 0
+        return [sig[i].tobytes() if ok[i] else None for i in range(len(ms))]
+
+    def sign(self, msg, secretKey, context=b"", engine=None):
+        """eddsa.sign (edwards.ts:909-930): a batch of one; raises where the reference throws"""
+        _abytes(secretKey, 57, "secretKey")
+        out = self.sign_batch([msg], secretKey, context, engine)[0]
+        if out is None:
+            raise ValueError("invalid scalar: expected 1 <= sc < curve.n")
+        return out
+
+    @staticmethod
+    def shake256_batch(msgs, dkLen, engine=None):
+        """shake256(msg, { dkLen }) for every message, on the device (`ncg_shake256_batch`): list of bytes"""
+        ms = [_abytes(m, None, "message") for m in msgs]
+        if not isinstance(dkLen, int) or isinstance(dkLen, bool) or not 1 <= dkLen <= 65535:
+            raise ValueError("dkLen must be an integer in 1..65535")
+        off = np.zeros(len(ms) + 1, np.uint64)
+        off[1:] = np.cumsum([len(m) for m in ms], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(ms), np.uint8) if off[-1] else np.zeros(0, np.uint8)
+        out = (engine or get_engine()).shake256_batch(blob, off, dkLen)
+        return [out[i].tobytes() for i in range(len(ms))]
 
 
 ed448 = _EdDSA(False)
