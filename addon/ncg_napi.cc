@@ -17,6 +17,7 @@
 //   ed448(kind, a | null, b, c)                      -> kind 0 x448.scalarMult (a scalars: n rows or ONE, b u rows), 1 x448.getPublicKey (b):
 //                                                       Uint8Array n * 57 (56-byte results, then ok flags); 2 ed448 verify (a signatures,
 //                                                       b public keys, c challenges) -> Uint8Array n (0 / 1)
+//   oprf(op, mode, flags, a, b, c, d)             -> the ristretto255 OPRF on packed rows (ncg_oprf_*): see Oprf below
 //   ristretto(mode, a, b | null)                   -> ristretto255 on packed rows; mode 0 decode (a: n x 32) -> n x 64 points + n ok flags,
 //                                                       1 encode (a: n x 64) -> n x 32, 2 equals (a, b: n x 64) -> n flags,
 //                                                       3 deriveToCurve (a: n x 64) -> n x 32, 4 multiply (a: n x 32 encodings, b: n or ONE
@@ -509,6 +510,71 @@ static napi_value Ristretto(napi_env env, napi_callback_info info) {
   else if (mode == 3) rc = ncg_ristretto_from_uniform_batch(g_ctx, n, a, out, nullptr);
   else if (mode == 4) rc = ncg_ristretto_mul_batch(g_ctx, n, a, b, bl != al ? NCG_RISTRETTO_ONE_SCALAR : 0, out, out + n * 32);
   else rc = ncg_ristretto_mul_base_batch(g_ctx, n, a, out);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
+// The ristretto255 OPRF on packed rows (ncg_oprf_*, ncg_ristretto_hash_to_scalar_batch): oprf(op, mode, flags, a, b, c, d), an empty
+// Uint8Array standing for "not given".  Messages travel back to back with n lengths as LE uint32; a refused row is zero with its status.
+//   op 0 blind     (a: inputs, b: lens, c: blinds n x 32)                              -> n x 32 blinded, then n statuses
+//   op 1 mul       (a: elements n x 32, b: scalars n x 32 or ONE row; flags: INVERT)   -> n x 32, then n statuses
+//   op 2 finalize  (a: inputs, b: lens, c: blinds n x 32 then evaluated n x 32, d: info) -> n x 64, then n statuses
+//   op 3 evaluate  (a: inputs, b: lens, c: the scalar, d: info; flags: INVERT)         -> n x 64, then n statuses
+//   op 4 proof     (a: k || B || r, b: C n x 32, c: D n x 32)                          -> 64 bytes c || s
+//   op 5 verify    (a: B || proof, b: C, c: D)                                         -> 1 byte
+//   op 6 hashToScalar (a: msgs, b: lens, c: DST)                                       -> n x 32
+static napi_value Oprf(napi_env env, napi_callback_info info) {
+  size_t argc = 7;
+  napi_value argv[7];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t op, mode, flags;
+  uint8_t *a = nullptr, *b = nullptr, *c = nullptr, *d = nullptr, *out;
+  size_t al = 0, bl = 0, cl = 0, dl = 0;
+  if (argc < 7 || napi_get_value_int32(env, argv[0], &op) != napi_ok || op < 0 || op > 6 || napi_get_value_int32(env, argv[1], &mode) != napi_ok ||
+      napi_get_value_int32(env, argv[2], &flags) != napi_ok || !get_u8(env, argv[3], &a, &al) || !get_u8(env, argv[4], &b, &bl) ||
+      !get_u8(env, argv[5], &c, &cl) || !get_u8(env, argv[6], &d, &dl)) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: oprf(op, mode, flags, a, b, c, d)");
+    return nullptr;
+  }
+  const int suite = NCG_OPRF_RISTRETTO255_SHA512;
+  const bool msgs = op == 0 || op == 2 || op == 3 || op == 6;
+  size_t n = msgs ? bl / 4 : (op == 1 ? al / 32 : bl / 32);
+  std::vector<uint64_t> off(n + 1, 0);
+  bool good = true;
+  if (msgs) {
+    good = bl % 4 == 0;
+    for (size_t i = 0; good && i < n; i++) {
+      uint32_t len;
+      memcpy(&len, b + 4 * i, 4);
+      off[i + 1] = off[i] + len;
+    }
+    good = good && off[n] == al;
+  }
+  if (op == 0) good = good && cl == 32 * n;
+  if (op == 1) good = al % 32 == 0 && (bl == al || bl == 32);
+  if (op == 2) good = good && cl == 64 * n;
+  if (op == 3) good = good && cl == 32;
+  if (op == 4) good = al == 96 && bl % 32 == 0 && cl == bl && n > 0;
+  if (op == 5) good = al == 96 && bl % 32 == 0 && cl == bl && n > 0;
+  if (!good) {
+    napi_throw_error(env, nullptr, "noble-gpu: oprf: the rows do not match");
+    return nullptr;
+  }
+  static const size_t per_row[7] = {33, 33, 65, 65, 0, 0, 32};
+  napi_value res = make_u8(env, op == 4 ? 64 : (op == 5 ? 1 : n * per_row[op]), &out);
+  if (!res) return nullptr;
+  const void* inf = mode == 2 ? (dl ? (const void*)d : (const void*)"") : nullptr;
+  int rc = 0;
+  if (n == 0) rc = 0;
+  else if (op == 0) rc = ncg_oprf_blind_batch(g_ctx, suite, mode, n, al ? a : nullptr, off.data(), c, out, out + n * 32);
+  else if (op == 1) rc = ncg_oprf_mul_batch(g_ctx, suite, n, a, b, flags | (bl != al ? NCG_OPRF_ONE_SCALAR : 0), out, out + n * 32);
+  else if (op == 2) rc = ncg_oprf_finalize_batch(g_ctx, suite, mode, n, al ? a : nullptr, off.data(), inf, mode == 2 ? dl : 0, c, c + 32 * n, out, out + n * 64);
+  else if (op == 3)
+    rc = ncg_oprf_evaluate_batch(g_ctx, suite, mode, n, al ? a : nullptr, off.data(), inf, mode == 2 ? dl : 0, c, flags | NCG_OPRF_ONE_SCALAR, out, out + n * 64);
+  else if (op == 4) rc = ncg_oprf_generate_proof(g_ctx, suite, mode, n, a, a + 32, b, c, a + 64, out);
+  else if (op == 5) rc = ncg_oprf_verify_proof(g_ctx, suite, mode, n, a, b, c, a + 32, out);
+  else rc = ncg_ristretto_hash_to_scalar_batch(g_ctx, n, al ? a : nullptr, off.data(), c, cl, out);
   if (rc != 0) return throw_native(env);
   return res;
 }
@@ -1232,7 +1298,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"oprf", Oprf}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -20,6 +20,8 @@
 //                                            host, or on the device with deviceHash: true
 //   ed448GetPublicKeyBatch(secretKeys), ed448SignBatch(items | {msgs, secretKey}, { context, prehash }) - eddsa.getPublicKey / sign
 //                                            for ed448 and ed448ph, every hash on the device; ed448GetPublicKey / ed448Sign: single items
+//   ristretto255_oprf                      - RFC 9497 OPRF / VOPRF / POPRF over ristretto255-SHA512 in the reference's shape, with
+//                                            blindBatch / blindEvaluateBatch / finalizeBatch / evaluateBatch beside the single forms
 //   ristrettoFromBytesBatch(encodings) ...  - array forms of ristretto255.Point.fromBytes / toBytes / equals / multiply /
 //                                            BASE.multiply, an MSM from encodings and ristretto255_hasher.deriveToCurve
 //                                            (src/ed25519.ts:443-668), with single-item forms that throw the reference's messages
@@ -1032,6 +1034,223 @@ function ristrettoMultiply(encoding, k) {
 function ristrettoMultiplyBase(k) { return ristrettoMultiplyBaseBatch([k])[0]; }
 function ristrettoDeriveToCurve(bytes64) { return ristrettoDeriveToCurveBatch([bytes64])[0]; }
 
+// ---- RFC 9497 OPRF over ristretto255-SHA512 (src/abstract/oprf.ts, ristretto255_oprf of src/ed25519.ts:682): an object of the reference's
+// shape with batch forms beside it.  The hashes to the group and to scalars, the blinding, evaluation and unblinding multiplies (secret
+// scalars: no table lookup by digit), the Finalize hash, the composite scalars and the DLEQ proof run on the device (native.oprf);
+// POPRF's m, t = skS + m and the argument checks with the reference's messages are here.  rng: (n) => Uint8Array of n bytes.
+const OPRF_NAME = 'ristretto255-SHA512';
+const OPRF_BASE = Uint8Array.from(Buffer.from('e2f2ae0a6abc4e71a884a961c500515f58e30b6aa582dd8db6a65945e08d2d76', 'hex'));
+const OPRF_NONE = new Uint8Array(0);
+function oprfInput(title, b) {
+  abytesT(b, undefined, title);
+  if (b.length > 0xffff) throw new Error(`"${title}" expected Uint8Array of length <= 65535, got length=${b.length}`);
+  return b;
+}
+function oprfCtx(mode) { return Buffer.concat([Buffer.from('OPRFV1-', 'ascii'), Buffer.from([mode]), Buffer.from('-' + OPRF_NAME, 'ascii')]); }
+function oprfScalar(b) {                          // Fn.fromBytes
+  abytesN(b, 32);
+  const k = leNumber(b, 0, 32);
+  if (k >= ED_L) throw new Error('invalid field element: outside of range 0..ORDER');
+  return k;
+}
+function oprfLe(k) { const out = new Uint8Array(32); leBytes(k, 32, out, 0); return out; }
+function oprfRandomScalar(rng) {
+  if (typeof rng !== 'function') throw new TypeError('"rng" expected function, got type=' + typeof rng);
+  const b = rng(48);
+  return leNumber(b, 0, 48) % (ED_L - 1n) + 1n;
+}
+function oprfBlob(msgs) {
+  const n = msgs.length, lens = new Uint8Array(4 * n), view = new DataView(lens.buffer);
+  let total = 0;
+  msgs.forEach((m, i) => { view.setUint32(4 * i, m.length, true); total += m.length; });
+  const blob = new Uint8Array(total);
+  for (let i = 0, at = 0; i < n; at += msgs[i++].length) blob.set(msgs[i], at);
+  return { blob, lens };
+}
+function oprfEncError(b) { return ristrettoCanonicalEven(b) ? RISTRETTO_ENC2 : RISTRETTO_ENC1; }
+function oprfRows(out, n, width, label, rows, invert) {   // the rows of a native answer, or the reference's message for the first refused one
+  for (let i = 0; i < n; i++) {
+    const st = out[width * n + i];
+    if (st === 3) throw new Error(invert ? 'invert: expected non-zero number' : 'invalid scalar: expected 1 <= sc < curve.n');
+    if (st === 2) throw new Error(label + ' point at infinity');
+    if (st === 1) throw new Error(oprfEncError(rows[i]));
+  }
+  return Array.from({ length: n }, (_, i) => out.slice(width * i, width * i + width));
+}
+function oprfWirePoints(label, rows) {
+  rows.forEach((r) => { abytesN(r, 32); if (r.every((x) => x === 0)) throw new Error(label + ' point at infinity'); });
+  if (rows.length) ristrettoFromBytesBatch(rows).forEach((p, i) => { if (p === null) throw new Error(oprfEncError(rows[i])); });
+  return rows;
+}
+function oprfArray(a) { if (!Array.isArray(a)) throw new Error('expected array'); return a; }
+function oprfRng(n) { return new Uint8Array(crypto.randomBytes(n)); }
+function oprfHashToScalar(msg, dst) {
+  init();
+  const { blob, lens } = oprfBlob([msg]);
+  return native.oprf(6, 0, 0, blob, lens, dst, OPRF_NONE);
+}
+function oprfMode(mode, info) {
+  const m = mode === 2 ? leNumber(oprfHashToScalar(Buffer.concat([Buffer.from('Info', 'ascii'), Buffer.from([info.length >> 8, info.length & 255]), info]),
+    Buffer.concat([Buffer.from('HashToScalar-', 'ascii'), oprfCtx(2)])), 0, 32) : 0n;
+  const inf = mode === 2 ? info : OPRF_NONE;
+  const mulOne = (label, elements, k, invert) => {
+    elements.forEach((e) => abytesN(e, 32));
+    const n = elements.length;
+    if (n === 0) return [];
+    init();
+    const K = oprfLe(k), out = native.oprf(1, mode, invert ? 2 : 0, ristrettoPack(elements, 32), K, OPRF_NONE, OPRF_NONE);
+    K.fill(0);
+    return oprfRows(out, n, 32, label, elements, invert);
+  };
+  const blindBatch = (inputs, rng = oprfRng) => {
+    inputs.forEach((i) => oprfInput('input', i));
+    const blinds = inputs.map(() => oprfLe(oprfRandomScalar(rng))), n = inputs.length;
+    if (n === 0) return { blind: [], blinded: [] };
+    init();
+    const { blob, lens } = oprfBlob(inputs);
+    const out = native.oprf(0, mode, 0, blob, lens, ristrettoPack(blinds, 32), OPRF_NONE);
+    for (let i = 0; i < n; i++) if (out[32 * n + i] !== 0) throw new Error('Input point at infinity');
+    return { blind: blinds, blinded: Array.from({ length: n }, (_, i) => out.slice(32 * i, 32 * i + 32)) };
+  };
+  const unblind = (inputs, blinds, evaluated) => {
+    const n = inputs.length;
+    blinds.forEach(oprfScalar);
+    evaluated.forEach((e) => abytesN(e, 32));
+    if (n === 0) return [];
+    init();
+    const { blob, lens } = oprfBlob(inputs), C = new Uint8Array(64 * n);
+    C.set(ristrettoPack(blinds, 32), 0);
+    C.set(ristrettoPack(evaluated, 32), 32 * n);
+    const out = native.oprf(2, mode, 0, blob, lens, C, inf);
+    C.fill(0);
+    return oprfRows(out, n, 64, 'evaluated', evaluated, true);
+  };
+  const evaluateBatch = (k, invert, inputs) => {
+    inputs.forEach((i) => oprfInput('input', i));
+    const n = inputs.length;
+    if (n === 0) return [];
+    init();
+    const { blob, lens } = oprfBlob(inputs), K = oprfLe(k);
+    const out = native.oprf(3, mode, invert ? 2 : 0, blob, lens, K, inf);
+    K.fill(0);
+    return oprfRows(out, n, 64, 'Input', inputs, invert);
+  };
+  const proof = (k, B, C, D, rng) => {
+    const A = new Uint8Array(96);
+    A.set(oprfLe(k), 0); A.set(B, 32); A.set(oprfLe(oprfRandomScalar(rng)), 64);
+    init();
+    const out = native.oprf(4, mode, 0, A, ristrettoPack(C, 32), ristrettoPack(D, 32), OPRF_NONE);
+    A.fill(0);
+    return out;
+  };
+  const verify = (B, C, D, prf) => {
+    abytesN(prf, 64);
+    oprfScalar(prf.subarray(0, 32)); oprfScalar(prf.subarray(32));
+    const A = new Uint8Array(96);
+    A.set(B, 0); A.set(prf, 32);
+    init();
+    if (native.oprf(5, mode, 0, A, ristrettoPack(C, 32), ristrettoPack(D, 32), OPRF_NONE)[0] !== 1) throw new Error('proof verification failed');
+  };
+  const common = {
+    generateKeyPair() {
+      const sk = oprfRandomScalar(oprfRng);
+      return { secretKey: oprfLe(sk), publicKey: mulOne('base', [OPRF_BASE], sk, false)[0] };
+    },
+    deriveKeyPair(seed, keyInfo) {
+      abytesT(seed, 32, 'seed');
+      oprfInput('keyInfo', keyInfo);
+      const dst = Buffer.concat([Buffer.from('DeriveKeyPair', 'ascii'), oprfCtx(mode)]);
+      for (let counter = 0; counter <= 255; counter++) {
+        const sk = oprfHashToScalar(Buffer.concat([seed, Buffer.from([keyInfo.length >> 8, keyInfo.length & 255]), keyInfo, Buffer.from([counter])]), dst);
+        if (sk.every((x) => x === 0)) continue;
+        return { secretKey: sk, publicKey: mulOne('base', [OPRF_BASE], leNumber(sk, 0, 32), false)[0] };
+      }
+      throw new Error('Cannot derive key');
+    },
+  };
+  if (mode !== 2) {
+    const S = Object.assign(common, {
+      blind(input, rng = oprfRng) { const r = blindBatch([input], rng); return { blind: r.blind[0], blinded: r.blinded[0] }; },
+      blindBatch,
+      evaluate(secretKey, input) { return evaluateBatch(oprfScalar(secretKey), false, [input])[0]; },
+      evaluateBatch(secretKey, inputs) { return evaluateBatch(oprfScalar(secretKey), false, inputs); },
+    });
+    if (mode === 0) return Object.freeze(Object.assign(S, {
+      blindEvaluate(secretKey, blinded) { return mulOne('blinded', [blinded], oprfScalar(secretKey), false)[0]; },
+      blindEvaluateBatch(secretKey, blinded) { return mulOne('blinded', oprfArray(blinded), oprfScalar(secretKey), false); },
+      finalize(input, blind, evaluated) { return unblind([oprfInput('input', input)], [blind], [evaluated])[0]; },
+      finalizeBatch(inputs, blinds, evaluated) { return unblind(inputs.map((i) => oprfInput('input', i)), blinds, evaluated); },
+    }));
+    return Object.freeze(Object.assign(S, {
+      blindEvaluateBatch(secretKey, publicKey, blinded, rng = oprfRng) {
+        oprfArray(blinded);
+        const sk = oprfScalar(secretKey), pk = oprfWirePoints('public key', [publicKey])[0];
+        const evaluated = mulOne('blinded', blinded, sk, false);
+        return { evaluated, proof: proof(sk, pk, blinded, evaluated, rng) };
+      },
+      blindEvaluate(secretKey, publicKey, blinded, rng = oprfRng) {
+        const res = this.blindEvaluateBatch(secretKey, publicKey, [blinded], rng);
+        return { evaluated: res.evaluated[0], proof: res.proof };
+      },
+      finalizeBatch(items, publicKey, prf) {
+        oprfArray(items);
+        const pk = oprfWirePoints('public key', [publicKey])[0];
+        const blinded = oprfWirePoints('blinded', items.map((i) => i.blinded)), evaluated = oprfWirePoints('evaluated', items.map((i) => i.evaluated));
+        verify(pk, blinded, evaluated, prf);
+        return unblind(items.map((i) => oprfInput('input', i.input)), items.map((i) => i.blind), evaluated);
+      },
+      finalize(input, blind, evaluated, blinded, publicKey, prf) { return this.finalizeBatch([{ input, blind, evaluated, blinded }], publicKey, prf)[0]; },
+    }));
+  }
+  const tOf = (secretKey) => {
+    const t = (oprfScalar(secretKey) + m) % ED_L;
+    if (t === 0n) throw new Error('invert: expected non-zero number');
+    return t;
+  };
+  return Object.freeze(Object.assign(common, {
+    blindBatch(inputs, publicKey, rng = oprfRng) {
+      inputs.forEach((i) => oprfInput('input', i));
+      const pk = oprfWirePoints('public key', [publicKey])[0];
+      // T + pkS, T = m G with the PUBLIC m: the MSM of the ristretto255 exports
+      const tweakedKey = ristrettoMsm([OPRF_BASE, pk], [m, 1n]);
+      if (tweakedKey.every((x) => x === 0)) throw new Error('tweakedKey point at infinity');
+      return Object.assign(blindBatch(inputs, rng), { tweakedKey });
+    },
+    blind(input, publicKey, rng = oprfRng) {
+      const r = this.blindBatch([input], publicKey, rng);
+      return { blind: r.blind[0], blinded: r.blinded[0], tweakedKey: r.tweakedKey };
+    },
+    blindEvaluateBatch(secretKey, blinded, rng = oprfRng) {
+      oprfArray(blinded);
+      const t = tOf(secretKey);
+      const evaluated = mulOne('blinded', blinded, t, true);
+      const tweakedKey = mulOne('base', [OPRF_BASE], t, false)[0];
+      return { evaluated, proof: proof(t, tweakedKey, evaluated, blinded, rng) };
+    },
+    blindEvaluate(secretKey, blinded, rng = oprfRng) {
+      const res = this.blindEvaluateBatch(secretKey, [blinded], rng);
+      return { evaluated: res.evaluated[0], proof: res.proof };
+    },
+    finalizeBatch(items, prf, tweakedKey) {
+      oprfArray(items);
+      const inputs = items.map((i) => oprfInput('input', i.input));
+      const evaluated = oprfWirePoints('evaluated', items.map((i) => i.evaluated));
+      const tw = oprfWirePoints('tweakedKey', [tweakedKey])[0];
+      verify(tw, evaluated, oprfWirePoints('blinded', items.map((i) => i.blinded)), prf);
+      return unblind(inputs, items.map((i) => i.blind), evaluated);
+    },
+    finalize(input, blind, evaluated, blinded, prf, tweakedKey) { return this.finalizeBatch([{ input, blind, evaluated, blinded }], prf, tweakedKey)[0]; },
+    evaluate(secretKey, input) { return evaluateBatch(tOf(secretKey), true, [input])[0]; },
+    evaluateBatch(secretKey, inputs) { return evaluateBatch(tOf(secretKey), true, inputs); },
+  }));
+}
+const ristretto255_oprf = Object.freeze({
+  name: OPRF_NAME,
+  get oprf() { return oprfMode(0); },
+  get voprf() { return oprfMode(1); },
+  poprf(info) { return oprfMode(2, Uint8Array.from(oprfInput('info', info))); },
+});
+
 // ---- decaf448 (src/ed448.ts:462-701, RFC 9496 section 5), with the argument conventions of the ristretto255 exports.  An element is
 // its 56-byte encoding on this side; fromBytes hands back the Edwards representative as a 112-byte Ed448 affine point (x || y).
 // Batch forms return null where the reference throws.
@@ -1375,6 +1594,6 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    ed448GetPublicKeyBatch, ed448SignBatch, ed448GetPublicKey, ed448Sign,
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
-                   ristrettoDeriveToCurve,
+                   ristrettoDeriveToCurve, ristretto255_oprf,
                    decaf448FromBytesBatch, decaf448ToBytesBatch, decaf448EqualsBatch, decaf448MultiplyBatch, decaf448MultiplyBaseBatch,
                    decaf448DeriveToCurveBatch, native };

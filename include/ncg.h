@@ -561,6 +561,96 @@ int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scala
 int ncg_ristretto_msm_dev(ncg_ctx* ctx, size_t n, const void* enc_dev, const void* scalars_dev, void* out32,
                           int64_t* out_bad_index, void* stream);
 
+/* ---- OPRF over ristretto255 (RFC 9497): OPRF, VOPRF and POPRF -------------------------------------------------
+ * ristretto255_oprf of src/ed25519.ts:682, built by createOPRF (src/abstract/oprf.ts).  suite: NCG_OPRF_RISTRETTO255_SHA512, any
+ * other id returns NCG_ERR_UNSUPPORTED; mode: 0 OPRF, 1 VOPRF, 2 POPRF.  Elements and scalars are rows of 32 bytes read as 8 LE
+ * words (a DEVICE pointer to them must be 4-byte aligned); messages are one blob with n + 1 ascending offsets, as in
+ * ncg_ed25519_sign_batch; dst, info, and in the proof calls k32, r32, B32, proof64 and the outputs are HOST pointers in both forms.
+ * n = 0 returns NCG_OK and touches nothing.
+ *
+ * Every scalar argument is a secret: the multiply doubles, always adds and keeps by mask, the inversion is the Fermat chain for
+ * L - 2, and no table is indexed by a digit.  The workspace and the staged copy of the scalars of a host form are cleared on the
+ * call's stream before the call returns.  The key and the nonce of ncg_oprf_generate_proof reach the device as a kernel argument:
+ * the library's copy of it is wiped, the HIP runtime's own argument buffer is beyond its reach and keeps them until it is reused.
+ * This is not a constant-time claim.  n above 2^31 - 256 is refused ("batch too large").
+ *
+ * out_status[i]: 0 ok; 1 the element does not decode; 2 the element is the identity (exactly 32 zero bytes); 3 the scalar is zero
+ * or not below L.  The element is looked at before the scalar.  A rejected row writes zero bytes and never stops the call.
+ *
+ * ncg_xmd_sha512_batch: out[i] = expand_message_xmd(msg i, dst, out_len) over SHA-512 (RFC 9380 section 5.3.1), out_len bytes per
+ *   row, 1 <= out_len <= 256, 1 <= dst_len <= 255 (an oversize DST is hashed by the caller).
+ * ncg_ristretto_hash_to_group_batch: out32[i] = ristretto255_hasher.hashToCurve(msg i, {DST: dst}).toBytes(); out_affine (may
+ *   be NULL): the Edwards representative, 64 bytes.
+ * ncg_ristretto_hash_to_scalar_batch: out32[i] = ristretto255_hasher.hashToScalar(msg i, {DST: dst}).
+ * ncg_oprf_blind_batch: out_blinded32[i] = hashToGroup(input i) * blind i (oprf.ts:595-606).  Inputs are at most 65535 bytes
+ *   (checked in the host form; the caller's promise in the _dev form).
+ * ncg_oprf_mul_batch: out32[i] = element i * scalar i, or * 1 / scalar i with NCG_OPRF_INVERT; NCG_OPRF_ONE_SCALAR: scalars32 is
+ *   one row used for every element (with INVERT it is inverted once).  blindEvaluate, and the unblinding of finalize.
+ * ncg_oprf_finalize_batch: out64[i] = Hash(len || input i || [len || info] || 0x0020 || evaluated i / blind i || "Finalize").
+ * ncg_oprf_evaluate_batch: out64[i] = the same hash of hashToGroup(input i) * scalar [1 / scalar with NCG_OPRF_INVERT] (oprf.ts:607-618;
+ *   POPRF passes t = skS + m and NCG_OPRF_INVERT).  flags as ncg_oprf_mul_batch.
+ *   info is read only in mode 2 and must be NULL with info_len 0 otherwise (at most 65535 bytes).
+ * ncg_oprf_composite_scalars_batch: out32[i] = the d_i of getTranscripts (oprf.ts:502-513) for the public key B32 (host); C_i and
+ *   D_i are hashed as given, a row where either is refused reports C's status first.  n <= 65535.
+ * ncg_oprf_generate_proof: out_proof64 = c || s of generateProof(k, B, C, D) with the nonce r (oprf.ts:542-550): M by
+ *   ncg_ristretto_msm, Z = k M, t3 = r M and t2 = r G by the secret multiplies.  ncg_oprf_verify_proof: *out_ok = 1 iff
+ *   verifyProof accepts (oprf.ts:552-562); a c or s not below L gives 0.  Both fail with NCG_ERR_INVALID_ARG on the first
+ *   refused row of C or D, on a refused B, and (generate) on k or r zero or not below L; n <= 65535; they synchronise. */
+enum { NCG_OPRF_RISTRETTO255_SHA512 = 0 };
+enum { NCG_OPRF_ONE_SCALAR = 1, NCG_OPRF_INVERT = 2 };
+int ncg_xmd_sha512_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                         size_t out_len, void* out);
+int ncg_xmd_sha512_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                             size_t dst_len, size_t out_len, void* out_dev, void* stream);
+int ncg_ristretto_hash_to_group_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                      size_t dst_len, void* out32, void* out_affine);
+int ncg_ristretto_hash_to_group_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                          size_t dst_len, void* out32_dev, void* out_affine_dev, void* stream);
+int ncg_ristretto_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                       size_t dst_len, void* out32);
+int ncg_ristretto_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                           size_t dst_len, void* out32_dev, void* stream);
+int ncg_oprf_blind_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* blinds32,
+                         void* out_blinded32, uint8_t* out_status);
+int ncg_oprf_blind_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev,
+                             const void* blinds32_dev, void* out_blinded32_dev, uint8_t* out_status_dev, void* stream);
+int ncg_oprf_mul_batch(ncg_ctx* ctx, int suite, size_t n, const void* elements32, const void* scalars32, int flags, void* out32,
+                       uint8_t* out_status);
+int ncg_oprf_mul_batch_dev(ncg_ctx* ctx, int suite, size_t n, const void* elements32_dev, const void* scalars32_dev, int flags,
+                           void* out32_dev, uint8_t* out_status_dev, void* stream);
+int ncg_oprf_finalize_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* info,
+                            size_t info_len, const void* blinds32, const void* evaluated32, void* out64, uint8_t* out_status);
+int ncg_oprf_finalize_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev,
+                                const void* info, size_t info_len, const void* blinds32_dev, const void* evaluated32_dev,
+                                void* out64_dev, uint8_t* out_status_dev, void* stream);
+int ncg_oprf_evaluate_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* info,
+                            size_t info_len, const void* scalar32, int flags, void* out64, uint8_t* out_status);
+int ncg_oprf_evaluate_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev,
+                                const void* info, size_t info_len, const void* scalar32_dev, int flags, void* out64_dev,
+                                uint8_t* out_status_dev, void* stream);
+int ncg_oprf_composite_scalars_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32, const void* D32,
+                                     void* out32, uint8_t* out_status);
+int ncg_oprf_composite_scalars_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32_dev,
+                                         const void* D32_dev, void* out32_dev, uint8_t* out_status_dev, void* stream);
+int ncg_oprf_generate_proof(ncg_ctx* ctx, int suite, int mode, size_t n, const void* k32, const void* B32, const void* C32,
+                            const void* D32, const void* r32, void* out_proof64);
+int ncg_oprf_generate_proof_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* k32, const void* B32, const void* C32_dev,
+                                const void* D32_dev, const void* r32, void* out_proof64, void* stream);
+int ncg_oprf_verify_proof(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32, const void* D32,
+                          const void* proof64, uint8_t* out_ok);
+int ncg_oprf_verify_proof_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32_dev, const void* D32_dev,
+                              const void* proof64, uint8_t* out_ok, void* stream);
+/* The lane code of csrc/oprf.hpp on n rows of RAW uint32 words, bit for bit with its CPU twin.  Words per row (a, b, out), per op:
+ *   0  a b mod L                  (8, 8, 8)    a, b below L
+ *   1  1 / a mod L                (8, 8, 8)    0 < a < L; b not read
+ *   2  [b] a, secret multiply     (16, 8, 8)   a = an ed25519 wire point (x, y), b below 2^253; out = the ristretto255 encoding
+ *   3  one xmd                    (8, 8, 16)   a = 32 message bytes, b = DST' = DST || len(DST) in its first `variant` bytes
+ *                                              (2 <= variant <= 32); out = 64 bytes
+ *   4  a + b mod L   5  a - b mod L   (8, 8, 8)   a, b below L
+ * b is required (non-NULL) even where it is not read.  An op nobody defines, or op 3 with a variant out of range, reads nothing and
+ * leaves out zero (rows of 8 words).  n above 2^24 is refused. */
+int ncg_oprf_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
+
 /* ---- X448 (RFC 7748) and Ed448-Goldilocks (RFC 8032): the reference's src/ed448.ts -------------------------------
  * The curve has no ncg_curve id and no ncg_field_check field: these are dedicated entry points, bytes in and bytes out.
  * Field elements and scalars are 56 bytes little-endian, read as 14 words: a DEVICE pointer to such rows (scalars56, u56, out56,

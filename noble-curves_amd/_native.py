@@ -28,6 +28,8 @@ SECP_PK_BYTES = {SECP_PK_COMPRESSED: 33, SECP_PK_UNCOMPRESSED: 65, SECP_PK_XONLY
 # ncg_secp256k1_sign_check: {op: words per row of (a, b, out)}, the table of include/ncg.h (csrc/secp256k1_sign.hpp)
 SECP_SIGN_CHECK_WORDS = {0: (24, 1, 8), 1: (8, 1, 16), 2: (32, 1, 18), 3: (24, 1, 8), 4: (24, 1, 18)}
 RISTRETTO_ONE_SCALAR = 1   # ncg_ristretto_mul_batch flag: one scalar for every row
+OPRF_RISTRETTO255_SHA512 = 0            # ncg_oprf_* suite
+OPRF_ONE_SCALAR, OPRF_INVERT = 1, 2     # ncg_oprf_mul_batch / ncg_oprf_evaluate_batch flags
 # ncg_fp12_batch ops (enum ncg_fp12_op); a GT element is GT_BYTES on the wire
 (FP12_MUL, FP12_SQR, FP12_INV, FP12_CONJUGATE, FP12_FROBENIUS1, FP12_FROBENIUS2, FP12_FROBENIUS3, FP12_CYCLOTOMIC_SQR, FP12_MUL014,
  FP12_FINAL_EXP, FP12_IS_ONE) = range(11)
@@ -230,6 +232,27 @@ _OPTIONAL_PROTOS = {
     "ncg_ristretto_mul_base_batch_dev": [_vp, _sz, _vp, _vp, _vp],
     "ncg_ristretto_msm": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_ristretto_msm_dev": [_vp, _sz, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
+    "ncg_xmd_sha512_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ncg_xmd_sha512_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ncg_ristretto_hash_to_group_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_ristretto_hash_to_group_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp],
+    "ncg_ristretto_hash_to_scalar_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ncg_ristretto_hash_to_scalar_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_oprf_blind_batch": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_blind_batch_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_mul_batch": [_vp, _i32, _sz, _vp, _vp, _i32, _vp, _vp],
+    "ncg_oprf_mul_batch_dev": [_vp, _i32, _sz, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ncg_oprf_finalize_batch": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp],
+    "ncg_oprf_finalize_batch_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_evaluate_batch": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp],
+    "ncg_oprf_evaluate_batch_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp, _vp],
+    "ncg_oprf_composite_scalars_batch": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_composite_scalars_batch_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_generate_proof": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_generate_proof_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_verify_proof": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_verify_proof_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ncg_oprf_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
     "ncg_pairing_batch": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_pairing_batch_dev": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
     "ncg_bls_verify_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
@@ -1111,6 +1134,138 @@ class Engine:
             err = NativeError((self.lib.ncg_last_error(self.h) or b"").decode() or "noble-gpu: native call failed (%d)" % rc)
             err.bad_index = int(bad.value)
             raise err
+        return out
+
+    # ---- OPRF over ristretto255 (RFC 9497): elements and scalars uint8 [n, 32], outputs [n, 64], messages a blob with offsets; status
+    # uint8 [n]: 0 ok, 1 undecodable, 2 identity, 3 scalar zero or not below L -----------------------------------------------------
+    @staticmethod
+    def _blob(msgs):
+        off = np.zeros(len(msgs) + 1, dtype=np.uint64)
+        if len(msgs):
+            off[1:] = np.cumsum([len(m) for m in msgs])
+        return np.frombuffer(b"".join(bytes(m) for m in msgs), dtype=np.uint8), off
+
+    def xmd_sha512_batch(self, msgs, dst, out_len):
+        """expand_message_xmd over SHA-512 of every message -> uint8 [n, out_len]"""
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_xmd_sha512_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst, len(dst),
+                                                      out_len, out.ctypes.data))
+        return out
+
+    def ristretto_hash_to_group_batch(self, msgs, dst, want_affine=False):
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out, aff = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 64), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ristretto_hash_to_group_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst,
+                                                                   len(dst), out.ctypes.data, aff.ctypes.data if want_affine else None))
+        return out, aff
+
+    def ristretto_hash_to_scalar_batch(self, msgs, dst):
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, 32), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ristretto_hash_to_scalar_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst,
+                                                                    len(dst), out.ctypes.data))
+        return out
+
+    def oprf_blind_batch(self, mode, inputs, blinds, suite=0):
+        blob, off = self._blob(inputs)
+        blinds = np.ascontiguousarray(blinds, dtype=np.uint8).reshape(-1, 32)
+        n = len(inputs)
+        if blinds.shape[0] != n:
+            raise ValueError("arrays of inputs and blinds must have equal length")
+        out, st = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_oprf_blind_batch(self.h, suite, mode, n, blob.ctypes.data if blob.size else None, off.ctypes.data,
+                                                      blinds.ctypes.data, out.ctypes.data, st.ctypes.data))
+        return out, st
+
+    def oprf_mul_batch(self, elements, scalars, one_scalar=False, invert=False, suite=0):
+        elements = np.ascontiguousarray(elements, dtype=np.uint8).reshape(-1, 32)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8).reshape(-1, 32)
+        n = elements.shape[0]
+        if scalars.shape[0] != (1 if one_scalar else n):
+            raise ValueError("arrays of elements and scalars must have equal length")
+        out, st = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_oprf_mul_batch(self.h, suite, n, elements.ctypes.data, scalars.ctypes.data,
+                                                    (OPRF_ONE_SCALAR if one_scalar else 0) | (OPRF_INVERT if invert else 0), out.ctypes.data,
+                                                    st.ctypes.data))
+        return out, st
+
+    def oprf_finalize_batch(self, mode, inputs, blinds, evaluated, info=None, suite=0):
+        blob, off = self._blob(inputs)
+        blinds = np.ascontiguousarray(blinds, dtype=np.uint8).reshape(-1, 32)
+        evaluated = np.ascontiguousarray(evaluated, dtype=np.uint8).reshape(-1, 32)
+        n = len(inputs)
+        if blinds.shape[0] != n or evaluated.shape[0] != n:
+            raise ValueError("arrays of inputs, blinds and elements must have equal length")
+        info = None if info is None else bytes(info)
+        out, st = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_oprf_finalize_batch(self.h, suite, mode, n, blob.ctypes.data if blob.size else None, off.ctypes.data,
+                                                         info if info else None, len(info or b""), blinds.ctypes.data, evaluated.ctypes.data,
+                                                         out.ctypes.data, st.ctypes.data))
+        return out, st
+
+    def oprf_evaluate_batch(self, mode, inputs, scalar, invert=False, info=None, suite=0):
+        """the one scalar against every input"""
+        blob, off = self._blob(inputs)
+        scalar = np.ascontiguousarray(scalar, dtype=np.uint8).reshape(1, 32)
+        info = None if info is None else bytes(info)
+        n = len(inputs)
+        out, st = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_oprf_evaluate_batch(self.h, suite, mode, n, blob.ctypes.data if blob.size else None, off.ctypes.data,
+                                                         info if info else None, len(info or b""), scalar.ctypes.data,
+                                                         OPRF_ONE_SCALAR | (OPRF_INVERT if invert else 0), out.ctypes.data, st.ctypes.data))
+        return out, st
+
+    def oprf_composite_scalars_batch(self, mode, B, C, D, suite=0):
+        C = np.ascontiguousarray(C, dtype=np.uint8).reshape(-1, 32)
+        D = np.ascontiguousarray(D, dtype=np.uint8).reshape(-1, 32)
+        n = C.shape[0]
+        if D.shape[0] != n:
+            raise ValueError("arrays of elements must have equal length")
+        out, st = np.zeros((n, 32), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_oprf_composite_scalars_batch(self.h, suite, mode, n, bytes(B), C.ctypes.data, D.ctypes.data, out.ctypes.data,
+                                                                  st.ctypes.data))
+        return out, st
+
+    def oprf_generate_proof(self, mode, k32, B, C, D, r32, suite=0):
+        C = np.ascontiguousarray(C, dtype=np.uint8).reshape(-1, 32)
+        D = np.ascontiguousarray(D, dtype=np.uint8).reshape(-1, 32)
+        if D.shape[0] != C.shape[0] or not C.shape[0]:
+            raise ValueError("arrays of elements must have equal, non-zero length")
+        out = np.zeros((64,), dtype=np.uint8)
+        self._check(self.lib.ncg_oprf_generate_proof(self.h, suite, mode, C.shape[0], bytes(k32), bytes(B), C.ctypes.data, D.ctypes.data,
+                                                     bytes(r32), out.ctypes.data))
+        return out.tobytes()
+
+    def oprf_verify_proof(self, mode, B, C, D, proof64, suite=0):
+        C = np.ascontiguousarray(C, dtype=np.uint8).reshape(-1, 32)
+        D = np.ascontiguousarray(D, dtype=np.uint8).reshape(-1, 32)
+        if D.shape[0] != C.shape[0] or not C.shape[0]:
+            raise ValueError("arrays of elements must have equal, non-zero length")
+        ok = np.zeros((1,), dtype=np.uint8)
+        self._check(self.lib.ncg_oprf_verify_proof(self.h, suite, mode, C.shape[0], bytes(B), C.ctypes.data, D.ctypes.data, bytes(proof64),
+                                                   ok.ctypes.data))
+        return bool(ok[0])
+
+    def oprf_check(self, op, variant, a, b):
+        """the lane code of csrc/oprf.hpp on raw rows (include/ncg.h has the table): a uint8 [n, 4 wa], b [n, 32] -> out [n, 4 wo]"""
+        wa, wo = (16 if op == 2 else 8), (16 if op == 3 else 8)
+        a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, 4 * wa)
+        b = np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros((a.shape[0], 4 * wo), dtype=np.uint8)
+        if a.shape[0]:
+            self._check(self.lib.ncg_oprf_check(self.h, op, variant, a.shape[0], a.ctypes.data, b.ctypes.data, out.ctypes.data))
         return out
 
     # ---- bls12-381 pairings: G1 / G2 affine wire points [n, 96] / [n, 192], GT elements uint8 [n, 576] ---------------------

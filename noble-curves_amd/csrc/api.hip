@@ -380,6 +380,7 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->ntt_ws) (void)hipFree(ctx->ntt_ws);
   if (ctx->poly_ws) (void)hipFree(ctx->poly_ws);
   if (ctx->rist_ws) (void)hipFree(ctx->rist_ws);
+  if (ctx->oprf_ws) (void)hipFree(ctx->oprf_ws);
   if (ctx->pair_ws) (void)hipFree(ctx->pair_ws);
   if (ctx->bls_ws) (void)hipFree(ctx->bls_ws);
   (void)ncg_comm_destroy(ctx);
@@ -2622,6 +2623,410 @@ int ncg_ristretto_msm(ncg_ctx* ctx, size_t n, const void* enc, const void* scala
   const int in = hc.in(enc, n * 32), sc = hc.in(scalars, n * 32);
   if (int rc = hc.stage()) return rc;
   return hc.finish(ncg_ristretto_msm_dev(ctx, n, hc.dev(in), hc.dev(sc), out32, out_bad_index, ctx->stream));
+}
+
+// ---- OPRF over ristretto255 (oprf.hip).  The strings of a call, the one scalar inverted and the rows of the proof calls live in
+// ctx->oprf_ws, which is cleared on the call's stream before the call returns, and so is the staged copy of the scalars of a host
+// form.  The scalar rows of a _dev form are read as words: 4-byte aligned or refused.
+// the row index of a kernel is an int, and the last block of 256 lanes runs past n: the largest batch leaves room for it
+constexpr size_t OPRF_NO_LIMIT = 0x7fffffffu - 255;
+constexpr size_t OPRF_PROOF_WS = 1024;   // behind the header: the rows of a proof call (M | k r | Z t3 t2, or G B M Z | s c)
+static Rule oprf_rule(ncg_ctx* ctx, const char* op, int suite, int mode, int flags, size_t n_max, size_t n, const void* info, size_t info_len,
+                      std::initializer_list<const void*> word_rows) {
+  int rc = NCG_OK;
+  if (suite != NCG_OPRF_RISTRETTO255_SHA512) rc = set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: %s: unsupported suite %d", op, suite);
+  else if (mode < 0 || mode > 2) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: mode %d is not 0, 1 or 2", op, mode);
+  else if (flags & ~(NCG_OPRF_ONE_SCALAR | NCG_OPRF_INVERT)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: unknown flag bits 0x%x", op, flags);
+  else if (n > n_max && n_max == 65535) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: %zu rows, the row index must fit 16 bits", op, n);
+  else if (n > n_max) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: batch too large", op);
+  else if (mode != 2 && (info || info_len)) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: info is read only in mode 2", op);
+  else if (info_len > 65535) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: info_len %zu above 65535", op, info_len);
+  else if (info_len && !info) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer (info)", op);
+  else
+    for (const void* p : word_rows)
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: element and scalar rows must be 4-byte aligned", op);
+  return {op, rc};
+}
+static Rule xmd_rule(ncg_ctx* ctx, const char* op, size_t n, const void* dst, size_t dst_len, size_t out_len,
+                     std::initializer_list<const void*> word_rows) {
+  int rc = NCG_OK;
+  if (n > OPRF_NO_LIMIT) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: batch too large", op);
+  else if (dst_len < 1 || dst_len > 255) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: dst_len %zu outside 1..255", op, dst_len);
+  else if (!dst) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer (dst)", op);
+  else if (out_len < 1 || out_len > 256) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: out_len %zu outside 1..256", op, out_len);
+  else
+    for (const void* p : word_rows)
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: output rows must be 4-byte aligned", op);
+  return {op, rc};
+}
+static int oprf_ws(ncg_ctx* ctx, size_t info_len, size_t extra, uint8_t** ws, size_t* bytes) {
+  *bytes = ncg::oprf_ws_bytes(info_len) + extra;
+  if (int rc = ncg_grow_buf(ctx, &ctx->oprf_ws, &ctx->oprf_ws_bytes, *bytes, *bytes + 4096, GrowWait::device)) return rc;
+  *ws = (uint8_t*)ctx->oprf_ws;
+  return NCG_OK;
+}
+// the end of a _dev form: the workspace cleared on the call's stream, then the launch status
+static int oprf_done(ncg_ctx* ctx, hipError_t e, size_t ws_bytes, hipStream_t st) {
+  (void)hipMemsetAsync(ctx->oprf_ws, 0, ws_bytes, st);
+  NCG_HIP(ctx, e);
+  return NCG_OK;
+}
+// the inputs of the host forms: at most 65535 bytes each, where the reference's inputBytes throws
+static int oprf_input_lengths(ncg_ctx* ctx, const char* op, size_t n, const uint64_t* off) {
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] >= off[i] && off[i + 1] - off[i] > 65535)
+      return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: input %zu is longer than 65535 bytes", op, i);
+  return NCG_OK;
+}
+
+int ncg_xmd_sha512_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst, size_t dst_len,
+                             size_t out_len, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "xmd_sha512_batch", n, dst, dst_len, out_len, {}), n, msg_off_dev, out_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_xmd_batch((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, (uint32_t)out_len,
+                                            (uint8_t*)out_dev, (int)n, ws, st), wb, st);
+}
+int ncg_xmd_sha512_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len, size_t out_len,
+                         void* out) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "xmd_sha512_batch", n, dst, dst_len, out_len, {}), n, msg_off, out);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "xmd_sha512_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out, n * out_len);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_xmd_sha512_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, out_len, hc.dev(o), ctx->stream));
+}
+int ncg_ristretto_hash_to_group_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                          size_t dst_len, void* out32_dev, void* out_affine_dev, void* stream) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "ristretto_hash_to_group_batch", n, dst, dst_len, 64, {out32_dev, out_affine_dev}), n, msg_off_dev, out32_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_hash_to_group_batch((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len,
+                                                      (uint32_t*)out32_dev, (uint32_t*)out_affine_dev, (int)n, ws, st), wb, st);
+}
+int ncg_ristretto_hash_to_group_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                      void* out32, void* out_affine) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "ristretto_hash_to_group_batch", n, dst, dst_len, 64, {}), n, msg_off, out32);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ristretto_hash_to_group_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out32, n * 32), aff = out_affine ? hc.out(out_affine, n * 64) : -1;
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_hash_to_group_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o),
+                                                         aff < 0 ? nullptr : hc.dev(aff), ctx->stream));
+}
+int ncg_ristretto_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                           size_t dst_len, void* out32_dev, void* stream) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "ristretto_hash_to_scalar_batch", n, dst, dst_len, 64, {out32_dev}), n, msg_off_dev, out32_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_hash_to_scalar_batch((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len,
+                                                       (uint32_t*)out32_dev, (int)n, ws, st), wb, st);
+}
+int ncg_ristretto_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                       void* out32) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "ristretto_hash_to_scalar_batch", n, dst, dst_len, 64, {}), n, msg_off, out32);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ristretto_hash_to_scalar_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ristretto_hash_to_scalar_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o), ctx->stream));
+}
+
+int ncg_oprf_blind_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev,
+                             const void* blinds32_dev, void* out_blinded32_dev, uint8_t* out_status_dev, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_blind_batch", suite, mode, 0, OPRF_NO_LIMIT, n, nullptr, 0, {blinds32_dev, out_blinded32_dev}), n, off_dev,
+            blinds32_dev, out_blinded32_dev, out_status_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_blind_batch(mode, (const uint8_t*)inputs_dev, off_dev, (const uint32_t*)blinds32_dev, (uint32_t*)out_blinded32_dev,
+                                              out_status_dev, (int)n, ws, st), wb, st);
+}
+int ncg_oprf_blind_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* blinds32,
+                         void* out_blinded32, uint8_t* out_status) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_blind_batch", suite, mode, 0, OPRF_NO_LIMIT, n, nullptr, 0, {}), n, off, blinds32, out_blinded32, out_status);
+  if (int rc = oprf_input_lengths(ctx, "oprf_blind_batch", n, off)) return rc;
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, o_;
+  if (int rc = stage_msgs(hc, "oprf_blind_batch", n, inputs, off, rel, &msg, &o_)) return rc;
+  const int b = hc.in(blinds32, n * 32), o = hc.out(out_blinded32, n * 32), s = hc.out(out_status, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, b, n * 32);
+    return rc;
+  }
+  const int rc = ncg_oprf_blind_batch_dev(ctx, suite, mode, n, hc.dev(msg), hc.dev<const uint64_t>(o_), hc.dev(b), hc.dev(o), hc.dev<uint8_t>(s),
+                                          ctx->stream);
+  ed_clear_staged(hc, b, n * 32);
+  return hc.finish(rc);
+}
+int ncg_oprf_mul_batch_dev(ncg_ctx* ctx, int suite, size_t n, const void* elements32_dev, const void* scalars32_dev, int flags, void* out32_dev,
+                           uint8_t* out_status_dev, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_mul_batch", suite, 0, flags, OPRF_NO_LIMIT, n, nullptr, 0, {elements32_dev, scalars32_dev, out32_dev}), n,
+            elements32_dev, scalars32_dev, out32_dev, out_status_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_mul_batch((const uint32_t*)elements32_dev, (const uint32_t*)scalars32_dev, flags, (uint32_t*)out32_dev,
+                                            out_status_dev, (int)n, ws, st), wb, st);
+}
+int ncg_oprf_mul_batch(ncg_ctx* ctx, int suite, size_t n, const void* elements32, const void* scalars32, int flags, void* out32,
+                       uint8_t* out_status) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_mul_batch", suite, 0, flags, OPRF_NO_LIMIT, n, nullptr, 0, {}), n, elements32, scalars32, out32, out_status);
+  const size_t sbytes = (flags & NCG_OPRF_ONE_SCALAR) ? 32 : n * 32;
+  HostCall hc(ctx);
+  const int e = hc.in(elements32, n * 32), k = hc.in(scalars32, sbytes), o = hc.out(out32, n * 32), s = hc.out(out_status, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, sbytes);
+    return rc;
+  }
+  const int rc = ncg_oprf_mul_batch_dev(ctx, suite, n, hc.dev(e), hc.dev(k), flags, hc.dev(o), hc.dev<uint8_t>(s), ctx->stream);
+  ed_clear_staged(hc, k, sbytes);
+  return hc.finish(rc);
+}
+int ncg_oprf_finalize_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev, const void* info,
+                                size_t info_len, const void* blinds32_dev, const void* evaluated32_dev, void* out64_dev, uint8_t* out_status_dev,
+                                void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_finalize_batch", suite, mode, 0, OPRF_NO_LIMIT, n, info, info_len, {blinds32_dev, evaluated32_dev}), n, off_dev,
+            blinds32_dev, evaluated32_dev, out64_dev, out_status_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, info_len, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_finalize_batch(mode, (const uint8_t*)inputs_dev, off_dev, (const uint8_t*)info, (uint32_t)info_len,
+                                                 (const uint32_t*)blinds32_dev, (const uint32_t*)evaluated32_dev, (uint8_t*)out64_dev,
+                                                 out_status_dev, (int)n, ws, st), wb, st);
+}
+int ncg_oprf_finalize_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* info,
+                            size_t info_len, const void* blinds32, const void* evaluated32, void* out64, uint8_t* out_status) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_finalize_batch", suite, mode, 0, OPRF_NO_LIMIT, n, info, info_len, {}), n, off, blinds32, evaluated32, out64,
+            out_status);
+  if (int rc = oprf_input_lengths(ctx, "oprf_finalize_batch", n, off)) return rc;
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, o_;
+  if (int rc = stage_msgs(hc, "oprf_finalize_batch", n, inputs, off, rel, &msg, &o_)) return rc;
+  const int b = hc.in(blinds32, n * 32), e = hc.in(evaluated32, n * 32), o = hc.out(out64, n * 64), s = hc.out(out_status, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, b, n * 32);
+    return rc;
+  }
+  const int rc = ncg_oprf_finalize_batch_dev(ctx, suite, mode, n, hc.dev(msg), hc.dev<const uint64_t>(o_), info, info_len, hc.dev(b), hc.dev(e),
+                                             hc.dev(o), hc.dev<uint8_t>(s), ctx->stream);
+  ed_clear_staged(hc, b, n * 32);
+  return hc.finish(rc);
+}
+int ncg_oprf_evaluate_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs_dev, const uint64_t* off_dev, const void* info,
+                                size_t info_len, const void* scalar32_dev, int flags, void* out64_dev, uint8_t* out_status_dev, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_evaluate_batch", suite, mode, flags, OPRF_NO_LIMIT, n, info, info_len, {scalar32_dev}), n, off_dev,
+            scalar32_dev, out64_dev, out_status_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, info_len, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_evaluate_batch(mode, (const uint8_t*)inputs_dev, off_dev, (const uint8_t*)info, (uint32_t)info_len,
+                                                 (const uint32_t*)scalar32_dev, flags, (uint8_t*)out64_dev, out_status_dev, (int)n, ws, st), wb, st);
+}
+int ncg_oprf_evaluate_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* inputs, const uint64_t* off, const void* info,
+                            size_t info_len, const void* scalar32, int flags, void* out64, uint8_t* out_status) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_evaluate_batch", suite, mode, flags, OPRF_NO_LIMIT, n, info, info_len, {}), n, off, scalar32, out64, out_status);
+  if (int rc = oprf_input_lengths(ctx, "oprf_evaluate_batch", n, off)) return rc;
+  const size_t sbytes = (flags & NCG_OPRF_ONE_SCALAR) ? 32 : n * 32;
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, o_;
+  if (int rc = stage_msgs(hc, "oprf_evaluate_batch", n, inputs, off, rel, &msg, &o_)) return rc;
+  const int k = hc.in(scalar32, sbytes), o = hc.out(out64, n * 64), s = hc.out(out_status, n);
+  if (int rc = hc.stage()) {
+    ed_clear_staged(hc, k, sbytes);
+    return rc;
+  }
+  const int rc = ncg_oprf_evaluate_batch_dev(ctx, suite, mode, n, hc.dev(msg), hc.dev<const uint64_t>(o_), info, info_len, hc.dev(k), flags,
+                                             hc.dev(o), hc.dev<uint8_t>(s), ctx->stream);
+  ed_clear_staged(hc, k, sbytes);
+  return hc.finish(rc);
+}
+int ncg_oprf_composite_scalars_batch_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32_dev, const void* D32_dev,
+                                         void* out32_dev, uint8_t* out_status_dev, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_composite_scalars_batch", suite, mode, 0, 65535, n, nullptr, 0, {C32_dev, D32_dev, out32_dev}), n, B32, C32_dev,
+            D32_dev, out32_dev, out_status_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, 0, &ws, &wb)) return rc;
+  return oprf_done(ctx, ncg::oprf_composite_batch(mode, (const uint8_t*)B32, (const uint32_t*)C32_dev, (const uint32_t*)D32_dev,
+                                                  (uint32_t*)out32_dev, out_status_dev, (int)n, ws, st), wb, st);
+}
+int ncg_oprf_composite_scalars_batch(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32, const void* D32, void* out32,
+                                     uint8_t* out_status) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_composite_scalars_batch", suite, mode, 0, 65535, n, nullptr, 0, {}), n, B32, C32, D32, out32, out_status);
+  HostCall hc(ctx);
+  const int c = hc.in(C32, n * 32), d = hc.in(D32, n * 32), o = hc.out(out32, n * 32), s = hc.out(out_status, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_oprf_composite_scalars_batch_dev(ctx, suite, mode, n, B32, hc.dev(c), hc.dev(d), hc.dev(o), hc.dev<uint8_t>(s), ctx->stream));
+}
+
+// The composites of a proof call: d on the device, every row of C and D accepted (or the call fails on the first one that is not),
+// then M = sum d_i C_i and, where Z32 is given, Z = sum d_i D_i by the ristretto MSM.  d stays at ws + OPRF_PROOF_WS + 1024.
+static int oprf_composites(ncg_ctx* ctx, const char* op, int mode, size_t n, const void* B32, const void* C32_dev, const void* D32_dev, uint8_t* ws,
+                           uint8_t* M32, uint8_t* Z32, hipStream_t st) {
+  uint32_t bw[8], baff[16];
+  uint8_t bok = 0;
+  memcpy(bw, B32, 32);
+  ncg::ristretto_decode_host(bw, baff, &bok, 0, 1);
+  bool bzero = true;
+  for (int i = 0; i < 8; i++) bzero = bzero && bw[i] == 0;
+  if (!bok || bzero) return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: the public key %s", op, bzero ? "is the identity" : "does not decode");
+  uint32_t* d_d = (uint32_t*)(ws + OPRF_PROOF_WS + 1024);
+  uint8_t* d_st = (uint8_t*)(d_d + n * 8);
+  NCG_HIP(ctx, ncg::oprf_composite_batch(mode, (const uint8_t*)B32, (const uint32_t*)C32_dev, (const uint32_t*)D32_dev, d_d, d_st, (int)n, ws, st));
+  std::vector<uint8_t> status(n);
+  NCG_HIP(ctx, hipMemcpyAsync(status.data(), d_st, n, hipMemcpyDeviceToHost, st));
+  NCG_HIP(ctx, hipStreamSynchronize(st));
+  for (size_t i = 0; i < n; i++)
+    if (status[i])
+      return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: row %zu: an element %s", op, i,
+                     status[i] == 2 ? "is the identity" : "does not decode");
+  if (int rc = ncg_ristretto_msm_dev(ctx, n, C32_dev, d_d, M32, nullptr, st)) return rc;
+  if (Z32)
+    if (int rc = ncg_ristretto_msm_dev(ctx, n, D32_dev, d_d, Z32, nullptr, st)) return rc;
+  return NCG_OK;
+}
+static size_t oprf_proof_ws_extra(size_t n) { return OPRF_PROOF_WS + 1024 + n * 32 + align256(n); }
+int ncg_oprf_generate_proof_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* k32, const void* B32, const void* C32_dev,
+                                const void* D32_dev, const void* r32, void* out_proof64, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_generate_proof", suite, mode, 0, 65535, n, nullptr, 0, {C32_dev, D32_dev}), n, k32, B32, C32_dev, D32_dev, r32,
+            out_proof64);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint32_t kr[16], pts[40], c[8], s[8];   // pts: B M Z t2 t3
+  memcpy(kr, k32, 32);
+  memcpy(kr + 8, r32, 32);
+  auto wipe = [&] {
+    for (int i = 0; i < 16; i++) ((volatile uint32_t*)kr)[i] = 0;
+  };
+  if (!ncg::oprf_scalar_ok_host(kr, 0) || !ncg::oprf_scalar_ok_host(kr + 8, 0)) {
+    wipe();
+    return set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: oprf_generate_proof: the key and the nonce must be below L and not zero");
+  }
+  uint8_t* ws = nullptr;
+  size_t wb = 0;
+  int rc = ensure_ed_scan_table(ctx);
+  if (rc == NCG_OK) rc = oprf_ws(ctx, 0, oprf_proof_ws_extra(n), &ws, &wb);
+  if (rc != NCG_OK) {
+    wipe();
+    return rc;
+  }
+  memcpy(pts, B32, 32);
+  rc = oprf_composites(ctx, "oprf_generate_proof", mode, n, B32, C32_dev, D32_dev, ws, (uint8_t*)(pts + 8), nullptr, st);
+  if (rc == NCG_OK) {
+    uint8_t* pw = ws + OPRF_PROOF_WS;   // M (32) | k r (64) | Z t3 t2 (96)
+    uint32_t zt[24];
+    hipError_t e = ncg::oprf_put(pw, (const uint8_t*)(pts + 8), 32, st);
+    if (e == hipSuccess) e = ncg::oprf_put(pw + 32, (const uint8_t*)kr, 64, st);
+    if (e == hipSuccess)
+      e = ncg::oprf_proof_points(ctx->ed_scan_tab, (const uint32_t*)pw, (const uint32_t*)(pw + 32), (uint32_t*)(pw + 96), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(zt, pw + 96, 96, hipMemcpyDeviceToHost, st);
+    (void)hipMemsetAsync(ctx->oprf_ws, 0, wb, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      wipe();
+      NCG_HIP(ctx, e);
+    }
+    memcpy(pts + 16, zt, 32);        // Z
+    memcpy(pts + 24, zt + 16, 32);   // t2
+    memcpy(pts + 32, zt + 8, 32);    // t3
+    ncg::oprf_challenge_host(mode, (const uint8_t*)pts, c);
+    ncg::oprf_proof_s_host(c, kr, kr + 8, s);
+    memcpy(out_proof64, c, 32);
+    memcpy((char*)out_proof64 + 32, s, 32);
+  } else {
+    (void)hipMemsetAsync(ctx->oprf_ws, 0, wb, st);
+  }
+  wipe();
+  return rc;
+}
+int ncg_oprf_generate_proof(ncg_ctx* ctx, int suite, int mode, size_t n, const void* k32, const void* B32, const void* C32, const void* D32,
+                            const void* r32, void* out_proof64) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_generate_proof", suite, mode, 0, 65535, n, nullptr, 0, {}), n, k32, B32, C32, D32, r32, out_proof64);
+  HostCall hc(ctx);
+  const int c = hc.in(C32, n * 32), d = hc.in(D32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_oprf_generate_proof_dev(ctx, suite, mode, n, k32, B32, hc.dev(c), hc.dev(d), r32, out_proof64, ctx->stream));
+}
+int ncg_oprf_verify_proof_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32_dev, const void* D32_dev,
+                              const void* proof64, uint8_t* out_ok, void* stream) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_verify_proof", suite, mode, 0, 65535, n, nullptr, 0, {C32_dev, D32_dev}), n, B32, C32_dev, D32_dev, proof64,
+            out_ok);
+  const hipStream_t st = stream_of(ctx, stream);
+  *out_ok = 0;
+  uint32_t cs[16], sc[16], pts[40], c2[8];   // pts: B M Z t2 t3
+  memcpy(cs, proof64, 64);
+  uint8_t* ws;
+  size_t wb;
+  if (int rc = oprf_ws(ctx, 0, oprf_proof_ws_extra(n), &ws, &wb)) return rc;
+  memcpy(pts, B32, 32);
+  int rc = oprf_composites(ctx, "oprf_verify_proof", mode, n, B32, C32_dev, D32_dev, ws, (uint8_t*)(pts + 8), (uint8_t*)(pts + 16), st);
+  if (rc == NCG_OK && ncg::oprf_scalar_ok_host(cs, 1) && ncg::oprf_scalar_ok_host(cs + 8, 1)) {   // Fn.fromBytes: below L, zero allowed
+    // t2 = s G + c B and t3 = s M + c Z: two MSMs of two terms on rows laid out in the workspace
+    static const uint8_t G[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x71, 0xa8, 0x84, 0xa9, 0x61, 0xc5, 0x00, 0x51, 0x5f,
+                                  0x58, 0xe3, 0x0b, 0x6a, 0xa5, 0x82, 0xdd, 0x8d, 0xb6, 0xa6, 0x59, 0x45, 0xe0, 0x8d, 0x2d, 0x76};
+    uint8_t rows[128];
+    memcpy(rows, G, 32);
+    memcpy(rows + 32, B32, 32);
+    memcpy(rows + 64, pts + 8, 64);
+    memcpy(sc, cs + 8, 32);   // s first
+    memcpy(sc + 8, cs, 32);
+    uint8_t* pw = ws + OPRF_PROOF_WS;   // G B M Z (128) | s c (64)
+    hipError_t e = ncg::oprf_put(pw, rows, 128, st);
+    if (e == hipSuccess) e = ncg::oprf_put(pw + 128, (const uint8_t*)sc, 64, st);
+    NCG_HIP(ctx, e);
+    rc = ncg_ristretto_msm_dev(ctx, 2, pw, pw + 128, pts + 24, nullptr, st);
+    if (rc == NCG_OK) rc = ncg_ristretto_msm_dev(ctx, 2, pw + 64, pw + 128, pts + 32, nullptr, st);
+    if (rc == NCG_OK) {
+      ncg::oprf_challenge_host(mode, (const uint8_t*)pts, c2);
+      *out_ok = memcmp(c2, cs, 32) == 0 ? 1 : 0;
+    }
+  }
+  (void)hipMemsetAsync(ctx->oprf_ws, 0, wb, st);
+  return rc;
+}
+int ncg_oprf_verify_proof(ncg_ctx* ctx, int suite, int mode, size_t n, const void* B32, const void* C32, const void* D32, const void* proof64,
+                          uint8_t* out_ok) {
+  NCG_BEGIN(ctx, oprf_rule(ctx, "oprf_verify_proof", suite, mode, 0, 65535, n, nullptr, 0, {}), n, B32, C32, D32, proof64, out_ok);
+  HostCall hc(ctx);
+  const int c = hc.in(C32, n * 32), d = hc.in(D32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_oprf_verify_proof_dev(ctx, suite, mode, n, B32, hc.dev(c), hc.dev(d), proof64, out_ok, ctx->stream));
+}
+// The pieces of oprf.hpp on raw words, in the style of ncg_decaf448_check
+int ncg_oprf_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out) {
+  int rrc = NCG_OK;
+  if (ctx && n > (1u << 24)) rrc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: oprf_check: batch too large (max 2^24)");
+  else if (ctx && op == 3 && (variant < 2 || variant > 32)) rrc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: oprf_check: variant %d outside 2..32", variant);
+  const Rule rule = {"oprf_check", rrc};
+  NCG_BEGIN(ctx, rule, n, a, b, out);
+  int wa, wb, wo;
+  ncg::oprf_check_words(op, &wa, &wb, &wo);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * wa * 4), db = hc.in(b, n * wb * 4);
+  const int o = hc.out(out, n * (wo ? wo : 8) * 4, true);
+  if (int rc = hc.stage()) return rc;
+  if (wo) NCG_HIP(ctx, ncg::oprf_check(op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, ctx->stream));
+  return hc.finish(NCG_OK);
 }
 
 // ---- bls12-381 pairings (pairing.hip).  The _dev form keeps the verdict word, the group offsets and the Miller values in

@@ -81,6 +81,10 @@ struct ncg_ctx {
   // the (X, Y, Z) rows of the fixed-base walk, a broadcast scalar; one call at a time
   void* rist_ws = nullptr;
   size_t rist_ws_bytes = 0;
+  // OPRF (oprf.hip): the strings of a call (DST', "Seed-" || ctx, info), the seed of the composites, the one scalar inverted, and the
+  // rows of the proof calls - it holds secrets during a call and is cleared on the call's stream before the call returns
+  void* oprf_ws = nullptr;
+  size_t oprf_ws_bytes = 0;
   // pairings (pairing.hip): the verdict word, the group offsets and one Miller value per pair; one call at a time
   void* pair_ws = nullptr;
   size_t pair_ws_bytes = 0;

@@ -335,6 +335,55 @@ void ristretto_from_uniform_host(const uint32_t* bytes64, uint32_t* out, uint32_
 void ristretto_mul_host(const uint32_t* enc, const uint32_t* scalars, int one_scalar, uint32_t* out, uint8_t* out_ok, int n);
 int ristretto_check_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
+// ristretto255-SHA512 OPRF (oprf.hip).  Elements and scalars are rows of 8 LE words, outputs 64 packed bytes, messages a blob with
+// n + 1 offsets; status: one byte per row (0 ok, 1 undecodable, 2 identity, 3 scalar zero or not below L).  dst_host, info_host and
+// B_host are HOST pointers; ws: oprf_ws_bytes(info_len) bytes of device memory laid out as below, which hold a secret (the one
+// scalar inverted) after a call with ONE_SCALAR | INVERT.  flags: bit 0 one scalar for every row, bit 1 multiply by its inverse.
+constexpr size_t OPRF_PUT_CHUNK = 1024;
+constexpr size_t OPRF_WS_DST = 0, OPRF_WS_SDST = 256, OPRF_WS_B = 320, OPRF_WS_SCALAR = 352, OPRF_WS_SEED = 384, OPRF_WS_INFO = 512;
+size_t oprf_ws_bytes(size_t info_len);
+size_t oprf_dst(const char* prefix, int mode, int with_len, uint8_t* out);  // prefix || "OPRFV1-" || mode || "-ristretto255-SHA512" [|| its length]
+hipError_t oprf_put(uint8_t* d_out, const uint8_t* host, size_t len, hipStream_t st);
+hipError_t oprf_xmd_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t out_len, uint8_t* out,
+                          int n, uint8_t* ws, hipStream_t st);
+hipError_t oprf_hash_to_group_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t* out,
+                                    uint32_t* out_affine, int n, uint8_t* ws, hipStream_t st);
+hipError_t oprf_hash_to_scalar_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t* out, int n,
+                                     uint8_t* ws, hipStream_t st);
+hipError_t oprf_blind_batch(int mode, const uint8_t* inputs, const uint64_t* off, const uint32_t* blinds, uint32_t* out, uint8_t* status, int n,
+                            uint8_t* ws, hipStream_t st);
+hipError_t oprf_mul_batch(const uint32_t* elements, const uint32_t* scalars, int flags, uint32_t* out, uint8_t* status, int n, uint8_t* ws,
+                          hipStream_t st);
+hipError_t oprf_finalize_batch(int mode, const uint8_t* inputs, const uint64_t* off, const uint8_t* info_host, uint32_t info_len,
+                               const uint32_t* blinds, const uint32_t* evaluated, uint8_t* out64, uint8_t* status, int n, uint8_t* ws,
+                               hipStream_t st);
+hipError_t oprf_evaluate_batch(int mode, const uint8_t* inputs, const uint64_t* off, const uint8_t* info_host, uint32_t info_len,
+                               const uint32_t* scalars, int flags, uint8_t* out64, uint8_t* status, int n, uint8_t* ws, hipStream_t st);
+hipError_t oprf_composite_batch(int mode, const uint8_t* B_host, const uint32_t* C, const uint32_t* D, uint32_t* out, uint8_t* status, int n,
+                                uint8_t* ws, hipStream_t st);
+// the proof: Z = k M, t3 = r M and t2 = r B (table: the signing scan table) from M (8 words) and kr = k || r (16 words) into out (24
+// words); then, on the host, the challenge of the five encodings B M Z t2 t3 and s = r - c k
+hipError_t oprf_proof_points(const uint32_t* table, const uint32_t* M, const uint32_t* kr, uint32_t* out, hipStream_t st);
+void oprf_proof_points_host(const uint32_t* table, const uint32_t* M, const uint32_t* kr, uint32_t* out);
+int oprf_scalar_ok_host(const uint32_t* k, int allow_zero);
+void oprf_challenge_host(int mode, const uint8_t* pts160, uint32_t* c);
+void oprf_proof_s_host(const uint32_t* c, const uint32_t* k, const uint32_t* r, uint32_t* s);
+// the pieces of oprf.hpp on raw words (ncg_oprf_check); words per row of each op: oprf_check_words (0 = unknown op)
+void oprf_check_words(int op, int* wa, int* wb, int* wo);
+hipError_t oprf_check(int op, int variant, const uint32_t* d_a, const uint32_t* d_b, uint32_t* d_out, int n, hipStream_t st);
+int oprf_check_host(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out);
+// one row each on the CPU; dst as the caller gave it (the twin appends the length byte)
+void oprf_xmd_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out);
+void oprf_hash_to_group_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out, uint32_t* out_affine);
+void oprf_hash_to_scalar_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out);
+uint8_t oprf_blind_host(int mode, const uint8_t* input, uint64_t len, const uint32_t* blind, uint32_t* out);
+uint8_t oprf_mul_host(const uint32_t* element, const uint32_t* scalar, int invert, uint32_t* out);
+uint8_t oprf_finalize_host(int mode, const uint8_t* input, uint64_t len, const uint8_t* info, uint32_t info_len, const uint32_t* blind,
+                           const uint32_t* evaluated, uint8_t* out64);
+uint8_t oprf_evaluate_host(int mode, const uint8_t* input, uint64_t len, const uint8_t* info, uint32_t info_len, const uint32_t* scalar,
+                           int invert, uint8_t* out64);
+void oprf_composite_host(int mode, const uint8_t* B32, const uint32_t* C, const uint32_t* D, uint32_t* out, uint8_t* status, int n);
+
 // bls12-381 pairings (pairing.hip).  ws: PAIRING_WS_WORDS words per pair; off: n_groups + 1 ascending pair offsets (device);
 // first_bad: one 64-bit word, all ones or (index << 8 | PairingBad code) of the first refused pair after pairing_miller;
 // pairing_finish multiplies each group's Miller values (largest_group decides the number of passes), exponentiates and stores

@@ -30,6 +30,7 @@
 #include "ed25519_sign.hip"
 #include "secp256k1_sign.hip"
 #include "ed448_sign.hip"
+#include "oprf.hip"
 
 using namespace ncg;
 
@@ -584,6 +585,64 @@ int ht_ristretto_consts(uint32_t* out32) {
   fe9_to_wire(out32 + 24, RistrettoConsts::d_minus_one_sq());
   return 0;
 }
+
+// The ristretto255 OPRF on the CPU twins of oprf.hip, one row per call unless n is given: elements and scalars 8 LE words, outputs 64
+// bytes, dst as the caller has it (1..255 bytes, -1 otherwise), flags as ncg_oprf_mul_batch without ONE_SCALAR.  The row functions
+// return the row status.  ht_oprf_check: the pieces of ncg_oprf_check, -1 for an unknown op.  ht_oprf_proof: c || s of generateProof
+// from M = the composite of C (the caller's MSM), with Z, t2 and t3 through the secret multiplies; ht_oprf_challenge: the challenge
+// of the five encodings B M Z t2 t3.
+int ht_oprf_xmd(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out) {
+  if (dst_len < 1 || dst_len > 255 || out_len < 1 || out_len > 256) return -1;
+  oprf_xmd_host(msg, len, dst, dst_len, out_len, out);
+  return 0;
+}
+int ht_oprf_hash_to_group(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out, uint32_t* out_affine) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  oprf_hash_to_group_host(msg, len, dst, dst_len, out, out_affine);
+  return 0;
+}
+int ht_oprf_hash_to_scalar(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  oprf_hash_to_scalar_host(msg, len, dst, dst_len, out);
+  return 0;
+}
+int ht_oprf_blind(int mode, const uint8_t* input, uint64_t len, const uint32_t* blind, uint32_t* out) { return oprf_blind_host(mode, input, len, blind, out); }
+int ht_oprf_mul(const uint32_t* element, const uint32_t* scalar, int flags, uint32_t* out) {
+  if (flags & ~NCG_OPRF_INVERT) return -1;
+  return oprf_mul_host(element, scalar, (flags & NCG_OPRF_INVERT) != 0, out);
+}
+int ht_oprf_finalize(int mode, const uint8_t* input, uint64_t len, const uint8_t* info, uint32_t info_len, const uint32_t* blind,
+                     const uint32_t* evaluated, uint8_t* out64) {
+  return oprf_finalize_host(mode, input, len, info, info_len, blind, evaluated, out64);
+}
+int ht_oprf_evaluate(int mode, const uint8_t* input, uint64_t len, const uint8_t* info, uint32_t info_len, const uint32_t* scalar, int flags,
+                     uint8_t* out64) {
+  if (flags & ~NCG_OPRF_INVERT) return -1;
+  return oprf_evaluate_host(mode, input, len, info, info_len, scalar, (flags & NCG_OPRF_INVERT) != 0, out64);
+}
+int ht_oprf_composite(int mode, const uint8_t* B32, const uint32_t* C, const uint32_t* D, uint32_t* out, uint8_t* status, int n) {
+  oprf_composite_host(mode, B32, C, D, out, status, n);
+  return 0;
+}
+int ht_oprf_challenge(int mode, const uint8_t* pts160, uint32_t* c) {
+  oprf_challenge_host(mode, pts160, c);
+  return 0;
+}
+int ht_oprf_proof(int mode, const uint32_t* k, const uint8_t* B32, const uint32_t* M, const uint32_t* r, uint32_t* out_proof16) {
+  uint32_t kr[16], zt[24], pts[40];
+  if (!oprf_scalar_ok_host(k, 0) || !oprf_scalar_ok_host(r, 0)) return -1;
+  for (int i = 0; i < 8; i++) kr[i] = k[i], kr[8 + i] = r[i];
+  oprf_proof_points_host(ht_ed_scan_table(), M, kr, zt);
+  memcpy(pts, B32, 32);
+  memcpy(pts + 8, M, 32);
+  memcpy(pts + 16, zt, 32);
+  memcpy(pts + 24, zt + 16, 32);
+  memcpy(pts + 32, zt + 8, 32);
+  oprf_challenge_host(mode, (const uint8_t*)pts, out_proof16);
+  oprf_proof_s_host(out_proof16, k, r, out_proof16 + 8);
+  return 0;
+}
+int ht_oprf_check(int op, int variant, const uint32_t* a, const uint32_t* b, uint32_t* out) { return oprf_check_host(op, variant, a, b, out); }
 
 // Fp2 square root lane: in = c0 c1 wire (24 words); out = root wire; returns 1 if a root exists
 int ht_fp2_sqrt(const uint32_t* in, uint32_t* out) {

@@ -5,7 +5,8 @@ An element is held as an Edwards representative - an ed25519 wire point, 64 byte
 EdwardsPoint; decoding, encoding, equals, the Elligator map and every multiply run in HIP kernels (`ncg_ristretto_*`).  The shim
 does the argument checks of the reference and raises its messages: 'invalid ristretto255 encoding 1' is decided here from
 canonicity and parity, 'invalid ristretto255 encoding 2' covers every other row the device rejects.  `expand_message_xmd` over
-SHA-512 runs on the host (`h2c.expand_message_xmd`), the map on the device.  Batch forms take and return encodings (32 bytes):
+SHA-512 runs on the host (`h2c.expand_message_xmd`) and the map on the device, or both on the device with `device_hash=True`;
+`hashToScalar` hashes and reduces on the device; the OPRF built on these is `noble_curves_amd.oprf`.  Batch forms take and return encodings (32 bytes):
 only bytes cross.  The representatives may be fed to the NCG_ED25519 entry points (MSM, resident sets, add pairs); two elements
 are compared only through `equals` or their encodings.
 """
@@ -234,12 +235,38 @@ def deriveToCurve(bytes64, engine=None):
     return Point(aff[0])
 
 
-def hashToCurve_batch(msgs, DST=None, engine=None):
-    """ristretto255_hasher.hashToCurve(msg, { DST }).toBytes() for every message: expand_message_xmd over SHA-512 here, the map on
-    the device"""
+def _device_dst(dst):
+    """RFC 9380 section 5.3.3: a DST above 255 bytes is replaced by its hash, on the host (the device takes 1..255 bytes)"""
+    return hashlib.sha512(b"H2C-OVERSIZE-DST-" + dst).digest() if len(dst) > 255 else dst
+
+
+def hashToCurve_batch(msgs, DST=None, engine=None, device_hash=False):
+    """ristretto255_hasher.hashToCurve(msg, { DST }).toBytes() for every message: expand_message_xmd over SHA-512 here and the map on
+    the device, or - device_hash - both in one kernel (ncg_ristretto_hash_to_group_batch)"""
     dst = _dst(DST)
+    if device_hash:
+        msgs = [bytes(m) for m in msgs]
+        if not msgs:
+            return []
+        return [r.tobytes() for r in (engine or get_engine()).ristretto_hash_to_group_batch(msgs, _device_dst(dst))[0]]
     return deriveToCurve_batch([expand_message_xmd(m, dst, 64, hashlib.sha512) for m in msgs], engine)
 
 
-def hashToCurve(msg, DST=None, engine=None):
+def hashToCurve(msg, DST=None, engine=None, device_hash=False):
+    if device_hash:
+        return Point((engine or get_engine()).ristretto_hash_to_group_batch([bytes(msg)], _device_dst(_dst(DST)), want_affine=True)[1][0])
     return deriveToCurve(expand_message_xmd(msg, _dst(DST), 64, hashlib.sha512), engine)
+
+
+def hashToScalar_batch(msgs, DST=None, engine=None):
+    """ristretto255_hasher.hashToScalar(msg, { DST }) for every message, as ints: expand_message_xmd and the reduction mod L on the
+    device (ncg_ristretto_hash_to_scalar_batch)"""
+    msgs = [bytes(m) for m in msgs]
+    if not msgs:
+        return []
+    out = (engine or get_engine()).ristretto_hash_to_scalar_batch(msgs, _device_dst(_dst(DST)))
+    return [int.from_bytes(r.tobytes(), "little") for r in out]
+
+
+def hashToScalar(msg, DST=None, engine=None):
+    return hashToScalar_batch([msg], DST, engine)[0]
