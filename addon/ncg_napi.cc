@@ -579,6 +579,46 @@ static napi_value Oprf(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// RFC 9380 for secp256k1 and edwards25519 (ncg_h2c_*): h2c(op, suite, count, msgs, lens, dst).  Messages travel back to back with n
+// lengths as LE uint32, as for oprf(); dst is 1..255 bytes (the shim hashes an oversize one).
+//   op 0 hashToCurve (count 2) / encodeToCurve (count 1)  -> n x 64 affine wire bytes of the suite's curve, then n ZERO flags
+//   op 1 hashToScalar (count ignored)                     -> n x 32 little-endian
+static napi_value H2c(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t op, suite, count;
+  uint8_t *a = nullptr, *b = nullptr, *c = nullptr, *out;
+  size_t al = 0, bl = 0, cl = 0;
+  if (argc < 6 || napi_get_value_int32(env, argv[0], &op) != napi_ok || (op != 0 && op != 1) || napi_get_value_int32(env, argv[1], &suite) != napi_ok ||
+      napi_get_value_int32(env, argv[2], &count) != napi_ok || !get_u8(env, argv[3], &a, &al) || !get_u8(env, argv[4], &b, &bl) ||
+      !get_u8(env, argv[5], &c, &cl)) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: h2c(op, suite, count, msgs, lens, dst)");
+    return nullptr;
+  }
+  const size_t n = bl / 4;
+  std::vector<uint64_t> off(n + 1, 0);
+  bool good = bl % 4 == 0;
+  for (size_t i = 0; good && i < n; i++) {
+    uint32_t len;
+    memcpy(&len, b + 4 * i, 4);
+    off[i + 1] = off[i] + len;
+  }
+  if (!good || off[n] != al) {
+    napi_throw_error(env, nullptr, "noble-gpu: h2c: the rows do not match");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n * (op == 0 ? 65 : 32), &out);
+  if (!res) return nullptr;
+  int rc = 0;
+  if (n == 0) rc = 0;
+  else if (op == 0) rc = ncg_h2c_hash_batch(g_ctx, suite, n, count, al ? a : nullptr, off.data(), c, cl, out, out + n * 64);
+  else rc = ncg_h2c_hash_to_scalar_batch(g_ctx, suite, n, al ? a : nullptr, off.data(), c, cl, out);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
 // decaf448 on packed rows (ncg_decaf448_*): one entry, the operation chosen by `mode` (see the list at the top of this file).
 static napi_value Decaf448(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -1298,7 +1338,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"oprf", Oprf}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"oprf", Oprf}, {"h2c", H2c}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

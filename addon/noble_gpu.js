@@ -1089,6 +1089,73 @@ function oprfHashToScalar(msg, dst) {
   const { blob, lens } = oprfBlob([msg]);
   return native.oprf(6, 0, 0, blob, lens, dst, OPRF_NONE);
 }
+// ---- RFC 9380 for secp256k1 and ed25519: secp256k1_hasher (src/secp256k1.ts:403-428) and ed25519_hasher (src/ed25519.ts:381-405)
+// under createHasher (src/abstract/hash-to-curve.ts:441-530), hashed and mapped on the device (ncg_h2c_hash_batch,
+// ncg_h2c_hash_to_scalar_batch).  Every batch form makes one native call.  Points come back as affine { x, y } of bigints - ZERO as
+// the curve's affine ZERO, (0, 0) or (0, 1) - or through opts.Point.fromAffine when the caller passes the reference's Point class.
+const H2C_SUITES = {
+  secp256k1: { id: 0, DST: 'secp256k1_XMD:SHA-256_SSWU_RO_', encodeDST: 'secp256k1_XMD:SHA-256_SSWU_NU_', hash: 'sha256',
+    p: 0xfffffffffffffffffffffffffffffffffffffffffffffffffffffffefffffc2fn },
+  ed25519: { id: 1, DST: 'edwards25519_XMD:SHA-512_ELL2_RO_', encodeDST: 'edwards25519_XMD:SHA-512_ELL2_NU_', hash: 'sha512',
+    p: (1n << 255n) - 19n },
+};
+function h2cDst(suite, DST) {       // normDST (hash-to-curve.ts:160-167) and the oversize rule of expand_message_xmd (:202)
+  if (!(DST instanceof Uint8Array) && typeof DST !== 'string') throw new Error('DST must be Uint8Array or ascii string');
+  let dst = typeof DST === 'string' ? Uint8Array.from(Buffer.from(DST, 'ascii')) : DST;
+  if (dst.length === 0) throw new Error('DST must be non-empty');
+  if (dst.length > 255) dst = new Uint8Array(crypto.createHash(suite.hash).update('H2C-OVERSIZE-DST-', 'ascii').update(dst).digest());
+  return dst;
+}
+function h2cMsgs(msgs) {
+  if (!Array.isArray(msgs)) throw new Error('expected array');
+  msgs.forEach((m) => { if (!(m instanceof Uint8Array)) throw new Error('expected Uint8Array, got type=' + typeof m); });
+  return msgs;
+}
+function h2cPoints(suite, msgs, opts, count) {
+  const dst = h2cDst(suite, opts && opts.DST !== undefined ? opts.DST : (count === 2 ? suite.DST : suite.encodeDST));   // only DST may be overridden
+  const n = h2cMsgs(msgs).length;
+  if (n === 0) return [];
+  init();
+  const { blob, lens } = oprfBlob(msgs);
+  const out = native.h2c(0, suite.id, count, blob, lens, dst);
+  return Array.from({ length: n }, (_, i) => {
+    const a = { x: leNumber(out, 64 * i, 32), y: leNumber(out, 64 * i + 32, 32) };
+    return opts && opts.Point ? (out[64 * n + i] ? opts.Point.ZERO : opts.Point.fromAffine(a)) : a;
+  });
+}
+function h2cScalars(suite, msgs, opts) {
+  const dst = h2cDst(suite, opts && opts.DST !== undefined ? opts.DST : 'HashToScalar-');     // _DST_scalar (:412, :523)
+  const n = h2cMsgs(msgs).length;
+  if (n === 0) return [];
+  init();
+  const { blob, lens } = oprfBlob(msgs);
+  const out = native.h2c(1, suite.id, 1, blob, lens, dst);
+  return Array.from({ length: n }, (_, i) => leNumber(out, 32 * i, 32));
+}
+const secp256k1HashToCurveBatch = (msgs, opts) => h2cPoints(H2C_SUITES.secp256k1, msgs, opts, 2);
+const secp256k1EncodeToCurveBatch = (msgs, opts) => h2cPoints(H2C_SUITES.secp256k1, msgs, opts, 1);
+const ed25519HashToCurveBatch = (msgs, opts) => h2cPoints(H2C_SUITES.ed25519, msgs, opts, 2);
+const ed25519EncodeToCurveBatch = (msgs, opts) => h2cPoints(H2C_SUITES.ed25519, msgs, opts, 1);
+// hashToScalarBatch(msgs, { DST, curve }): curve 'secp256k1' (the default) or 'ed25519'
+function hashToScalarBatch(msgs, opts) {
+  const suite = H2C_SUITES[(opts && opts.curve) || 'secp256k1'];
+  if (!suite) throw new Error('hashToScalarBatch: curve must be secp256k1 or ed25519');
+  return h2cScalars(suite, msgs, opts);
+}
+function h2cHasher(name) {
+  const suite = H2C_SUITES[name];
+  return Object.freeze({
+    get defaults() { return { DST: suite.DST, encodeDST: suite.encodeDST, p: suite.p, m: 1, k: 128, expand: 'xmd', hash: suite.hash }; },
+    hashToCurve: (msg, opts) => h2cPoints(suite, [msg], opts, 2)[0],
+    encodeToCurve: (msg, opts) => h2cPoints(suite, [msg], opts, 1)[0],
+    hashToScalar: (msg, opts) => h2cScalars(suite, [msg], opts)[0],
+    hashToCurveBatch: (msgs, opts) => h2cPoints(suite, msgs, opts, 2),
+    encodeToCurveBatch: (msgs, opts) => h2cPoints(suite, msgs, opts, 1),
+    hashToScalarBatch: (msgs, opts) => h2cScalars(suite, msgs, opts),
+  });
+}
+const secp256k1_hasher = h2cHasher('secp256k1'), ed25519_hasher = h2cHasher('ed25519');
+
 function oprfMode(mode, info) {
   const m = mode === 2 ? leNumber(oprfHashToScalar(Buffer.concat([Buffer.from('Info', 'ascii'), Buffer.from([info.length >> 8, info.length & 255]), info]),
     Buffer.concat([Buffer.from('HashToScalar-', 'ascii'), oprfCtx(2)])), 0, 32) : 0n;
@@ -1595,5 +1662,7 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    ristrettoFromBytesBatch, ristrettoToBytesBatch, ristrettoEqualsBatch, ristrettoMultiplyBatch, ristrettoMultiplyBaseBatch, ristrettoMsm,
                    ristrettoDeriveToCurveBatch, ristrettoFromBytes, ristrettoToBytes, ristrettoEquals, ristrettoMultiply, ristrettoMultiplyBase,
                    ristrettoDeriveToCurve, ristretto255_oprf,
+                   secp256k1HashToCurveBatch, secp256k1EncodeToCurveBatch, ed25519HashToCurveBatch, ed25519EncodeToCurveBatch, hashToScalarBatch,
+                   secp256k1_hasher, ed25519_hasher,
                    decaf448FromBytesBatch, decaf448ToBytesBatch, decaf448EqualsBatch, decaf448MultiplyBatch, decaf448MultiplyBaseBatch,
                    decaf448DeriveToCurveBatch, native };

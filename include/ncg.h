@@ -651,6 +651,60 @@ int ncg_oprf_verify_proof_dev(ncg_ctx* ctx, int suite, int mode, size_t n, const
  * leaves out zero (rows of 8 words).  n above 2^24 is refused. */
 int ncg_oprf_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, const void* b, void* out);
 
+/* ---- RFC 9380 hash-to-curve for secp256k1 and edwards25519 ----------------------------------------------------
+ * secp256k1_hasher (src/secp256k1.ts:345-428: expand_message_xmd over SHA-256, simplified SWU on E', the 3-isogeny) and
+ * ed25519_hasher (src/ed25519.ts:294-405: xmd over SHA-512, Elligator 2, the map to Edwards form, the cofactor 8) under
+ * createHasher (src/abstract/hash-to-curve.ts:441-530), hashing included.  suite: one of NCG_H2C_*, any other id returns
+ * NCG_ERR_UNSUPPORTED (ncg_map_to_curve_batch keeps refusing both curves: these are dedicated entry points).  count: NCG_H2C_RO
+ * (2, hashToCurve: two field elements per row, their images added) or NCG_H2C_NU (1, encodeToCurve / mapToCurve); anything else is
+ * NCG_ERR_INVALID_ARG.  Messages are one blob with n + 1 ascending offsets, as in ncg_xmd_sha512_batch; dst is a HOST pointer in
+ * both forms, 1 <= dst_len <= 255 (an oversize DST is hashed by the caller: H("H2C-OVERSIZE-DST-" || DST)).  Outputs are affine
+ * wire points of NCG_SECP256K1 / NCG_ED25519 (64 bytes) and one is_inf byte per row, exactly what ncg_mul_var_batch, ncg_msm and
+ * ncg_encode_points_batch take; ZERO is written as (0, 0) on secp256k1 and (0, 1) on ed25519 with the byte set, as
+ * ncg_mul_var_batch reports it.  Rows of words (u48, out_u, out32, the points) behind a DEVICE pointer must be 4-byte aligned.
+ * n = 0 returns NCG_OK and touches nothing; n above 2^31 - 256 is refused ("batch too large").  Nothing here is secret.
+ * DST' and every hand-off of a call (the uniform bytes, the reduced elements, the mapped points) live in one workspace of the context:
+ * one call at a time per context, whatever streams the _dev forms are given - a second call on another stream would overwrite them.
+ *
+ * ncg_h2c_hash_batch: out[i] = hasher.hashToCurve(msg i, {DST: dst}) (count 2) or hasher.encodeToCurve(msg i, {DST: dst}) (count 1).
+ * ncg_h2c_map_batch: u48 holds count values per row, 48 bytes little-endian each, any value below 2^384, reduced mod p like
+ *   Fp.create; out[i] = hasher.mapToCurve(u) for count 1, and the cleared sum of the two images for count 2 - the way to reach
+ *   Q0 = +-Q1 (a doubling, or ZERO).
+ * ncg_h2c_hash_to_field_batch: out_u[i] = hash_to_field(msg i, count, {DST: dst, m: 1, k: 128}) as count reduced elements of 32
+ *   bytes little-endian: the hash half of ncg_h2c_hash_batch on its own.
+ * ncg_h2c_hash_to_scalar_batch: out32[i] = hasher.hashToScalar(msg i, {DST: dst}): one 48-byte chunk mod n (secp256k1) or mod L
+ *   (ed25519), 32 bytes little-endian.
+ * ncg_xmd_sha256_batch: out[i] = expand_message_xmd(msg i, dst, out_len) over SHA-256, out_len bytes per row, 1 <= out_len <= 256. */
+enum { NCG_H2C_SECP256K1_XMD_SHA256_SSWU = 0, NCG_H2C_EDWARDS25519_XMD_SHA512_ELL2 = 1 };
+enum { NCG_H2C_RO = 2, NCG_H2C_NU = 1 };
+int ncg_h2c_hash_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst,
+                       size_t dst_len, void* out_affine, uint8_t* out_is_inf);
+int ncg_h2c_hash_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev,
+                           const void* dst, size_t dst_len, void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream);
+int ncg_h2c_map_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* u48, void* out_affine, uint8_t* out_is_inf);
+int ncg_h2c_map_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* u48_dev, void* out_affine_dev,
+                          uint8_t* out_is_inf_dev, void* stream);
+int ncg_h2c_hash_to_scalar_batch(ncg_ctx* ctx, int suite, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                 size_t dst_len, void* out32);
+int ncg_h2c_hash_to_scalar_batch_dev(ncg_ctx* ctx, int suite, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev,
+                                     const void* dst, size_t dst_len, void* out32_dev, void* stream);
+int ncg_h2c_hash_to_field_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs, const uint64_t* msg_off,
+                                const void* dst, size_t dst_len, void* out_u);
+int ncg_h2c_hash_to_field_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev,
+                                    const void* dst, size_t dst_len, void* out_u_dev, void* stream);
+int ncg_xmd_sha256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                         size_t out_len, void* out);
+int ncg_xmd_sha256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                             size_t dst_len, size_t out_len, void* out_dev, void* stream);
+/* The lane code of csrc/h2c_suites.hpp on n rows of RAW uint32 words, bit for bit with its CPU twin: 24 words per row of a and of
+ * out, words an op does not use are not read / left zero.  Its own entry point: the table of ncg_field_check is closed.
+ *   0 / 1  a[0..12) mod p of secp256k1 / ed25519 -> out[0..8)          2 / 3  a[0..12) mod n of secp256k1 / mod L -> out[0..8)
+ *   4      SWU on E' of u = a[0..12): out = x, xd, y (8 words each), the point being (x / xd, y)
+ *   5      the 3-isogeny at the affine point (x', y') = a[0..8), a[8..16) of E': out = X, Y, Z of the Jacobian image, Z = 0 for ZERO
+ *   6      the edwards25519 map of u = a[0..12) before the cofactor: out = X, Y, Z with (x, y) = (X / Z, Y / Z)
+ * An op nobody defines reads nothing and leaves out zero.  n above 2^24 is refused. */
+int ncg_h2c_check(ncg_ctx* ctx, int op, size_t n, const void* a, void* out);
+
 /* ---- X448 (RFC 7748) and Ed448-Goldilocks (RFC 8032): the reference's src/ed448.ts -------------------------------
  * The curve has no ncg_curve id and no ncg_field_check field: these are dedicated entry points, bytes in and bytes out.
  * Field elements and scalars are 56 bytes little-endian, read as 14 words: a DEVICE pointer to such rows (scalars56, u56, out56,

@@ -16,6 +16,7 @@ SECP256K1, ED25519, BLS12_381_G1, BLS12_381_G2, BN254_G1 = 0, 1, 2, 3, 5
 POINT_BYTES = {SECP256K1: 64, ED25519: 64, BLS12_381_G1: 96, BLS12_381_G2: 192, BN254_G1: 64}
 FIELD_BYTES = {SECP256K1: 32, ED25519: 32, BLS12_381_G1: 48, BLS12_381_G2: 48, BN254_G1: 32}
 FIELD_BLS12_381_FR = 0
+H2C_SECP256K1, H2C_EDWARDS25519 = 0, 1       # suites of ncg_h2c_*: secp256k1_XMD:SHA-256_SSWU, edwards25519_XMD:SHA-512_ELL2
 FIELD_BN254_FR = 5
 POLY_ADD, POLY_SUB, POLY_DOT = 0, 1, 2
 POLY_MAX_POINTS = 8
@@ -253,6 +254,17 @@ _OPTIONAL_PROTOS = {
     "ncg_oprf_verify_proof": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp],
     "ncg_oprf_verify_proof_dev": [_vp, _i32, _i32, _sz, _vp, _vp, _vp, _vp, _vp, _vp],
     "ncg_oprf_check": [_vp, _i32, _i32, _sz, _vp, _vp, _vp],
+    "ncg_h2c_hash_batch": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_h2c_hash_batch_dev": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp],
+    "ncg_h2c_map_batch": [_vp, _i32, _sz, _i32, _vp, _vp, _vp],
+    "ncg_h2c_map_batch_dev": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _vp],
+    "ncg_h2c_hash_to_scalar_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ncg_h2c_hash_to_scalar_batch_dev": [_vp, _i32, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_h2c_hash_to_field_batch": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _sz, _vp],
+    "ncg_h2c_hash_to_field_batch_dev": [_vp, _i32, _sz, _i32, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_xmd_sha256_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ncg_xmd_sha256_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ncg_h2c_check": [_vp, _i32, _sz, _vp, _vp],
     "ncg_pairing_batch": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_pairing_batch_dev": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
     "ncg_bls_verify_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
@@ -1547,6 +1559,63 @@ class Engine:
 
     def map_to_curve_batch_dev(self, curve, n, count, d_u, d_out, d_inf, stream):
         self._check(self.lib.ncg_map_to_curve_batch_dev(self.h, curve, n, count, d_u, d_out, d_inf, stream))
+
+    # ---- RFC 9380 for secp256k1 and edwards25519 (suite H2C_SECP256K1 / H2C_EDWARDS25519): messages a list of byte strings, points
+    # affine wire rows uint8 [n, 64] of the suite's curve with is_inf uint8 [n], count 2 (hashToCurve) or 1 (encodeToCurve) ----------
+    def h2c_hash_batch(self, suite, msgs, dst, count):
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out, inf = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_h2c_hash_batch(self.h, suite, n, count, blob.ctypes.data if blob.size else None, off.ctypes.data, dst,
+                                                    len(dst), out.ctypes.data, inf.ctypes.data))
+        return out, inf
+
+    def h2c_map_batch(self, suite, u48, count):
+        """u48 uint8 [n, count * 48]: count values per row, 48 bytes little-endian each, any value below 2^384"""
+        u48 = np.ascontiguousarray(u48, dtype=np.uint8).reshape(-1, count * 48)
+        n = u48.shape[0]
+        out, inf = np.zeros((n, 64), dtype=np.uint8), np.zeros((n,), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_h2c_map_batch(self.h, suite, n, count, u48.ctypes.data, out.ctypes.data, inf.ctypes.data))
+        return out, inf
+
+    def h2c_hash_to_scalar_batch(self, suite, msgs, dst):
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, 32), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_h2c_hash_to_scalar_batch(self.h, suite, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst,
+                                                              len(dst), out.ctypes.data))
+        return out
+
+    def h2c_hash_to_field_batch(self, suite, msgs, dst, count):
+        """-> uint8 [n, count * 32]: the reduced elements, little-endian"""
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, count * 32), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_h2c_hash_to_field_batch(self.h, suite, n, count, blob.ctypes.data if blob.size else None, off.ctypes.data,
+                                                             dst, len(dst), out.ctypes.data))
+        return out
+
+    def xmd_sha256_batch(self, msgs, dst, out_len):
+        """expand_message_xmd over SHA-256 of every message -> uint8 [n, out_len]"""
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_xmd_sha256_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst, len(dst),
+                                                      out_len, out.ctypes.data))
+        return out
+
+    def h2c_check(self, op, a):
+        """the lane code of csrc/h2c_suites.hpp on raw words: a uint32 [n, 24] -> uint32 [n, 24] (ncg_h2c_check)"""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 24)
+        out = np.zeros_like(a)
+        if a.shape[0]:
+            self._check(self.lib.ncg_h2c_check(self.h, op, a.shape[0], a.ctypes.data, out.ctypes.data))
+        return out
 
     @staticmethod
     def _ntt_flags(inverse, brp_input, brp_output):

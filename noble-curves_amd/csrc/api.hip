@@ -381,6 +381,7 @@ void ncg_destroy(ncg_ctx* ctx) {
   if (ctx->poly_ws) (void)hipFree(ctx->poly_ws);
   if (ctx->rist_ws) (void)hipFree(ctx->rist_ws);
   if (ctx->oprf_ws) (void)hipFree(ctx->oprf_ws);
+  if (ctx->h2c_ws) (void)hipFree(ctx->h2c_ws);
   if (ctx->pair_ws) (void)hipFree(ctx->pair_ws);
   if (ctx->bls_ws) (void)hipFree(ctx->bls_ws);
   (void)ncg_comm_destroy(ctx);
@@ -3026,6 +3027,142 @@ int ncg_oprf_check(ncg_ctx* ctx, int op, int variant, size_t n, const void* a, c
   const int o = hc.out(out, n * (wo ? wo : 8) * 4, true);
   if (int rc = hc.stage()) return rc;
   if (wo) NCG_HIP(ctx, ncg::oprf_check(op, variant, hc.dev<const uint32_t>(da), hc.dev<const uint32_t>(db), hc.dev<uint32_t>(o), (int)n, ctx->stream));
+  return hc.finish(NCG_OK);
+}
+
+// ---- RFC 9380 hash-to-curve for secp256k1 and edwards25519 (h2c_suites.hip).  The hand-offs of a call live in ctx->h2c_ws, never in
+// ctx->scratch (the host forms stage there).  The limits and the DST rules are xmd_rule's; nothing here is secret, nothing is cleared.
+static Rule h2c_rule(ncg_ctx* ctx, const char* op, int suite, int count, size_t n, const void* dst, size_t dst_len,
+                     std::initializer_list<const void*> word_rows) {
+  if (suite != NCG_H2C_SECP256K1_XMD_SHA256_SSWU && suite != NCG_H2C_EDWARDS25519_XMD_SHA512_ELL2)
+    return {op, set_err(ctx, NCG_ERR_UNSUPPORTED, "noble-gpu: %s: unsupported suite %d", op, suite)};
+  if (count != NCG_H2C_NU && count != NCG_H2C_RO) return {op, set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: count must be 1 or 2", op)};
+  return xmd_rule(ctx, op, n, dst, dst_len, 48 * (size_t)count, word_rows);
+}
+// the maps take no DST
+static Rule h2c_map_rule(ncg_ctx* ctx, int suite, int count, size_t n, std::initializer_list<const void*> word_rows) {
+  static const uint8_t none[1] = {0};
+  return h2c_rule(ctx, "h2c_map_batch", suite, count, n, none, 1, word_rows);
+}
+static int h2c_ws(ncg_ctx* ctx, size_t bytes, hipStream_t st, uint8_t** ws) {
+  if (int rc = ncg_grow_buf(ctx, &ctx->h2c_ws, &ctx->h2c_ws_bytes, bytes, bytes + (bytes >> 2) + 4096, GrowWait::device)) return rc;
+  *ws = (uint8_t*)ctx->h2c_ws;
+  return NCG_OK;
+}
+
+int ncg_h2c_hash_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                           size_t dst_len, void* out_affine_dev, uint8_t* out_is_inf_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_batch", suite, count, n, dst, dst_len, {out_affine_dev}), n, msg_off_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c_suites_ws_bytes(suite, n, count), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c_suites_hash(suite, (const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, count,
+                                    (uint32_t*)out_affine_dev, out_is_inf_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_h2c_hash_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                       void* out_affine, uint8_t* out_is_inf) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_batch", suite, count, n, dst, dst_len, {}), n, msg_off, out_affine, out_is_inf);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "h2c_hash_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out_affine, n * 64), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_h2c_hash_batch_dev(ctx, suite, n, count, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o),
+                                          hc.dev<uint8_t>(f), ctx->stream));
+}
+int ncg_h2c_map_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* u48_dev, void* out_affine_dev, uint8_t* out_is_inf_dev,
+                          void* stream) {
+  NCG_BEGIN(ctx, h2c_map_rule(ctx, suite, count, n, {u48_dev, out_affine_dev}), n, u48_dev, out_affine_dev, out_is_inf_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c_suites_ws_bytes(suite, n, count), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c_suites_map(suite, (const uint32_t*)u48_dev, 12, count, (uint32_t*)out_affine_dev, out_is_inf_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_h2c_map_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* u48, void* out_affine, uint8_t* out_is_inf) {
+  NCG_BEGIN(ctx, h2c_map_rule(ctx, suite, count, n, {}), n, u48, out_affine, out_is_inf);
+  HostCall hc(ctx);
+  const int in = hc.in(u48, n * (size_t)count * 48);
+  const int o = hc.out(out_affine, n * 64), f = hc.out(out_is_inf, n);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_h2c_map_batch_dev(ctx, suite, n, count, hc.dev(in), hc.dev(o), hc.dev<uint8_t>(f), ctx->stream));
+}
+int ncg_h2c_hash_to_scalar_batch_dev(ncg_ctx* ctx, int suite, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                     size_t dst_len, void* out32_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_to_scalar_batch", suite, 1, n, dst, dst_len, {out32_dev}), n, msg_off_dev, out32_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c_suites_ws_bytes(suite, n, 1), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c_suites_hash_to_scalar(suite, (const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len,
+                                              (uint32_t*)out32_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_h2c_hash_to_scalar_batch(ncg_ctx* ctx, int suite, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                 void* out32) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_to_scalar_batch", suite, 1, n, dst, dst_len, {}), n, msg_off, out32);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "h2c_hash_to_scalar_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out32, n * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_h2c_hash_to_scalar_batch_dev(ctx, suite, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o), ctx->stream));
+}
+int ncg_h2c_hash_to_field_batch_dev(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev,
+                                    const void* dst, size_t dst_len, void* out_u_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_to_field_batch", suite, count, n, dst, dst_len, {out_u_dev}), n, msg_off_dev, out_u_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c_suites_ws_bytes(suite, n, count), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c_suites_hash_to_field(suite, (const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, count,
+                                             (uint32_t*)out_u_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_h2c_hash_to_field_batch(ncg_ctx* ctx, int suite, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                size_t dst_len, void* out_u) {
+  NCG_BEGIN(ctx, h2c_rule(ctx, "h2c_hash_to_field_batch", suite, count, n, dst, dst_len, {}), n, msg_off, out_u);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "h2c_hash_to_field_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out_u, n * (size_t)count * 32);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_h2c_hash_to_field_batch_dev(ctx, suite, n, count, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o),
+                                                   ctx->stream));
+}
+int ncg_xmd_sha256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst, size_t dst_len,
+                             size_t out_len, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "xmd_sha256_batch", n, dst, dst_len, out_len, {}), n, msg_off_dev, out_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, 256, st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c_xmd_sha256_batch((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, (uint32_t)out_len,
+                                         (uint8_t*)out_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_xmd_sha256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len, size_t out_len,
+                         void* out) {
+  NCG_BEGIN(ctx, xmd_rule(ctx, "xmd_sha256_batch", n, dst, dst_len, out_len, {}), n, msg_off, out);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "xmd_sha256_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out, n * out_len);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_xmd_sha256_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, out_len, hc.dev(o), ctx->stream));
+}
+// The pieces of h2c_suites.hpp on raw words, in the style of ncg_oprf_check: rows of 24 words in and out
+int ncg_h2c_check(ncg_ctx* ctx, int op, size_t n, const void* a, void* out) {
+  const Rule rule = {"h2c_check", !ctx || n <= (1u << 24) ? NCG_OK
+                                      : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: h2c_check: batch too large (max 2^24)")};
+  NCG_BEGIN(ctx, rule, n, a, out);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * 96);
+  const int o = hc.out(out, n * 96, true);
+  if (int rc = hc.stage()) return rc;
+  NCG_HIP(ctx, ncg::h2c_check(op, hc.dev<const uint32_t>(da), hc.dev<uint32_t>(o), (int)n, ctx->stream));
   return hc.finish(NCG_OK);
 }
 

@@ -85,6 +85,10 @@ struct ncg_ctx {
   // rows of the proof calls - it holds secrets during a call and is cleared on the call's stream before the call returns
   void* oprf_ws = nullptr;
   size_t oprf_ws_bytes = 0;
+  // RFC 9380 suites for secp256k1 and edwards25519 (h2c_suites.hip): DST', the uniform bytes, the reduced elements and the mapped points
+  // of one call: one call at a time per context, on whatever stream
+  void* h2c_ws = nullptr;
+  size_t h2c_ws_bytes = 0;
   // pairings (pairing.hip): the verdict word, the group offsets and one Miller value per pair; one call at a time
   void* pair_ws = nullptr;
   size_t pair_ws_bytes = 0;

@@ -384,6 +384,32 @@ uint8_t oprf_evaluate_host(int mode, const uint8_t* input, uint64_t len, const u
                            int invert, uint8_t* out64);
 void oprf_composite_host(int mode, const uint8_t* B32, const uint32_t* C, const uint32_t* D, uint32_t* out, uint8_t* status, int n);
 
+// RFC 9380 hash-to-curve for secp256k1 and edwards25519 (h2c_suites.hip).  suite: 0 secp256k1_XMD:SHA-256_SSWU, 1
+// edwards25519_XMD:SHA-512_ELL2; count: 1 (encodeToCurve, mapToCurve) or 2 (hashToCurve) field elements per row.  Messages are a blob
+// with n + 1 offsets; dst_host is a HOST pointer (1..255 bytes); u: n * count elements of in_words words (12: 48 bytes, any value;
+// 8: reduced); out: affine wire points of the curve (16 words) and their ZERO flags.  ws: h2c_suites_ws_bytes(suite, n, count) bytes
+// of device memory (256 for h2c_xmd_sha256_batch).
+size_t h2c_suites_ws_bytes(int suite, size_t n, int count);
+hipError_t h2c_suites_map(int suite, const uint32_t* u, int in_words, int count, uint32_t* out, uint8_t* inf, int n, uint8_t* ws,
+                          hipStream_t st);
+hipError_t h2c_suites_hash_to_field(int suite, const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, int count,
+                                    uint32_t* out_u, int n, uint8_t* ws, hipStream_t st);
+hipError_t h2c_suites_hash(int suite, const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, int count,
+                           uint32_t* out, uint8_t* inf, int n, uint8_t* ws, hipStream_t st);
+hipError_t h2c_suites_hash_to_scalar(int suite, const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len,
+                                     uint32_t* out, int n, uint8_t* ws, hipStream_t st);
+hipError_t h2c_xmd_sha256_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t out_len,
+                                uint8_t* out, int n, uint8_t* ws, hipStream_t st);
+// the pieces of h2c_suites.hpp on raw words (ncg_h2c_check): 24 words per row of a and out; an unknown op writes nothing
+hipError_t h2c_check(int op, const uint32_t* d_a, uint32_t* d_out, int n, hipStream_t st);
+// one row each on the CPU; dst as the caller gave it (the twin appends the length byte); -1 for an unknown suite or op
+void h2c_xmd_sha256_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out);
+int h2c_hash_to_field_host(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out_u);
+int h2c_hash_to_scalar_host(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out8);
+int h2c_map_host(int suite, const uint32_t* u, int in_words, int count, uint32_t* out, uint8_t* inf);
+int h2c_hash_host(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out, uint8_t* inf);
+int h2c_check_host(int op, const uint32_t* a, uint32_t* out);
+
 // bls12-381 pairings (pairing.hip).  ws: PAIRING_WS_WORDS words per pair; off: n_groups + 1 ascending pair offsets (device);
 // first_bad: one 64-bit word, all ones or (index << 8 | PairingBad code) of the first refused pair after pairing_miller;
 // pairing_finish multiplies each group's Miller values (largest_group decides the number of passes), exponentiates and stores

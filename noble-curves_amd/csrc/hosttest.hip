@@ -31,6 +31,7 @@
 #include "secp256k1_sign.hip"
 #include "ed448_sign.hip"
 #include "oprf.hip"
+#include "h2c_suites.hip"
 
 using namespace ncg;
 
@@ -585,6 +586,32 @@ int ht_ristretto_consts(uint32_t* out32) {
   fe9_to_wire(out32 + 24, RistrettoConsts::d_minus_one_sq());
   return 0;
 }
+
+// RFC 9380 for secp256k1 (suite 0) and edwards25519 (suite 1) on the CPU twins of h2c_suites.hip, one row per call: dst as the caller
+// has it (1..255 bytes), count 1 or 2, u as count elements of 12 LE words, points as affine wire (16 words) and a ZERO flag; -1 for an
+// argument outside these.  ht_h2c_check: the pieces of ncg_h2c_check (24 words in and out), -1 for an unknown op.
+int ht_h2c_xmd_sha256(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out) {
+  if (dst_len < 1 || dst_len > 255 || out_len < 1 || out_len > 256) return -1;
+  h2c_xmd_sha256_host(msg, len, dst, dst_len, out_len, out);
+  return 0;
+}
+int ht_h2c_hash_to_field(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out_u) {
+  if (dst_len < 1 || dst_len > 255 || (count != 1 && count != 2)) return -1;
+  return h2c_hash_to_field_host(suite, msg, len, dst, dst_len, count, out_u);
+}
+int ht_h2c_hash_to_scalar(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out8) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  return h2c_hash_to_scalar_host(suite, msg, len, dst, dst_len, out8);
+}
+int ht_h2c_map(int suite, const uint32_t* u, int count, uint32_t* out, uint8_t* inf) {
+  if (count != 1 && count != 2) return -1;
+  return h2c_map_host(suite, u, 12, count, out, inf);
+}
+int ht_h2c_hash(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out, uint8_t* inf) {
+  if (dst_len < 1 || dst_len > 255 || (count != 1 && count != 2)) return -1;
+  return h2c_hash_host(suite, msg, len, dst, dst_len, count, out, inf);
+}
+int ht_h2c_check(int op, const uint32_t* a, uint32_t* out) { return h2c_check_host(op, a, out); }
 
 // The ristretto255 OPRF on the CPU twins of oprf.hip, one row per call unless n is given: elements and scalars 8 LE words, outputs 64
 // bytes, dst as the caller has it (1..255 bytes, -1 otherwise), flags as ncg_oprf_mul_batch without ONE_SCALAR.  The row functions

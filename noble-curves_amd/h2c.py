@@ -4,13 +4,17 @@ src/abstract/hash-to-curve.ts:441-548; suite options src/bls12-381.ts:305-313, :
 batch forms the GPU needs.  The shim does the byte hashing exactly as the reference does
 (expand_message_xmd over SHA-256, hash_to_field: :189-228, :312-378, here with hashlib); all
 field and curve arithmetic runs in `libncg.so` (`ncg_map_to_curve_batch`).
+
+`secp256k1_hasher` (src/secp256k1.ts:330-428) and `ed25519_hasher` (src/ed25519.ts:294-405) are the same surface with the
+hashing on the device as well (`ncg_h2c_hash_batch`, `ncg_h2c_map_batch`, `ncg_h2c_hash_to_scalar_batch`): the shim checks the
+arguments the way the reference does, hashes an oversize DST, and makes one call per batch.
 """
 import hashlib
 
 import numpy as np
 
 from . import curve as _curve
-from ._native import BLS12_381_G1, BLS12_381_G2, get_engine
+from ._native import BLS12_381_G1, BLS12_381_G2, H2C_EDWARDS25519, H2C_SECP256K1, get_engine
 
 _P = _curve.bls12_381_G1_Point.Fp.ORDER
 
@@ -128,3 +132,98 @@ class H2CHasher:
 
 bls12_381_G1_hasher = H2CHasher(_curve.bls12_381_G1_Point, BLS12_381_G1, 1, "BLS_SIG_BLS12381G1_XMD:SHA-256_SSWU_RO_NUL_")
 bls12_381_G2_hasher = H2CHasher(_curve.bls12_381_G2_Point, BLS12_381_G2, 2, "BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_NUL_")
+
+
+def _msg_bytes(x):
+    """abytes(msg) of hash_to_field (hash-to-curve.ts:325): bytes only, a string is refused like any other type"""
+    if isinstance(x, str):
+        raise TypeError('"msg" expected Uint8Array, got type=str')
+    return _bytes(x, "msg")
+
+
+def _norm_dst(DST, H):
+    """normDST (hash-to-curve.ts:160-167) and the oversize rule of expand_message_xmd (:202), which the device leaves to its caller"""
+    if not isinstance(DST, (str, bytes, bytearray, memoryview)):
+        raise TypeError("DST must be Uint8Array or ascii string")
+    dst = DST.encode("ascii") if isinstance(DST, str) else bytes(DST)
+    if len(dst) == 0:
+        raise ValueError("DST must be non-empty")
+    if len(dst) > 255:
+        dst = H(b"H2C-OVERSIZE-DST-" + dst).digest()
+    return dst
+
+
+class H2CSuiteHasher:
+    """createHasher(Point, mapToCurve, defaults) (hash-to-curve.ts:441-530) for a suite that runs on the device from the message
+    bytes on: m = 1, k = 128, expand = 'xmd'.  The `*Batch` forms take lists and make one call into the library each."""
+
+    def __init__(self, Point, suite, DST, encodeDST, hash_name, engine=None):
+        self.Point, self._suite, self._engine = Point, suite, engine
+        self._H = getattr(hashlib, hash_name)
+        self._defaults = {"DST": DST, "encodeDST": encodeDST, "p": Point.Fp.ORDER, "m": 1, "k": 128, "expand": "xmd", "hash": hash_name}
+
+    @property
+    def defaults(self):
+        """a fresh copy: changing it does not reach the hasher (createHasher's snapshot, :451-463, :482-484)"""
+        return dict(self._defaults)
+
+    def _dst(self, options, default):
+        """dstOverride (:467-468): only DST may be overridden per call"""
+        DST = default
+        if options is not None and options.get("DST") is not None:
+            DST = options["DST"]
+        return _norm_dst(DST, self._H)
+
+    def _eng(self):
+        return self._engine or get_engine()
+
+    def _points(self, out, inf):
+        return [self.Point._from_wire(out[i], bool(inf[i])) for i in range(out.shape[0])]
+
+    # ---- batch forms -------------------------------------------------------------------------
+    def hashToCurveBatch(self, msgs, options=None):
+        dst = self._dst(options, self._defaults["DST"])
+        msgs = [_msg_bytes(m) for m in msgs]
+        return self._points(*self._eng().h2c_hash_batch(self._suite, msgs, dst, 2)) if msgs else []
+
+    def encodeToCurveBatch(self, msgs, options=None):
+        dst = self._dst(options, self._defaults["encodeDST"])
+        msgs = [_msg_bytes(m) for m in msgs]
+        return self._points(*self._eng().h2c_hash_batch(self._suite, msgs, dst, 1)) if msgs else []
+
+    def mapToCurveBatch(self, scalars_list):
+        p = self._defaults["p"]
+        raw = bytearray()
+        for u in scalars_list:
+            if not isinstance(u, int) or isinstance(u, bool):
+                raise ValueError("expected bigint (m=1)")
+            raw += (u % p).to_bytes(48, "little")               # Fp.create (secp256k1.ts:412; ed25519.ts: Fp ops reduce)
+        if not raw:
+            return []
+        return self._points(*self._eng().h2c_map_batch(self._suite, np.frombuffer(bytes(raw), dtype=np.uint8).reshape(-1, 48), 1))
+
+    def hashToScalarBatch(self, msgs, options=None):
+        dst = self._dst(options, "HashToScalar-")                # _DST_scalar (:412, :523)
+        msgs = [_msg_bytes(m) for m in msgs]
+        if not msgs:
+            return []
+        out = self._eng().h2c_hash_to_scalar_batch(self._suite, msgs, dst)
+        return [int.from_bytes(bytes(out[i]), "little") for i in range(len(msgs))]
+
+    # ---- the reference's single-call forms -----------------------------------------------------
+    def hashToCurve(self, msg, options=None):
+        return self.hashToCurveBatch([msg], options)[0]
+
+    def encodeToCurve(self, msg, options=None):
+        return self.encodeToCurveBatch([msg], options)[0]
+
+    def mapToCurve(self, scalars):
+        return self.mapToCurveBatch([scalars])[0]
+
+    def hashToScalar(self, msg, options=None):
+        return self.hashToScalarBatch([msg], options)[0]
+
+
+secp256k1_hasher = H2CSuiteHasher(_curve.secp256k1_Point, H2C_SECP256K1, "secp256k1_XMD:SHA-256_SSWU_RO_", "secp256k1_XMD:SHA-256_SSWU_NU_", "sha256")
+ed25519_hasher = H2CSuiteHasher(_curve.ed25519_Point, H2C_EDWARDS25519, "edwards25519_XMD:SHA-512_ELL2_RO_", "edwards25519_XMD:SHA-512_ELL2_NU_",
+                                "sha512")

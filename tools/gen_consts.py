@@ -344,6 +344,52 @@ def main():
     out += arr28("SQRT_MINUS_D", sqrt_minus_d) + arr28("INVSQRT_MINUS_D", invsqrt_minus_d)
     out += arr28("BASE_X", dbx) + arr28("BASE_Y", dby)
     out += "};\n\n"
+    # RFC 9380 suites for secp256k1 and edwards25519 (h2c_suites.hpp), plain residues in the radix-2^29 form of fe9.hpp.
+    # secp256k1 (RFC 9380 section 8.7, appendix E.1; src/secp256k1.ts:345-401): E' : y^2 = x^3 + A' x + B', Z = -11 and the 3-isogeny
+    # E' -> E, coefficients in ascending degree.  C2 = sqrt(-Z) of sqrt_ratio_3mod4 (either root: SWU fixes the sign of y afterwards).
+    swu_a = 0x3f8731abdd661adca08a5558f0f5d272e953d363cb6f0e5d405447c01a444533
+    swu_b, swu_z = 1771, kp - 11
+    iso = {
+        "XNUM": [0x8e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38daaaaa8c7,
+                 0x7d3d4c80bc321d5b9f315cea7fd44c5d595d2fc0bf63b92dfff1044f17c6581,
+                 0x534c328d23f234e6e2a413deca25caece4506144037c40314ecbd0b53d9dd262,
+                 0x8e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38e38daaaaa88c],
+        "XDEN": [0xd35771193d94918a9ca34ccbb7b640dd86cd409542f8487d9fe6b745781eb49b,
+                 0xedadc6f64383dc1df7c4b2d51b54225406d36b641f5e41bbc52a56612a8c6d14, 1],
+        "YNUM": [0x4bda12f684bda12f684bda12f684bda12f684bda12f684bda12f684b8e38e23c,
+                 0xc75e0c32d5cb7c0fa9d0a54b12a0a6d5647ab046d686da6fdffc90fc201d71a3,
+                 0x29a6194691f91a73715209ef6512e576722830a201be2018a765e85a9ecee931,
+                 0x2f684bda12f684bda12f684bda12f684bda12f684bda12f684bda12f38e38d84],
+        "YDEN": [0xfffffffffffffffffffffffffffffffffffffffffffffffffffffffefffff93b,
+                 0x7a06534bb8bdb49fd5e9e6632722c2989467c1bfc8e8d978dfb425d2685c2573,
+                 0x6484aa716545ca2cf3a70c3fa8fe337e0a3d21162f0d6299a7bf8192bfd2a76f, 1],
+    }
+    assert kp % 4 == 3 and pow(swu_z, (kp - 1) // 2, kp) == kp - 1                     # Z is a non-square
+    swu_c2 = pow(11, (kp + 1) // 4, kp)
+    assert swu_c2 * swu_c2 % kp == 11
+    # the isogeny carries E' to y^2 = x^3 + 7: checked on the image of one point of E'
+    xe = 1
+    while pow((xe ** 3 + swu_a * xe + swu_b) % kp, (kp - 1) // 2, kp) != 1:
+        xe += 1
+    ye = pow((xe ** 3 + swu_a * xe + swu_b) % kp, (kp + 1) // 4, kp)
+    ev = {k: sum(c * pow(xe, i, kp) for i, c in enumerate(v)) % kp for k, v in iso.items()}
+    xi, yi = ev["XNUM"] * pow(ev["XDEN"], -1, kp) % kp, ye * ev["YNUM"] * pow(ev["YDEN"], -1, kp) % kp
+    assert (yi * yi - xi ** 3 - 7) % kp == 0
+    out += "// RFC 9380 suite secp256k1_XMD:SHA-256_SSWU_RO_ (h2c_suites.hpp): 9 limbs in radix 2^29, plain residues\nstruct SecpH2c {\n"
+    for k, rows in iso.items():
+        out += "  static constexpr int ISO_%s_N = %d;\n" % (k, len(rows))
+        out += "  static constexpr uint32_t ISO_%s[%d][9] = {\n%s\n  };\n" % (
+            k, len(rows), ",\n".join("    {%s}" % ", ".join("0x%08xu" % l for l in limbs29(v % kp, 9)) for v in rows))
+    out += arr29("SWU_A", swu_a, 9) + arr29("SWU_B", swu_b, 9) + arr29("SWU_Z", swu_z, 9) + arr29("SWU_C2", swu_c2, 9)
+    out += "};\n\n"
+    # edwards25519 (RFC 9380 appendix G.2.1, G.2.2; src/ed25519.ts:294-379): J = 486662, c2 = 2^((p + 3) / 8), c3 = sqrt(-1) (the
+    # field's SQRT_M1: either root, the sign of y is fixed afterwards) and the EVEN root c1 of -(J + 2) of the map to Edwards form
+    ell2_c2 = pow(2, (ep + 3) // 8, ep)
+    ell2_c1_edwards = ed_sqrt_even(-486664)
+    assert ell2_c1_edwards % 2 == 0 and ell2_c1_edwards ** 2 % ep == (-486664) % ep
+    out += "// RFC 9380 suite edwards25519_XMD:SHA-512_ELL2_RO_ (h2c_suites.hpp): 9 limbs in radix 2^29, plain residues\nstruct EdH2c {\n"
+    out += arr29("ELL2_J", 486662, 9) + arr29("ELL2_C2", ell2_c2, 9) + arr29("ELL2_C1_EDWARDS", ell2_c1_edwards, 9)
+    out += "};\n\n"
     out += "}  // namespace ncg\n"
     with open(OUT, "w") as f:
         f.write(out)
