@@ -619,6 +619,48 @@ static napi_value H2c(napi_env env, napi_callback_info info) {
   return res;
 }
 
+// RFC 9380 for edwards448 and the hash side of decaf448 (ncg_ed448_h2c_*, ncg_decaf448_hash_to_*): h2c448(op, count, msgs, lens, dst).
+// Messages travel as for h2c(); dst is 1..255 bytes (the shim compresses an oversize one).
+//   op 0 ed448 hashToCurve (count 2) / encodeToCurve (count 1)  -> n x 112 bytes, affine x || y little-endian, ZERO as (0, 1)
+//   op 1 ed448 hashToScalar   op 2 decaf448 hashToCurve (the encoded element)   op 3 decaf448 hashToScalar   -> n x 56 (count ignored)
+static napi_value H2c448(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_OK(napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  if (!need_ctx(env)) return nullptr;
+  int32_t op, count;
+  uint8_t *a = nullptr, *b = nullptr, *c = nullptr, *out;
+  size_t al = 0, bl = 0, cl = 0;
+  if (argc < 5 || napi_get_value_int32(env, argv[0], &op) != napi_ok || op < 0 || op > 3 || napi_get_value_int32(env, argv[1], &count) != napi_ok ||
+      !get_u8(env, argv[2], &a, &al) || !get_u8(env, argv[3], &b, &bl) || !get_u8(env, argv[4], &c, &cl)) {
+    napi_throw_type_error(env, nullptr, "noble-gpu: h2c448(op, count, msgs, lens, dst)");
+    return nullptr;
+  }
+  const size_t n = bl / 4;
+  std::vector<uint64_t> off(n + 1, 0);
+  bool good = bl % 4 == 0;
+  for (size_t i = 0; good && i < n; i++) {
+    uint32_t len;
+    memcpy(&len, b + 4 * i, 4);
+    off[i + 1] = off[i] + len;
+  }
+  if (!good || off[n] != al) {
+    napi_throw_error(env, nullptr, "noble-gpu: h2c448: the rows do not match");
+    return nullptr;
+  }
+  napi_value res = make_u8(env, n * (op == 0 ? 112 : 56), &out);
+  if (!res) return nullptr;
+  const void* msgs = al ? a : nullptr;
+  int rc = 0;
+  if (n == 0) rc = 0;
+  else if (op == 0) rc = ncg_ed448_h2c_hash_batch(g_ctx, n, count, msgs, off.data(), c, cl, out);
+  else if (op == 1) rc = ncg_ed448_h2c_hash_to_scalar_batch(g_ctx, n, msgs, off.data(), c, cl, out);
+  else if (op == 2) rc = ncg_decaf448_hash_to_group_batch(g_ctx, n, msgs, off.data(), c, cl, out);
+  else rc = ncg_decaf448_hash_to_scalar_batch(g_ctx, n, msgs, off.data(), c, cl, out);
+  if (rc != 0) return throw_native(env);
+  return res;
+}
+
 // decaf448 on packed rows (ncg_decaf448_*): one entry, the operation chosen by `mode` (see the list at the top of this file).
 static napi_value Decaf448(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -1338,7 +1380,7 @@ NAPI_MODULE_INIT() {
     napi_callback fn;
   } fns[] = {{"init", Init},           {"initMulti", InitMulti}, {"msm", Msm},
              {"mulVarBatch", MulVarBatch}, {"mulBaseBatch", MulBaseBatch},
-             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"oprf", Oprf}, {"h2c", H2c}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
+             {"ed25519VerifyBatch", Ed25519VerifyBatch}, {"x25519", X25519}, {"ed25519Sign", Ed25519Sign}, {"secpSign", SecpSign}, {"ed448", Ed448}, {"ed448Sign", Ed448Sign}, {"ristretto", Ristretto}, {"oprf", Oprf}, {"h2c", H2c}, {"h2c448", H2c448}, {"decaf448", Decaf448},{"bls", Bls}, {"pointBytes", PointBytes},
              {"decodePoints", DecodePoints}, {"encodePoints", EncodePoints},
              {"aggregateEncoded", AggregateEncoded},
              {"ntt", Ntt},               {"poly", Poly},             {"mapToCurve", MapToCurve},

@@ -1156,6 +1156,61 @@ function h2cHasher(name) {
 }
 const secp256k1_hasher = h2cHasher('secp256k1'), ed25519_hasher = h2cHasher('ed25519');
 
+// ---- RFC 9380 for edwards448 and decaf448: ed448_hasher (src/ed448.ts:408-417) under createHasher, and the hash side of
+// decaf448_hasher (:662-701), with expand_message_xof over SHAKE256, the maps and the group law on the device (ncg_ed448_h2c_hash_batch,
+// ncg_ed448_h2c_hash_to_scalar_batch, ncg_decaf448_hash_to_group_batch, ncg_decaf448_hash_to_scalar_batch).  Every batch form makes one
+// native call.  Ed448 points come back as affine { x, y } of bigints, ZERO as (0, 1), or through opts.Point.fromAffine; decaf448
+// elements as their 56-byte encodings.
+const H2C448 = { DST: 'edwards448_XOF:SHAKE256_ELL2_RO_', encodeDST: 'edwards448_XOF:SHAKE256_ELL2_NU_' };
+function h2c448Dst(DST, k) {        // normDST and the oversize rule of expand_message_xof (:263-266): ceil(2 k / 8) bytes of SHAKE256
+  if (!(DST instanceof Uint8Array) && typeof DST !== 'string') throw new Error('DST must be Uint8Array or ascii string');
+  let dst = typeof DST === 'string' ? Uint8Array.from(Buffer.from(DST, 'ascii')) : DST;
+  if (dst.length === 0) throw new Error('DST must be non-empty');
+  if (dst.length > 255)
+    dst = new Uint8Array(crypto.createHash('shake256', { outputLength: Math.ceil((2 * k) / 8) }).update('H2C-OVERSIZE-DST-', 'ascii').update(dst).digest());
+  return dst;
+}
+function h2c448Call(op, count, msgs, dst, width) {
+  const n = h2cMsgs(msgs).length;
+  if (n === 0) return [];
+  init();
+  const { blob, lens } = oprfBlob(msgs);
+  const out = native.h2c448(op, count, blob, lens, dst);
+  return Array.from({ length: n }, (_, i) => out.subarray(width * i, width * i + width));
+}
+function h2c448Points(msgs, opts, count) {
+  const dst = h2c448Dst(opts && opts.DST !== undefined ? opts.DST : (count === 2 ? H2C448.DST : H2C448.encodeDST), 224);
+  return h2c448Call(0, count, msgs, dst, 112).map((row) => {
+    const a = { x: leNumber(row, 0, 56), y: leNumber(row, 56, 56) };
+    return opts && opts.Point ? (a.x === 0n && a.y === 1n ? opts.Point.ZERO : opts.Point.fromAffine(a)) : a;
+  });
+}
+function h2c448Scalars(msgs, opts) {
+  const dst = h2c448Dst(opts && opts.DST !== undefined ? opts.DST : 'HashToScalar-', 224);
+  return h2c448Call(1, 1, msgs, dst, 56).map((row) => leNumber(row, 0, 56));
+}
+const ed448HashToCurveBatch = (msgs, opts) => h2c448Points(msgs, opts, 2);
+const ed448EncodeToCurveBatch = (msgs, opts) => h2c448Points(msgs, opts, 1);
+// decaf448_hasher.hashToCurve(msg, { DST }).toBytes() for every message
+function decaf448HashToCurveBatch(msgs, opts) {
+  const dst = h2c448Dst(opts && opts.DST !== undefined ? opts.DST : 'decaf448_XOF:SHAKE256_D448MAP_RO_', 224);
+  return h2c448Call(2, 1, msgs, dst, 56).map((row) => Uint8Array.from(row));
+}
+// decaf448_hasher.hashToScalar: k = 256, so an oversize DST is compressed to 64 bytes (ed448.ts:677)
+function decaf448HashToScalarBatch(msgs, opts) {
+  const dst = h2c448Dst(opts && opts.DST !== undefined ? opts.DST : 'HashToScalar-', 256);
+  return h2c448Call(3, 1, msgs, dst, 56).map((row) => leNumber(row, 0, 56));
+}
+const ed448_hasher = Object.freeze({
+  get defaults() { return { DST: H2C448.DST, encodeDST: H2C448.encodeDST, p: ED448_P, m: 1, k: 224, expand: 'xof', hash: 'shake256' }; },
+  hashToCurve: (msg, opts) => h2c448Points([msg], opts, 2)[0],
+  encodeToCurve: (msg, opts) => h2c448Points([msg], opts, 1)[0],
+  hashToScalar: (msg, opts) => h2c448Scalars([msg], opts)[0],
+  hashToCurveBatch: (msgs, opts) => h2c448Points(msgs, opts, 2),
+  encodeToCurveBatch: (msgs, opts) => h2c448Points(msgs, opts, 1),
+  hashToScalarBatch: (msgs, opts) => h2c448Scalars(msgs, opts),
+});
+
 function oprfMode(mode, info) {
   const m = mode === 2 ? leNumber(oprfHashToScalar(Buffer.concat([Buffer.from('Info', 'ascii'), Buffer.from([info.length >> 8, info.length & 255]), info]),
     Buffer.concat([Buffer.from('HashToScalar-', 'ascii'), oprfCtx(2)])), 0, 32) : 0n;
@@ -1664,5 +1719,6 @@ module.exports = { CURVE, init, initMulti, register, install, uninstall, STATS, 
                    ristrettoDeriveToCurve, ristretto255_oprf,
                    secp256k1HashToCurveBatch, secp256k1EncodeToCurveBatch, ed25519HashToCurveBatch, ed25519EncodeToCurveBatch, hashToScalarBatch,
                    secp256k1_hasher, ed25519_hasher,
+                   ed448_hasher, ed448HashToCurveBatch, ed448EncodeToCurveBatch, decaf448HashToCurveBatch, decaf448HashToScalarBatch,
                    decaf448FromBytesBatch, decaf448ToBytesBatch, decaf448EqualsBatch, decaf448MultiplyBatch, decaf448MultiplyBaseBatch,
                    decaf448DeriveToCurveBatch, native };

@@ -863,6 +863,63 @@ int ncg_decaf448_mul_batch_dev(ncg_ctx* ctx, size_t n, const void* enc56_dev, co
 int ncg_decaf448_mul_base_batch(ncg_ctx* ctx, size_t n, const void* k56, void* out56);
 int ncg_decaf448_mul_base_batch_dev(ncg_ctx* ctx, size_t n, const void* k56_dev, void* out56_dev, void* stream);
 
+/* ---- RFC 9380 for edwards448 and decaf448: ed448_hasher (src/ed448.ts:313-417) and the hash side of decaf448_hasher (:662-701) ----
+ * edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_: m = 1, k = 224, L = 84, expand_message_xof over SHAKE256 (hash-to-curve.ts:252-286), all of
+ * it on the device.  Messages are one blob with n + 1 non-decreasing offsets (msgs may be NULL only when every message is empty).
+ * dst is a HOST pointer in both forms, 1 <= dst_len <= 255, anything else returns NCG_ERR_INVALID_ARG: the caller compresses an
+ * oversize DST (SHAKE256("H2C-OVERSIZE-DST-" || DST, ceil(2 k / 8)): 56 bytes for k = 224, 64 for decaf448's hashToScalar, k = 256).
+ * count: NCG_H2C_RO (2, hashToCurve) or NCG_H2C_NU (1, encodeToCurve / mapToCurve); anything else returns NCG_ERR_INVALID_ARG.
+ * Rows of words (u56, out_u56, out56, out_affine112) are read and written as 32-bit words: a DEVICE pointer to them must be 4-byte
+ * aligned and is refused, not dereferenced, otherwise; host pointers may sit at any address.  n = 0 returns NCG_OK and touches
+ * nothing; n >= 2^31 is refused before any buffer is read.  Nothing here is secret.  The hand-offs of a call (the staged DST, the
+ * uniform bytes, the reduced elements) live in a workspace of the context: ONE CALL AT A TIME per context, on whatever stream.
+ *
+ * ncg_xof_shake256_batch: out[i] = expand_message_xof(msg i, dst, out_len) over SHAKE256 =
+ *   SHAKE256(msg || I2OSP(out_len, 2) || dst || I2OSP(dst_len, 1), out_len), out_len bytes per row, 1 <= out_len <= 65535.
+ * ncg_ed448_h2c_hash_batch: hashToCurve (count 2) / encodeToCurve (count 1) from messages: hash_to_field, the Elligator 2 map to
+ *   curve448 and on to edwards448 (ed448.ts:320-394), the sum of the images, the cofactor 4, the canonical affine x || y, 56
+ *   little-endian bytes each.  The identity is written as (0, 1); there is no flag byte (as ncg_ed448_add_pairs_batch).
+ * ncg_ed448_h2c_map_batch: the same from count field elements per row, 56 little-endian bytes each, any value below 2^448, reduced
+ *   mod p.
+ * ncg_ed448_h2c_hash_to_field_batch: hash_to_field alone: count reduced elements of 56 little-endian bytes per row.
+ * ncg_ed448_h2c_hash_to_scalar_batch: createHasher's hashToScalar (hash-to-curve.ts:520-528): 84 bytes big-endian mod the group
+ *   order n, 56 little-endian bytes.
+ * ncg_decaf448_hash_to_group_batch: decaf448_hasher.hashToCurve: expand_message_xof(112 bytes, k = 224) then deriveToCurve, the
+ *   ENCODED element (the 56 bytes ncg_decaf448_from_uniform_batch gives for the same uniform bytes).
+ * ncg_decaf448_hash_to_scalar_batch: decaf448_hasher.hashToScalar: expand_message_xof(64 bytes) little-endian mod n. */
+int ncg_xof_shake256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                           size_t out_len, void* out);
+int ncg_xof_shake256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                               size_t dst_len, size_t out_len, void* out_dev, void* stream);
+int ncg_ed448_h2c_hash_batch(ncg_ctx* ctx, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst,
+                             size_t dst_len, void* out_affine112);
+int ncg_ed448_h2c_hash_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                 size_t dst_len, void* out_affine112_dev, void* stream);
+int ncg_ed448_h2c_map_batch(ncg_ctx* ctx, size_t n, int count, const void* u56, void* out_affine112);
+int ncg_ed448_h2c_map_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* u56_dev, void* out_affine112_dev, void* stream);
+int ncg_ed448_h2c_hash_to_field_batch(ncg_ctx* ctx, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                      size_t dst_len, void* out_u56);
+int ncg_ed448_h2c_hash_to_field_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev,
+                                          const void* dst, size_t dst_len, void* out_u56_dev, void* stream);
+int ncg_ed448_h2c_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                       size_t dst_len, void* out56);
+int ncg_ed448_h2c_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                           size_t dst_len, void* out56_dev, void* stream);
+int ncg_decaf448_hash_to_group_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                     size_t dst_len, void* out56);
+int ncg_decaf448_hash_to_group_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                         size_t dst_len, void* out56_dev, void* stream);
+int ncg_decaf448_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                      size_t dst_len, void* out56);
+int ncg_decaf448_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                          size_t dst_len, void* out56_dev, void* stream);
+/* The lane code of csrc/h2c448.hpp on n <= 2^24 rows of RAW uint32 words (host pointers), 42 words per row of a and of out; an op
+ * reads and writes only its own width, an undefined op reads nothing and leaves out zero.  Every output element is 14 LE words,
+ * canonical.  0: the 84-byte value as 21 LE words, mod p.  1: the same value mod n.  2: 16 LE words (the 64-byte form) mod n.
+ * 3: map_to_curve_elligator2_curve448 of u (14 words, any value below 2^448): xn, xd, y.  4: map_to_curve_elligator2_edwards448
+ * of u before the cofactor: X, Y, Z of the projective point (xEn yEd : yEn xEd : xEd yEd). */
+int ncg_h2c448_check(ncg_ctx* ctx, int op, size_t n, const void* a, void* out);
+
 /* ---- measurement helpers (not on the product path) ------------------------------------ */
 /* ---- secp256k1 ECDSA batch verification --------------------------------------------------------
  * out_ok[i] = ecdsa.verify(sig[i], msgHash[i], publicKey[i], { prehash: false, format: 'compact', lowS })

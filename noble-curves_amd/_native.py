@@ -265,6 +265,21 @@ _OPTIONAL_PROTOS = {
     "ncg_xmd_sha256_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
     "ncg_xmd_sha256_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
     "ncg_h2c_check": [_vp, _i32, _sz, _vp, _vp],
+    "ncg_xof_shake256_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp],
+    "ncg_xof_shake256_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _sz, _vp, _vp],
+    "ncg_ed448_h2c_hash_batch": [_vp, _sz, _i32, _vp, _vp, _vp, _sz, _vp],
+    "ncg_ed448_h2c_hash_batch_dev": [_vp, _sz, _i32, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_ed448_h2c_map_batch": [_vp, _sz, _i32, _vp, _vp],
+    "ncg_ed448_h2c_map_batch_dev": [_vp, _sz, _i32, _vp, _vp, _vp],
+    "ncg_ed448_h2c_hash_to_field_batch": [_vp, _sz, _i32, _vp, _vp, _vp, _sz, _vp],
+    "ncg_ed448_h2c_hash_to_field_batch_dev": [_vp, _sz, _i32, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_ed448_h2c_hash_to_scalar_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ncg_ed448_h2c_hash_to_scalar_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_decaf448_hash_to_group_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ncg_decaf448_hash_to_group_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_decaf448_hash_to_scalar_batch": [_vp, _sz, _vp, _vp, _vp, _sz, _vp],
+    "ncg_decaf448_hash_to_scalar_batch_dev": [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp],
+    "ncg_h2c448_check": [_vp, _i32, _sz, _vp, _vp],
     "ncg_pairing_batch": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64)],
     "ncg_pairing_batch_dev": [_vp, _sz, _vp, _vp, _sz, _vp, _i32, _vp, _vp, ctypes.POINTER(ctypes.c_int64), _vp],
     "ncg_bls_verify_batch": [_vp, _i32, _sz, _vp, _vp, _vp, _vp],
@@ -1615,6 +1630,61 @@ class Engine:
         out = np.zeros_like(a)
         if a.shape[0]:
             self._check(self.lib.ncg_h2c_check(self.h, op, a.shape[0], a.ctypes.data, out.ctypes.data))
+        return out
+
+    # ---- RFC 9380 for edwards448 (edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_) and the hash side of decaf448: messages a list of byte
+    # strings, elements / scalars / encodings uint8 [n, 56] little-endian, points x || y uint8 [n, 112] with the identity as (0, 1) ----
+    def _h2c448_rows(self, fn, msgs, dst, width, *lead):
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, width), dtype=np.uint8)
+        if n:
+            self._check(fn(self.h, n, *lead, blob.ctypes.data if blob.size else None, off.ctypes.data, dst, len(dst), out.ctypes.data))
+        return out
+
+    def xof_shake256_batch(self, msgs, dst, out_len):
+        """expand_message_xof over SHAKE256 of every message -> uint8 [n, out_len]"""
+        blob, off = self._blob(msgs)
+        dst, n = bytes(dst), len(msgs)
+        out = np.zeros((n, out_len), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_xof_shake256_batch(self.h, n, blob.ctypes.data if blob.size else None, off.ctypes.data, dst, len(dst),
+                                                        out_len, out.ctypes.data))
+        return out
+
+    def ed448_h2c_hash_batch(self, msgs, dst, count):
+        """hashToCurve (count 2) / encodeToCurve (count 1) -> uint8 [n, 112]"""
+        return self._h2c448_rows(self.lib.ncg_ed448_h2c_hash_batch, msgs, dst, 112, count)
+
+    def ed448_h2c_map_batch(self, u56, count):
+        """u56 uint8 [n, count * 56]: count values per row, 56 bytes little-endian each, any value below 2^448 -> uint8 [n, 112]"""
+        u56 = np.ascontiguousarray(u56, dtype=np.uint8).reshape(-1, count * 56)
+        n = u56.shape[0]
+        out = np.zeros((n, 112), dtype=np.uint8)
+        if n:
+            self._check(self.lib.ncg_ed448_h2c_map_batch(self.h, n, count, u56.ctypes.data, out.ctypes.data))
+        return out
+
+    def ed448_h2c_hash_to_field_batch(self, msgs, dst, count):
+        """-> uint8 [n, count * 56]: the reduced elements, little-endian"""
+        return self._h2c448_rows(self.lib.ncg_ed448_h2c_hash_to_field_batch, msgs, dst, count * 56, count)
+
+    def ed448_h2c_hash_to_scalar_batch(self, msgs, dst):
+        return self._h2c448_rows(self.lib.ncg_ed448_h2c_hash_to_scalar_batch, msgs, dst, 56)
+
+    def decaf448_hash_to_group_batch(self, msgs, dst):
+        """decaf448_hasher.hashToCurve -> the encoded elements uint8 [n, 56]"""
+        return self._h2c448_rows(self.lib.ncg_decaf448_hash_to_group_batch, msgs, dst, 56)
+
+    def decaf448_hash_to_scalar_batch(self, msgs, dst):
+        return self._h2c448_rows(self.lib.ncg_decaf448_hash_to_scalar_batch, msgs, dst, 56)
+
+    def h2c448_check(self, op, a):
+        """the lane code of csrc/h2c448.hpp on raw words: a uint32 [n, 42] -> uint32 [n, 42] (ncg_h2c448_check)"""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 42)
+        out = np.zeros_like(a)
+        if a.shape[0]:
+            self._check(self.lib.ncg_h2c448_check(self.h, op, a.shape[0], a.ctypes.data, out.ctypes.data))
         return out
 
     @staticmethod

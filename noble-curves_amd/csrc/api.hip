@@ -3166,6 +3166,165 @@ int ncg_h2c_check(ncg_ctx* ctx, int op, size_t n, const void* a, void* out) {
   return hc.finish(NCG_OK);
 }
 
+// ---- RFC 9380 for edwards448 and decaf448 (h2c448.hip).  The hand-offs of a call live in ctx->h2c_ws like those of the 255-bit
+// suites: one call at a time per context.  Nothing here is secret, nothing is cleared.
+// the batch limit, count and the alignment of the rows of words: all a map call has to obey
+static Rule h2c448_rows_rule(ncg_ctx* ctx, const char* op, int count, size_t n, std::initializer_list<const void*> word_rows) {
+  int rc = NCG_OK;
+  if (n > 0x7fffffffu) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: batch too large", op);
+  else if (count != NCG_H2C_NU && count != NCG_H2C_RO) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: count must be 1 or 2", op);
+  else
+    for (const void* p : word_rows)
+      if ((uintptr_t)p & 3) rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: 56-byte rows must be 4-byte aligned", op);
+  return {op, rc};
+}
+// the calls that hash: the DST as well (out_len: 1 where the call fixes the length itself)
+static Rule h2c448_rule(ncg_ctx* ctx, const char* op, int count, size_t n, const void* dst, size_t dst_len, size_t out_len,
+                        std::initializer_list<const void*> word_rows) {
+  Rule r = h2c448_rows_rule(ctx, op, count, n, word_rows);
+  if (r.rc) return r;
+  if (dst_len < 1 || dst_len > 255) r.rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: dst_len %zu outside 1..255", op, dst_len);
+  else if (!dst) r.rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: NULL buffer (dst)", op);
+  else if (out_len < 1 || out_len > 65535) r.rc = set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: %s: out_len %zu outside 1..65535", op, out_len);
+  return r;
+}
+
+int ncg_xof_shake256_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst, size_t dst_len,
+                               size_t out_len, void* out_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "xof_shake256_batch", 1, n, dst, dst_len, out_len, {}), n, msg_off_dev, out_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, 512, st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c448_xof_batch((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, (uint32_t)out_len,
+                                     (uint8_t*)out_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_xof_shake256_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len, size_t out_len,
+                           void* out) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "xof_shake256_batch", 1, n, dst, dst_len, out_len, {}), n, msg_off, out);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "xof_shake256_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out, n * out_len);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_xof_shake256_batch_dev(ctx, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, out_len, hc.dev(o), ctx->stream));
+}
+int ncg_ed448_h2c_hash_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                 size_t dst_len, void* out_affine112_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "ed448_h2c_hash_batch", count, n, dst, dst_len, 1, {out_affine112_dev}), n, msg_off_dev, out_affine112_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c448_ws_bytes(n), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c448_hash((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, count,
+                                (uint32_t*)out_affine112_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_ed448_h2c_hash_batch(ncg_ctx* ctx, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                             void* out_affine112) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "ed448_h2c_hash_batch", count, n, dst, dst_len, 1, {}), n, msg_off, out_affine112);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed448_h2c_hash_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out_affine112, n * 112);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_h2c_hash_batch_dev(ctx, n, count, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o), ctx->stream));
+}
+int ncg_ed448_h2c_map_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* u56_dev, void* out_affine112_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c448_rows_rule(ctx, "ed448_h2c_map_batch", count, n, {u56_dev, out_affine112_dev}), n, u56_dev, out_affine112_dev);
+  NCG_HIP(ctx, ncg::h2c448_map((const uint32_t*)u56_dev, count, (uint32_t*)out_affine112_dev, (int)n, stream_of(ctx, stream)));
+  return NCG_OK;
+}
+int ncg_ed448_h2c_map_batch(ncg_ctx* ctx, size_t n, int count, const void* u56, void* out_affine112) {
+  NCG_BEGIN(ctx, h2c448_rows_rule(ctx, "ed448_h2c_map_batch", count, n, {}), n, u56, out_affine112);
+  HostCall hc(ctx);
+  const int in = hc.in(u56, n * (size_t)count * 56);
+  const int o = hc.out(out_affine112, n * 112);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_h2c_map_batch_dev(ctx, n, count, hc.dev(in), hc.dev(o), ctx->stream));
+}
+int ncg_ed448_h2c_hash_to_field_batch_dev(ncg_ctx* ctx, size_t n, int count, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                          size_t dst_len, void* out_u56_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "ed448_h2c_hash_to_field_batch", count, n, dst, dst_len, 1, {out_u56_dev}), n, msg_off_dev, out_u56_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c448_ws_bytes(n), st, &ws)) return rc;
+  NCG_HIP(ctx, ncg::h2c448_hash_to_field((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, count,
+                                         (uint32_t*)out_u56_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+int ncg_ed448_h2c_hash_to_field_batch(ncg_ctx* ctx, size_t n, int count, const void* msgs, const uint64_t* msg_off, const void* dst,
+                                      size_t dst_len, void* out_u56) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, "ed448_h2c_hash_to_field_batch", count, n, dst, dst_len, 1, {}), n, msg_off, out_u56);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, "ed448_h2c_hash_to_field_batch", n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out_u56, n * (size_t)count * 56);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(ncg_ed448_h2c_hash_to_field_batch_dev(ctx, n, count, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o),
+                                                         ctx->stream));
+}
+// the three calls that hash every message to one 56-byte row
+typedef hipError_t (*H2c448RowFn)(const uint8_t*, const uint64_t*, const uint8_t*, uint32_t, uint32_t*, int, uint8_t*, hipStream_t);
+static int h2c448_rows_dev(ncg_ctx* ctx, const char* op, H2c448RowFn fn, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev,
+                           const void* dst, size_t dst_len, void* out56_dev, void* stream) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, op, 1, n, dst, dst_len, 1, {out56_dev}), n, msg_off_dev, out56_dev);
+  const hipStream_t st = stream_of(ctx, stream);
+  uint8_t* ws;
+  if (int rc = h2c_ws(ctx, ncg::h2c448_ws_bytes(n), st, &ws)) return rc;
+  NCG_HIP(ctx, fn((const uint8_t*)msgs_dev, msg_off_dev, (const uint8_t*)dst, (uint32_t)dst_len, (uint32_t*)out56_dev, (int)n, ws, st));
+  return NCG_OK;
+}
+static int h2c448_rows_host(ncg_ctx* ctx, const char* op, H2c448RowFn fn, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst,
+                            size_t dst_len, void* out56) {
+  NCG_BEGIN(ctx, h2c448_rule(ctx, op, 1, n, dst, dst_len, 1, {}), n, msg_off, out56);
+  std::vector<uint64_t> rel;
+  HostCall hc(ctx);
+  int msg, off;
+  if (int rc = stage_msgs(hc, op, n, msgs, msg_off, rel, &msg, &off)) return rc;
+  const int o = hc.out(out56, n * 56);
+  if (int rc = hc.stage()) return rc;
+  return hc.finish(h2c448_rows_dev(ctx, op, fn, n, hc.dev(msg), hc.dev<const uint64_t>(off), dst, dst_len, hc.dev(o), ctx->stream));
+}
+int ncg_ed448_h2c_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                           size_t dst_len, void* out56_dev, void* stream) {
+  return h2c448_rows_dev(ctx, "ed448_h2c_hash_to_scalar_batch", ncg::h2c448_hash_to_scalar, n, msgs_dev, msg_off_dev, dst, dst_len, out56_dev, stream);
+}
+int ncg_ed448_h2c_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                       void* out56) {
+  return h2c448_rows_host(ctx, "ed448_h2c_hash_to_scalar_batch", ncg::h2c448_hash_to_scalar, n, msgs, msg_off, dst, dst_len, out56);
+}
+int ncg_decaf448_hash_to_group_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                         size_t dst_len, void* out56_dev, void* stream) {
+  return h2c448_rows_dev(ctx, "decaf448_hash_to_group_batch", ncg::decaf448_hash_to_group, n, msgs_dev, msg_off_dev, dst, dst_len, out56_dev, stream);
+}
+int ncg_decaf448_hash_to_group_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                     void* out56) {
+  return h2c448_rows_host(ctx, "decaf448_hash_to_group_batch", ncg::decaf448_hash_to_group, n, msgs, msg_off, dst, dst_len, out56);
+}
+int ncg_decaf448_hash_to_scalar_batch_dev(ncg_ctx* ctx, size_t n, const void* msgs_dev, const uint64_t* msg_off_dev, const void* dst,
+                                          size_t dst_len, void* out56_dev, void* stream) {
+  return h2c448_rows_dev(ctx, "decaf448_hash_to_scalar_batch", ncg::decaf448_hash_to_scalar, n, msgs_dev, msg_off_dev, dst, dst_len, out56_dev, stream);
+}
+int ncg_decaf448_hash_to_scalar_batch(ncg_ctx* ctx, size_t n, const void* msgs, const uint64_t* msg_off, const void* dst, size_t dst_len,
+                                      void* out56) {
+  return h2c448_rows_host(ctx, "decaf448_hash_to_scalar_batch", ncg::decaf448_hash_to_scalar, n, msgs, msg_off, dst, dst_len, out56);
+}
+// The pieces of h2c448.hpp on raw words, in the style of ncg_h2c_check: rows of 42 words in and out
+int ncg_h2c448_check(ncg_ctx* ctx, int op, size_t n, const void* a, void* out) {
+  const Rule rule = {"h2c448_check", !ctx || n <= (1u << 24) ? NCG_OK
+                                         : set_err(ctx, NCG_ERR_INVALID_ARG, "noble-gpu: h2c448_check: batch too large (max 2^24)")};
+  NCG_BEGIN(ctx, rule, n, a, out);
+  HostCall hc(ctx);
+  const int da = hc.in(a, n * 168);
+  const int o = hc.out(out, n * 168, true);
+  if (int rc = hc.stage()) return rc;
+  NCG_HIP(ctx, ncg::h2c448_check(op, hc.dev<const uint32_t>(da), hc.dev<uint32_t>(o), (int)n, ctx->stream));
+  return hc.finish(NCG_OK);
+}
+
 // ---- bls12-381 pairings (pairing.hip).  The _dev form keeps the verdict word, the group offsets and the Miller values in
 // ctx->pair_ws, never in ctx->scratch.
 static Rule pairing_rule(ncg_ctx* ctx, size_t n_pairs, size_t n_groups, const uint32_t* off, int flags) {

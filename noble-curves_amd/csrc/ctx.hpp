@@ -86,7 +86,8 @@ struct ncg_ctx {
   void* oprf_ws = nullptr;
   size_t oprf_ws_bytes = 0;
   // RFC 9380 suites for secp256k1 and edwards25519 (h2c_suites.hip): DST', the uniform bytes, the reduced elements and the mapped points
-  // of one call: one call at a time per context, on whatever stream
+  // of one call: one call at a time per context, on whatever stream.  The edwards448 / decaf448 suites (h2c448.hip) keep their staged
+  // DST, uniform bytes and reduced elements here as well, under the same rule
   void* h2c_ws = nullptr;
   size_t h2c_ws_bytes = 0;
   // pairings (pairing.hip): the verdict word, the group offsets and one Miller value per pair; one call at a time

@@ -410,6 +410,35 @@ int h2c_map_host(int suite, const uint32_t* u, int in_words, int count, uint32_t
 int h2c_hash_host(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out, uint8_t* inf);
 int h2c_check_host(int op, const uint32_t* a, uint32_t* out);
 
+// RFC 9380 for edwards448 (edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_) and the hash side of decaf448 (h2c448.hip).  Messages are a blob with
+// n + 1 offsets; dst_host is a HOST pointer (1..255 bytes); elements, scalars and encodings are 14 LE words, affine points x || y 28.
+// ws: h2c448_ws_bytes(n) bytes of device memory (512 for h2c448_xof_batch); h2c448_map needs none.
+size_t h2c448_ws_bytes(size_t n);
+hipError_t h2c448_xof_batch(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t out_len, uint8_t* out,
+                            int n, uint8_t* ws, hipStream_t st);
+hipError_t h2c448_hash_to_field(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, int count, uint32_t* out_u,
+                                int n, uint8_t* ws, hipStream_t st);
+hipError_t h2c448_map(const uint32_t* u, int count, uint32_t* out, int n, hipStream_t st);
+hipError_t h2c448_hash(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, int count, uint32_t* out, int n,
+                       uint8_t* ws, hipStream_t st);
+hipError_t h2c448_hash_to_scalar(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t* out, int n,
+                                 uint8_t* ws, hipStream_t st);
+hipError_t decaf448_hash_to_group(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t* out, int n,
+                                  uint8_t* ws, hipStream_t st);
+hipError_t decaf448_hash_to_scalar(const uint8_t* msgs, const uint64_t* off, const uint8_t* dst_host, uint32_t dst_len, uint32_t* out, int n,
+                                   uint8_t* ws, hipStream_t st);
+// the pieces of h2c448.hpp on raw words (ncg_h2c448_check): 42 words per row of a and out; an unknown op writes nothing
+hipError_t h2c448_check(int op, const uint32_t* d_a, uint32_t* d_out, int n, hipStream_t st);
+// one row each on the CPU; dst as the caller gave it
+void h2c448_xof_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out);
+void h2c448_hash_to_field_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out_u);
+void h2c448_hash_to_scalar_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14);
+void h2c448_map_host(const uint32_t* u, int count, uint32_t* out28);
+void h2c448_hash_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out28);
+void decaf448_hash_to_group_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14);
+void decaf448_hash_to_scalar_host(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14);
+int h2c448_check_host(int op, const uint32_t* a, uint32_t* out);
+
 // bls12-381 pairings (pairing.hip).  ws: PAIRING_WS_WORDS words per pair; off: n_groups + 1 ascending pair offsets (device);
 // first_bad: one 64-bit word, all ones or (index << 8 | PairingBad code) of the first refused pair after pairing_miller;
 // pairing_finish multiplies each group's Miller values (largest_group decides the number of passes), exponentiates and stores

@@ -32,6 +32,7 @@
 #include "ed448_sign.hip"
 #include "oprf.hip"
 #include "h2c_suites.hip"
+#include "h2c448.hip"
 
 using namespace ncg;
 
@@ -612,6 +613,46 @@ int ht_h2c_hash(int suite, const uint8_t* msg, uint64_t len, const uint8_t* dst,
   return h2c_hash_host(suite, msg, len, dst, dst_len, count, out, inf);
 }
 int ht_h2c_check(int op, const uint32_t* a, uint32_t* out) { return h2c_check_host(op, a, out); }
+
+// RFC 9380 for edwards448 and the hash side of decaf448 on the CPU twins of h2c448.hip, one row per call: dst as the caller has it
+// (1..255 bytes), count 1 or 2, elements, scalars and encodings 14 LE words, points x || y 28 words; -1 for an argument outside these.
+// ht_h2c448_check: the pieces of ncg_h2c448_check (42 words in and out), -1 for an unknown op.
+int ht_h2c448_xof(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t out_len, uint8_t* out) {
+  if (dst_len < 1 || dst_len > 255 || out_len < 1 || out_len > 65535) return -1;
+  h2c448_xof_host(msg, len, dst, dst_len, out_len, out);
+  return 0;
+}
+int ht_h2c448_hash_to_field(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out_u) {
+  if (dst_len < 1 || dst_len > 255 || (count != 1 && count != 2)) return -1;
+  h2c448_hash_to_field_host(msg, len, dst, dst_len, count, out_u);
+  return 0;
+}
+int ht_h2c448_hash_to_scalar(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  h2c448_hash_to_scalar_host(msg, len, dst, dst_len, out14);
+  return 0;
+}
+int ht_h2c448_map(const uint32_t* u, int count, uint32_t* out28) {
+  if (count != 1 && count != 2) return -1;
+  h2c448_map_host(u, count, out28);
+  return 0;
+}
+int ht_h2c448_hash(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, int count, uint32_t* out28) {
+  if (dst_len < 1 || dst_len > 255 || (count != 1 && count != 2)) return -1;
+  h2c448_hash_host(msg, len, dst, dst_len, count, out28);
+  return 0;
+}
+int ht_h2c448_decaf_hash_to_group(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  decaf448_hash_to_group_host(msg, len, dst, dst_len, out14);
+  return 0;
+}
+int ht_h2c448_decaf_hash_to_scalar(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint32_t dst_len, uint32_t* out14) {
+  if (dst_len < 1 || dst_len > 255) return -1;
+  decaf448_hash_to_scalar_host(msg, len, dst, dst_len, out14);
+  return 0;
+}
+int ht_h2c448_check(int op, const uint32_t* a, uint32_t* out) { return h2c448_check_host(op, a, out); }
 
 // The ristretto255 OPRF on the CPU twins of oprf.hip, one row per call unless n is given: elements and scalars 8 LE words, outputs 64
 // bytes, dst as the caller has it (1..255 bytes, -1 otherwise), flags as ncg_oprf_mul_batch without ONE_SCALAR.  The row functions

@@ -5,8 +5,8 @@ An element is held as an Edwards representative - an Ed448 affine point x || y, 
 EdwardsPoint; decoding, encoding, equals, the Elligator map and every multiply run in HIP kernels (`ncg_decaf448_*`, and the
 `ncg_ed448_*` entry points for the group law on representatives).  The shim does the argument checks of the reference and raises
 its messages; for a row the device refused, the field's range error (s >= p), 'invalid decaf448 encoding 1' (s odd) and
-'encoding 2' are told apart with host integers.  `expand_message_xof` over SHAKE256 runs on the host (hashlib), the map on the
-device.  Batch forms take and return encodings (56 bytes): only bytes cross.  Two elements are compared only through `equals` or
+'encoding 2' are told apart with host integers.  `expand_message_xof` over SHAKE256 runs on the host (hashlib) and the map on the
+device by default; with `device_hash=True` the hash runs on the device too, and `hashToScalar_batch` always does.  Batch forms take and return encodings (56 bytes): only bytes cross.  Two elements are compared only through `equals` or
 their encodings.
 
 Not provided: an MSM, a fixed-base table (multiplyBase runs the variable-base kernel on the base point), `decaf448_oprf`, FROST.
@@ -16,7 +16,7 @@ import hashlib
 import numpy as np
 
 from ._native import get_engine
-from .ed448 import N, P
+from .ed448 import N, P, xof_oversize_dst
 
 DEFAULT_DST = "decaf448_XOF:SHAKE256_D448MAP_RO_"
 DST_SCALAR = "HashToScalar-"
@@ -230,8 +230,7 @@ def expand_message_xof(msg, DST, lenInBytes, k):
     ceil(2 k / 8))"""
     if not isinstance(msg, (bytes, bytearray, memoryview, np.ndarray)):
         raise TypeError("expected Uint8Array, got type=%s" % type(msg).__name__)
-    if len(DST) > 255:
-        DST = hashlib.shake_256(b"H2C-OVERSIZE-DST-" + DST).digest((2 * k + 7) // 8)
+    DST = xof_oversize_dst(DST, k)
     return hashlib.shake_256(bytes(msg) + lenInBytes.to_bytes(2, "big") + DST + bytes([len(DST)])).digest(lenInBytes)
 
 
@@ -250,17 +249,47 @@ def deriveToCurve(bytes112, engine=None):
     return Point(eng.decaf448_decode_batch(eng.decaf448_from_uniform_batch(_rows([bytes112], 112)))[0][0])
 
 
-def hashToCurve_batch(msgs, DST=None, engine=None):
-    """decaf448_hasher.hashToCurve(msg, { DST }).toBytes() for every message: expand_message_xof over SHAKE256 here (112 bytes,
-    k = 224), the map on the device"""
+def _msgs(msgs):
+    for m in msgs:
+        if not isinstance(m, (bytes, bytearray, memoryview, np.ndarray)):
+            raise TypeError("expected Uint8Array, got type=%s" % type(m).__name__)
+    return [bytes(m) for m in msgs]
+
+
+def hashToCurve_batch(msgs, DST=None, engine=None, device_hash=False):
+    """decaf448_hasher.hashToCurve(msg, { DST }).toBytes() for every message: expand_message_xof over SHAKE256 (112 bytes, k = 224)
+    here with hashlib and the map on the device, or with device_hash=True the hash on the device as well, one call for the batch
+    (`ncg_decaf448_hash_to_group_batch`)"""
     dst = _dst(DST, DEFAULT_DST)
-    return deriveToCurve_batch([expand_message_xof(m, dst, 112, 224) for m in msgs], engine)
+    if not device_hash:
+        return deriveToCurve_batch([expand_message_xof(m, dst, 112, 224) for m in msgs], engine)
+    msgs = _msgs(msgs)
+    if not msgs:
+        return []
+    return [r.tobytes() for r in (engine or get_engine()).decaf448_hash_to_group_batch(msgs, xof_oversize_dst(dst, 224))]
 
 
-def hashToCurve(msg, DST=None, engine=None):
-    return deriveToCurve(expand_message_xof(msg, _dst(DST, DEFAULT_DST), 112, 224), engine)
+def hashToCurve(msg, DST=None, engine=None, device_hash=False):
+    if not device_hash:
+        return deriveToCurve(expand_message_xof(msg, _dst(DST, DEFAULT_DST), 112, 224), engine)
+    eng = engine or get_engine()
+    enc = eng.decaf448_hash_to_group_batch(_msgs([msg]), xof_oversize_dst(_dst(DST, DEFAULT_DST), 224))
+    return Point(eng.decaf448_decode_batch(enc)[0][0])
 
 
-def hashToScalar(msg, DST=None):
-    """decaf448_hasher.hashToScalar: 64 bytes of expand_message_xof (k = 256), little-endian, mod n.  Host only."""
+def hashToScalar_batch(msgs, DST=None, engine=None):
+    """decaf448_hasher.hashToScalar for every message, on the device (`ncg_decaf448_hash_to_scalar_batch`): 64 bytes of
+    expand_message_xof (k = 256, so an oversize DST is compressed to 64 bytes), little-endian, mod n"""
+    dst = _dst(DST, DST_SCALAR)
+    msgs = _msgs(msgs)
+    if not msgs:
+        return []
+    out = (engine or get_engine()).decaf448_hash_to_scalar_batch(msgs, xof_oversize_dst(dst, 256))
+    return [int.from_bytes(out[i].tobytes(), "little") for i in range(len(msgs))]
+
+
+def hashToScalar(msg, DST=None, engine=None, device_hash=False):
+    """decaf448_hasher.hashToScalar: 64 bytes of expand_message_xof (k = 256), little-endian, mod n.  On the host by default."""
+    if device_hash:
+        return hashToScalar_batch([msg], DST, engine)[0]
     return int.from_bytes(expand_message_xof(msg, _dst(DST, DST_SCALAR), 64, 256), "little") % N

@@ -20,7 +20,11 @@ range errors of multiply / multiplyUnsafe raised here.
 
 decaf448 and its hasher, the prime-order group of this curve, live in `noble_curves_amd.decaf448`.
 
-Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), `ed448_hasher` (hash-to-curve), FROST
+`ed448_hasher`: the reference's RFC 9380 hasher (edwards448_XOF:SHAKE256_ELL2_RO_ / _NU_, ed448.ts:313-417) with `*Batch` forms; the
+hash (expand_message_xof over SHAKE256), the two Elligator maps, the sum, the cofactor and the affine conversion run on the device
+(`ncg_ed448_h2c_*`).  Points are affine (x, y) pairs, the identity `ed448_Point.ZERO` = (0, 1).
+
+Out of scope, not provided by this module: `E448` (the NIST Edwards model of Curve448), FROST
 and OPRF suites, an MSM over Ed448, and a fixed-base table (multiplyBase runs the variable-base kernel on the base
 point).
 """
@@ -28,6 +32,7 @@ import hashlib
 
 import numpy as np
 
+from . import h2c as _h2c
 from ._native import ED448_KEY_BYTES, get_engine
 
 P = 2**448 - 2**224 - 1
@@ -306,7 +311,9 @@ ed448ph = _EdDSA(True)
 
 
 class ed448_Point:
-    """batch forms of the reference's ed448.Point on ENCODINGS (57 bytes)"""
+    """batch forms of the reference's ed448.Point on ENCODINGS (57 bytes); decoded points are affine (x, y) pairs"""
+
+    ZERO = (0, 1)
 
     @staticmethod
     def fromBytes_batch(encodings, engine=None):
@@ -374,3 +381,62 @@ class ed448_Point:
         pa[~np.asarray(oka, bool), 56] = 1
         out = eng.ed448_encode_batch(eng.ed448_add_pairs_batch(pa, pb, subtract))
         return _result(out, np.asarray(oka, bool) & np.asarray(okb, bool))
+
+
+def xof_oversize_dst(dst, k):
+    """the oversize rule of expand_message_xof over SHAKE256 (hash-to-curve.ts:263-266), which the device leaves to its caller: a DST
+    above 255 bytes is replaced by SHAKE256("H2C-OVERSIZE-DST-" || DST, ceil(2 k / 8)) - 56 bytes for k = 224, 64 for k = 256"""
+    return _xof_compress(b"H2C-OVERSIZE-DST-" + dst, k) if len(dst) > 255 else dst
+
+
+def _xof_compress(tagged, k):
+    return hashlib.shake_256(tagged).digest((2 * k + 7) // 8)
+
+
+class _Ed448Hasher(_h2c.H2CDeviceHasher):
+    """createHasher(ed448_Point, map_to_curve_elligator2_edwards448, defaults) (hash-to-curve.ts:441-530; ed448.ts:408-417): m = 1,
+    k = 224, expand = 'xof' over SHAKE256, everything from the message bytes on running on the device (`ncg_ed448_h2c_*`).  The
+    `defaults` snapshot, the DST override and the single-call forms are H2CDeviceHasher's; points are affine (x, y) pairs."""
+
+    def __init__(self, engine=None):
+        self.Point, self._engine = ed448_Point, engine
+        self._defaults = {"DST": "edwards448_XOF:SHAKE256_ELL2_RO_", "encodeDST": "edwards448_XOF:SHAKE256_ELL2_NU_", "p": P, "m": 1,
+                          "k": 224, "expand": "xof", "hash": "shake256"}
+
+    def _compress_dst(self, tagged):
+        return _xof_compress(tagged, self._defaults["k"])
+
+    @staticmethod
+    def _pairs(out):
+        return [(int.from_bytes(out[i, :56].tobytes(), "little"), int.from_bytes(out[i, 56:].tobytes(), "little")) for i in range(out.shape[0])]
+
+    def _hash(self, msgs, dst, count):
+        msgs = [_h2c._msg_bytes(m) for m in msgs]
+        return self._pairs(self._eng().ed448_h2c_hash_batch(msgs, dst, count)) if msgs else []
+
+    def hashToCurveBatch(self, msgs, options=None):
+        return self._hash(msgs, self._dst(options, self._defaults["DST"]), 2)
+
+    def encodeToCurveBatch(self, msgs, options=None):
+        return self._hash(msgs, self._dst(options, self._defaults["encodeDST"]), 1)
+
+    def mapToCurveBatch(self, scalars_list):
+        raw = bytearray()
+        for u in scalars_list:
+            if not isinstance(u, int) or isinstance(u, bool):
+                raise ValueError("expected bigint (m=1)")
+            raw += (u % P).to_bytes(56, "little")
+        if not raw:
+            return []
+        return self._pairs(self._eng().ed448_h2c_map_batch(np.frombuffer(bytes(raw), dtype=np.uint8).reshape(-1, 56), 1))
+
+    def hashToScalarBatch(self, msgs, options=None):
+        dst = self._dst(options, "HashToScalar-")                # _DST_scalar (hash-to-curve.ts:412, :523)
+        msgs = [_h2c._msg_bytes(m) for m in msgs]
+        if not msgs:
+            return []
+        out = self._eng().ed448_h2c_hash_to_scalar_batch(msgs, dst)
+        return [int.from_bytes(out[i].tobytes(), "little") for i in range(len(msgs))]
+
+
+ed448_hasher = _Ed448Hasher()

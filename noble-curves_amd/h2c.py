@@ -141,26 +141,23 @@ def _msg_bytes(x):
     return _bytes(x, "msg")
 
 
-def _norm_dst(DST, H):
-    """normDST (hash-to-curve.ts:160-167) and the oversize rule of expand_message_xmd (:202), which the device leaves to its caller"""
+def _norm_dst(DST, compress):
+    """normDST (hash-to-curve.ts:160-167) and the oversize rule of the expander (:202, :263-266), which the device leaves to its
+    caller: `compress` takes "H2C-OVERSIZE-DST-" || DST and gives the DST that replaces it"""
     if not isinstance(DST, (str, bytes, bytearray, memoryview)):
         raise TypeError("DST must be Uint8Array or ascii string")
     dst = DST.encode("ascii") if isinstance(DST, str) else bytes(DST)
     if len(dst) == 0:
         raise ValueError("DST must be non-empty")
     if len(dst) > 255:
-        dst = H(b"H2C-OVERSIZE-DST-" + dst).digest()
+        dst = compress(b"H2C-OVERSIZE-DST-" + dst)
     return dst
 
 
-class H2CSuiteHasher:
-    """createHasher(Point, mapToCurve, defaults) (hash-to-curve.ts:441-530) for a suite that runs on the device from the message
-    bytes on: m = 1, k = 128, expand = 'xmd'.  The `*Batch` forms take lists and make one call into the library each."""
-
-    def __init__(self, Point, suite, DST, encodeDST, hash_name, engine=None):
-        self.Point, self._suite, self._engine = Point, suite, engine
-        self._H = getattr(hashlib, hash_name)
-        self._defaults = {"DST": DST, "encodeDST": encodeDST, "p": Point.Fp.ORDER, "m": 1, "k": 128, "expand": "xmd", "hash": hash_name}
+class H2CDeviceHasher:
+    """What the createHasher mirrors that run on the device from the message bytes on have in common (hash-to-curve.ts:441-530):
+    the `defaults` snapshot, the DST override, the engine and the reference's single-call forms over the `*Batch` forms.  A subclass
+    sets `Point`, `_engine` and `_defaults`, and gives `_compress_dst` (the oversize rule of its expander) and the four `*Batch` forms."""
 
     @property
     def defaults(self):
@@ -172,10 +169,36 @@ class H2CSuiteHasher:
         DST = default
         if options is not None and options.get("DST") is not None:
             DST = options["DST"]
-        return _norm_dst(DST, self._H)
+        return _norm_dst(DST, self._compress_dst)
 
     def _eng(self):
         return self._engine or get_engine()
+
+    # ---- the reference's single-call forms -----------------------------------------------------
+    def hashToCurve(self, msg, options=None):
+        return self.hashToCurveBatch([msg], options)[0]
+
+    def encodeToCurve(self, msg, options=None):
+        return self.encodeToCurveBatch([msg], options)[0]
+
+    def mapToCurve(self, scalars):
+        return self.mapToCurveBatch([scalars])[0]
+
+    def hashToScalar(self, msg, options=None):
+        return self.hashToScalarBatch([msg], options)[0]
+
+
+class H2CSuiteHasher(H2CDeviceHasher):
+    """createHasher(Point, mapToCurve, defaults) (hash-to-curve.ts:441-530) for a suite that runs on the device from the message
+    bytes on: m = 1, k = 128, expand = 'xmd'.  The `*Batch` forms take lists and make one call into the library each."""
+
+    def __init__(self, Point, suite, DST, encodeDST, hash_name, engine=None):
+        self.Point, self._suite, self._engine = Point, suite, engine
+        self._H = getattr(hashlib, hash_name)
+        self._defaults = {"DST": DST, "encodeDST": encodeDST, "p": Point.Fp.ORDER, "m": 1, "k": 128, "expand": "xmd", "hash": hash_name}
+
+    def _compress_dst(self, tagged):
+        return self._H(tagged).digest()
 
     def _points(self, out, inf):
         return [self.Point._from_wire(out[i], bool(inf[i])) for i in range(out.shape[0])]
@@ -209,19 +232,6 @@ class H2CSuiteHasher:
             return []
         out = self._eng().h2c_hash_to_scalar_batch(self._suite, msgs, dst)
         return [int.from_bytes(bytes(out[i]), "little") for i in range(len(msgs))]
-
-    # ---- the reference's single-call forms -----------------------------------------------------
-    def hashToCurve(self, msg, options=None):
-        return self.hashToCurveBatch([msg], options)[0]
-
-    def encodeToCurve(self, msg, options=None):
-        return self.encodeToCurveBatch([msg], options)[0]
-
-    def mapToCurve(self, scalars):
-        return self.mapToCurveBatch([scalars])[0]
-
-    def hashToScalar(self, msg, options=None):
-        return self.hashToScalarBatch([msg], options)[0]
 
 
 secp256k1_hasher = H2CSuiteHasher(_curve.secp256k1_Point, H2C_SECP256K1, "secp256k1_XMD:SHA-256_SSWU_RO_", "secp256k1_XMD:SHA-256_SSWU_NU_", "sha256")
